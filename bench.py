@@ -9,17 +9,23 @@ sharded by stride across ranks (no data-path collective during the solve); the
 RNG is keyed by the global point index so results do not depend on N.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config B|B_grid|C|D|E|A]
-                    [--scaling weak|strong]
+                    [--scaling weak|strong] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...   (same ranks, external launcher)
 
 With --gpus N > 1 and no WORLD_SIZE in the environment, bench.py starts the N ranks
 itself (N child processes, rank r on GPU r, RCCL); under a launcher --gpus must equal
 WORLD_SIZE or it exits non-zero.
 
+A plain run sets up, warms up, times the K steps and prints the line (headline figure,
+its per-kernel split and the rooflines derived from the timed steps' own counters).
+--dump-outputs DIR also writes what the last timed step computed (DIR/p.npy, DIR/grad.npy).
+--full adds the legs that take runs of their own: the strong line and the stride-8 shard,
+the projection wall time and the CPU baseline (each with its --no-... switch).
+
 Scaling: "weak" (default for B) gives every rank one 64k-point batch of an
 N x 64k projection; "strong" (default for the grid configs C, D, E -- BASELINE's
 8-GPU configs are fixed-size problems) shards the config's fixed point set.
-Config B's line carries both views: `value` (weak) and a `strong` object (the fixed
+With --full, config B's line carries both views: `value` (weak) and a `strong` object (the fixed
 65398-point projection stride-sharded over the N ranks + its all-gather); at N=1 it
 also times `strong_shard_ms`, the 1/8 stride shard rank 0 of an 8-GPU strong run
 solves, alone on this GPU (the per-rank latency that bounds 8-GPU strong scaling); the
@@ -61,6 +67,13 @@ def parse():
     ap.add_argument("--config", default="B", help="A, B, B_grid, C, D or E (SURVEY.md section 8(d))")
     ap.add_argument("--scaling", default=None, choices=["weak", "strong"])
     ap.add_argument("--points", type=int, default=65536, help="config B: random points per rank (weak)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's outputs (the full field every rank "
+                         "holds) as DIR/p.npy and DIR/grad.npy, float32; above 64 MB a fixed, seeded row sample")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure: strong line and stride-8 shard, "
+                         "projection wall time, CPU baseline (see --no-strong, --no-projection-wall, "
+                         "--no-cpu-baseline)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-threads", type=int, default=0)
     ap.add_argument("--cpu-budget-s", type=float, default=15.0)
@@ -309,18 +322,22 @@ def cpu_baseline(cfg, n_threads, budget_s):
     }
 
 
-def timed_projections(scene, x, params, base, stride, steps, warmup, blocking, world, dist, torch, gather=None):
+def timed_projections(scene, x, params, base, stride, steps, warmup, blocking, world, dist, torch, gather=None,
+                      last=None):
     """Time `steps` projections of the points `x` (global indices base + i * stride),
     each followed by `gather(p, grad)` (the RCCL all-gather for N > 1), bracketed by a
     barrier + device sync on both sides; returns (max-over-ranks seconds, per-solve
     stats).  One projection stays in flight behind the one whose counters are read
-    (device counters, copied per solve; wos_solve_stats waits only for that solve)."""
+    (device counters, copied per solve; wos_solve_stats waits only for that solve).
+    A list passed as `last` receives the [p, grad] of the last step."""
     sync = torch.cuda.synchronize if x.device.type == "cuda" else (lambda: None)
 
     def step():
         p, g, st = scene.solve(x, params, index_base=base, index_stride=stride, sync=blocking)
         if gather is not None:
             gather(p, g)
+        if last is not None:
+            last[:] = [p, g]
         return st["ticket"]
 
     for _ in range(warmup):
@@ -345,6 +362,25 @@ def timed_projections(scene, x, params, base, stride, steps, warmup, blocking, w
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     return elapsed, stats
+
+
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, cap_bytes=DUMP_CAP_BYTES, seed=0):
+    """--dump-outputs: every array (same leading length, one row per query point) as
+    <out_dir>/<name>.npy in float32.  When they exceed `cap_bytes` together, the same fixed
+    rows of each are kept (seeded choice, ascending), so two runs sample the same points."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    n = next(iter(arrays.values())).shape[0]
+    total = sum(v.nbytes for v in arrays.values())
+    if total > cap_bytes:
+        m = int(cap_bytes // (total // n + 1))
+        rows = np.sort(np.random.default_rng(seed).choice(n, m, replace=False))
+        arrays = {k: v[rows] for k, v in arrays.items()}
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
 
 
 def reduce_steps(steps_rec, steps_all, world, dist, torch, dev):
@@ -441,8 +477,17 @@ def main():
     x = torch.from_numpy(local).to(dev)
     gather = wdist.make_gather(world, dist, n_local, n_pad, dim, dev, torch)
 
+    last = []
     elapsed, stats = timed_projections(scene, x, params, rank, world, a.steps, a.warmup, a.blocking,
-                                       world, dist, torch, gather)
+                                       world, dist, torch, gather, last)
+    if a.dump_outputs and rank == 0:
+        if gather is None:
+            p_out, g_out = last
+        else:
+            # rank r's block holds points r, r + N, ...: the view sharded_projection returns
+            field = gather.buf.view(world, n_pad, 1 + dim).transpose(0, 1).reshape(world * n_pad, 1 + dim)[:n_all]
+            p_out, g_out = field[:, 0], field[:, 1:]
+        dump_outputs(a.dump_outputs, {"p": p_out.cpu().numpy(), "grad": g_out.cpu().numpy()})
     steps_rec = steps_all = rej_iters = 0
     kernel_ms, walk_ms, fb_ms, fold_ms, walk_kernel_steps, launches = [], [], [], [], 0, 0
     for st in stats:
@@ -460,11 +505,12 @@ def main():
     steps_rec, steps_all = reduce_steps(steps_rec, steps_all, world, dist, torch, dev)
 
     strong = shard = None
-    if a.config == "B" and scaling == "weak" and not a.no_strong:
+    run_strong = a.full and not a.no_strong
+    if run_strong and a.config == "B" and scaling == "weak":
         strong = strong_projection(a, scene, params, world, rank, dim, dist, torch, dev, workloads)
         if world == 1:
             shard = shard_projection(a, scene, params, workloads.config_by_name("B")["points"], torch, dev)
-    elif scaling == "strong" and world == 1 and not a.no_strong and a.config != "A":
+    elif run_strong and scaling == "strong" and world == 1 and a.config != "A":
         # the fixed-size configs BASELINE runs on 8 GPUs (D, E; C alike): rank 0's 1/8 shard
         shard = shard_projection(a, scene, params, pts_all, torch, dev)
 
@@ -550,7 +596,7 @@ def main():
                                   "wait_any_frac": sq["wait_any_frac"], "wait_inst_frac": sq["wait_inst_frac"],
                                   "active_frac": sq.get("active_frac"),
                                   "source": f"{sq['file']}: {sq['source']}"}
-        if world == 1 and a.config == "B" and not a.no_projection_wall:
+        if a.full and world == 1 and a.config == "B" and not a.no_projection_wall:
             # the metric's second half: wall time of one whole projection call as the
             # time-stepper issues it (fresh Scene(sceneConfig, div) + wost, model_split.py:185-202)
             sys.path.insert(0, os.path.join(REPO, "tools"))
@@ -566,7 +612,7 @@ def main():
                         "reference: div/points via .cpu().numpy(), nested-list outputs, grad p back to the device; "
                         "scene_create_ms: Scene(cfg, div numpy); device_scene_reuse_ms: one Scene, set_source + wost",
             }
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             sys.path.insert(0, os.path.join(REPO, "tests"))
             import oracle_lib
             threads = a.cpu_threads or oracle_lib.default_threads()

@@ -107,7 +107,7 @@ def test_bench_gpus_flag_launches_ranks(world):
     the scaling run): exactly one JSON line, n_gpus == N, the strong line's step count
     covering the fixed point set once (3 stand-in steps per point, summed over ranks)."""
     r = _bench(["--gpus", str(world), "--steps", "3", "--warmup", "1", "--dist-backend", "gloo",
-                "--points", "4096", "--standin-scene"])
+                "--points", "4096", "--standin-scene", "--full"])
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, r.stdout
@@ -117,6 +117,47 @@ def test_bench_gpus_flag_launches_ranks(world):
     assert line["config"]["points"] > 0.9 * 4096 * world
     assert line["strong"]["n_gpus"] == world and line["strong"]["walk_steps_per_projection"] == 3 * 65398
     assert "stand-in" in line["engine"]
+
+
+@pytest.mark.parametrize("world", [1, 2])
+def test_bench_plain_run_is_lean_and_dumps_the_last_step(tmp_path, world):
+    """Without --full the line carries the headline figure only (no strong line, shard,
+    projection wall or CPU baseline), and --dump-outputs writes the full field of the last
+    timed step in global point order: the stand-in's p is the global index, grad (p, -p)."""
+    out = tmp_path / "dump"
+    r = _bench(["--gpus", str(world), "--steps", "2", "--warmup", "1", "--dist-backend", "gloo",
+                "--points", "1024", "--standin-scene", "--dump-outputs", str(out)])
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, r.stdout
+    line = json.loads(lines[0])
+    assert line["n_gpus"] == world and line["steps"] == 2 and line["ms_per_step"] > 0
+    assert not {"strong", "strong_shard", "strong_shard_ms", "projection_wall", "cpu_baseline"} & set(line)
+    n = line["config"]["points"]
+    p, g = np.load(out / "p.npy"), np.load(out / "grad.npy")
+    assert sorted(f.name for f in out.iterdir()) == ["grad.npy", "p.npy"]
+    assert p.dtype == np.float32 and g.dtype == np.float32 and p.shape == (n,) and g.shape == (n, 2)
+    np.testing.assert_array_equal(p, np.arange(n, dtype=np.float32))
+    np.testing.assert_array_equal(g, np.stack([p, -p], 1))
+
+
+def test_dump_outputs_samples_the_same_rows_above_the_cap(tmp_path):
+    """Outputs above the size cap are cut to one fixed, seeded set of rows, the same in
+    every array and from call to call; below it they are written whole."""
+    import bench
+    n = 1000
+    p = np.arange(n, dtype=np.float64)
+    g = np.stack([p, -p, 2 * p], 1)
+    bench.dump_outputs(str(tmp_path / "a"), {"p": p, "grad": g}, cap_bytes=4000)
+    bench.dump_outputs(str(tmp_path / "b"), {"p": p, "grad": g}, cap_bytes=4000)
+    pa, ga = np.load(tmp_path / "a" / "p.npy"), np.load(tmp_path / "a" / "grad.npy")
+    assert pa.dtype == np.float32 and ga.dtype == np.float32
+    assert 0 < pa.size < n and pa.nbytes + ga.nbytes <= 4000 and pa.nbytes + ga.nbytes > 3000
+    assert np.all(np.diff(pa) > 0)
+    np.testing.assert_array_equal(ga, np.stack([pa, -pa, 2 * pa], 1))
+    np.testing.assert_array_equal(pa, np.load(tmp_path / "b" / "p.npy"))
+    bench.dump_outputs(str(tmp_path / "c"), {"p": p, "grad": g}, cap_bytes=16 * n)
+    np.testing.assert_array_equal(np.load(tmp_path / "c" / "p.npy"), p.astype(np.float32))
 
 
 def test_bench_gpus_mismatch_with_launcher_fails():
@@ -141,7 +182,7 @@ def test_bench_gpus_flag_gloo_hip_engine():
     """`bench.py --gpus 2 --dist-backend gloo` on the GPU box, no torchrun: two ranks on
     GPU 0 through the HIP engine, one line with n_gpus 2."""
     r = _bench(["--gpus", "2", "--steps", "3", "--warmup", "1", "--points", "8192", "--dist-backend", "gloo",
-                "--no-cpu-baseline"], timeout=110)
+                "--full", "--no-cpu-baseline"], timeout=110)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -163,7 +204,7 @@ def test_bench_two_ranks_gloo_hip_engine(tmp_path, gpu):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(REPO, "bench.py"),
            "--gpus", "2", "--steps", "3", "--warmup", "1", "--points", "8192", "--dist-backend", "gloo",
-           "--no-cpu-baseline"]
+           "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, env=env, cwd=REPO, capture_output=True, text=True, timeout=110)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -34,9 +34,11 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from bench import lib_sha16  # noqa: E402
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-TAG = sys.argv[1] if len(sys.argv) > 1 and sys.argv[1] != "combine" else "r1"
-CONFIG = sys.argv[2] if len(sys.argv) > 2 else "B"
-SET = sys.argv[3] if len(sys.argv) > 3 and sys.argv[1] != "combine" else "issue"
+# the command line is this tool's only when it runs as a script; imported (tests/), the defaults hold
+ARGV = sys.argv if __name__ == "__main__" else sys.argv[:1]
+TAG = ARGV[1] if len(ARGV) > 1 and ARGV[1] != "combine" else "r1"
+CONFIG = ARGV[2] if len(ARGV) > 2 else "B"
+SET = ARGV[3] if len(ARGV) > 3 and ARGV[1] != "combine" else "issue"
 SETS = {
     "issue": ["SQ_INSTS_VALU", "SQ_INSTS_SALU", "SQ_INSTS_LDS", "SQ_INSTS_VMEM", "SQ_WAVE_CYCLES", "SQ_WAIT_ANY",
               "SQ_WAIT_INST_ANY", "SQ_ACTIVE_INST_ANY"],
