@@ -162,7 +162,7 @@ typedef struct wos_solver_params {
 #define WOS_SCHED_NO_DIR_GRID   0x8u  /* no Dirichlet-distance cell grid (2D): the culled scans alone */
 #define WOS_SCHED_NO_TAIL_SPREAD 0x10u /* no hand-over of walks to idle sibling waves once the queue is dry */
 #define WOS_SCHED_NO_GRID_SPREAD 0x20u /* reserved, no effect: grid-wide hand-over was measured slower than the
-                                          in-workgroup one and removed (ABI 9 keeps the bit so callers still build) */
+                                          in-workgroup one and removed (the bit stays defined so callers still build) */
 
 void wos_default_params(wos_solver_params *p);
 
@@ -203,6 +203,24 @@ int wos_solve(wos_scene *scene, const wos_solver_params *params,
               const float *pts, int64_t n, int64_t index_base, int64_t index_stride,
               float *p, float *grad, int32_t *n_est, int32_t *steps,
               wos_stats *stats, void *stream, uint32_t flags);
+
+/* wos_solve with the estimator's error bars (added within ABI 10: a new entry point, no struct or
+ * existing signature changes, so the version number stays): the reference keeps them on the same Welford
+ * pass as the means (SampleStatistics::update, walk_on_stars.h:863-868) and so does the fold kernel.
+ *   p_var[n]         getEstimatedSolutionVariance, solutionM2 / max(1, nSolutionEstimates - 1)
+ *   grad_var[n*dim]  getEstimatedGradientVariance, gradientM2[k] / max(1, nGradientEstimates - 1)
+ *                    (walk_on_stars.h:811-831; both counts are n_est here)
+ * Each may be NULL.  They are the per-walk sample variances of the point's walk contributions, in
+ * walk order, bit for bit the reference's float operations.  Masking rule: a variance is masked
+ * exactly like its mean -- p_var[i] is 0 wherever the distance mask or the domain test zeroes p[i]
+ * (grid.h:155-179), grad_var[i*dim+k] is 0 wherever grad[i*dim+k] is zeroed (grid.h:207-237), and
+ * both are 0 for points that are not estimated (n_est 0).  With one recorded walk M2 is 0.
+ * Pointers follow `flags` like p and grad (host, or WOS_PTRS_DEVICE with or without WOS_ASYNC).
+ * wos_solve is this call with both NULL: the same kernels, results and timings as before. */
+int wos_solve_var(wos_scene *scene, const wos_solver_params *params,
+                  const float *pts, int64_t n, int64_t index_base, int64_t index_stride,
+                  float *p, float *grad, float *p_var, float *grad_var, int32_t *n_est, int32_t *steps,
+                  wos_stats *stats, void *stream, uint32_t flags);
 
 /* Boundary value caching: the reference's `bvc(scene, solver, output)`
  * (bindings/zombie/demo/demo.cpp:265-363, exported at :396), replaced here.

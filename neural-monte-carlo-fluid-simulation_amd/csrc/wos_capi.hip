@@ -101,6 +101,9 @@ struct DevCtx {
   int32_t* d_nest = nullptr;
   int32_t* d_steps = nullptr;
   size_t ws_points = 0;
+  float* d_pvar = nullptr;     // staging of wos_solve_var's host outputs (only once one is asked for)
+  float* d_gvar = nullptr;
+  size_t ws_var_points = 0;
   uint64_t* d_jump = nullptr;  // PCG32 jump-ahead table (A_k, C_k), grow-only
   int n_jump = 0;
   float* d_tasks = nullptr;    // walk-task workspace (DevTasks arrays), grow-only
@@ -126,6 +129,9 @@ DevCtx g_ctx[kMaxDevices];  // never destroyed: the HIP runtime may be gone at p
 
 void ctx_free(DevCtx& c) {
   hipFree(c.d_pts); hipFree(c.d_p); hipFree(c.d_g); hipFree(c.d_nest); hipFree(c.d_steps);
+  hipFree(c.d_pvar); hipFree(c.d_gvar);
+  c.d_pvar = c.d_gvar = nullptr;
+  c.ws_var_points = 0;
   hipFree(c.d_jump); hipFree(c.d_tasks); hipFree(c.d_pstate); hipFree(c.d_counters); hipFree(c.d_rejtab);
   c.d_rejtab = nullptr;
   for (StatSlot& q : c.slot) {
@@ -660,6 +666,18 @@ int ensure_workspace(DevCtx& c, int dim, size_t npts) {
   return WOS_OK;
 }
 
+// the variance staging buffers, apart from the rest so a plain wos_solve allocates what it always did
+int ensure_var_workspace(DevCtx& c, size_t npts) {
+  if (npts <= c.ws_var_points) return WOS_OK;
+  hipFree(c.d_pvar); hipFree(c.d_gvar);
+  c.d_pvar = c.d_gvar = nullptr; c.ws_var_points = 0;
+  const size_t cap = npts + npts / 4 + 1024;
+  HIP_TRY(hipMalloc((void**)&c.d_pvar, cap * sizeof(float)));
+  HIP_TRY(hipMalloc((void**)&c.d_gvar, cap * 3 * sizeof(float)));  // either dimension
+  c.ws_var_points = cap;
+  return WOS_OK;
+}
+
 
 int ensure_tasks_in(float*& d_tasks, int64_t& task_cap, int32_t*& d_pstate, int64_t& pstate_cap, int dim,
                     int64_t tasks, int64_t points) {
@@ -899,6 +917,9 @@ struct SolveExtra {
   float* deriv = nullptr;
   bool force_estimate = false;
   int wave_prio = 0;  // the walk / fold kernels' waves at this issue priority (0..3)
+  // wos_solve_var: the variances out (host or device pointers like p and grad; null: not asked for)
+  float* p_var = nullptr;
+  float* grad_var = nullptr;
 };
 
 int solve_locked(wos_scene* s, const wos_solver_params* prm, const float* pts, int64_t n, int64_t index_base,
@@ -909,9 +930,9 @@ int solve_locked(wos_scene* s, const wos_solver_params* prm, const float* pts, i
 
 extern "C" {
 
-int wos_solve(wos_scene* s, const wos_solver_params* prm, const float* pts, int64_t n, int64_t index_base,
-              int64_t index_stride, float* p, float* grad, int32_t* n_est, int32_t* steps, wos_stats* stats,
-              void* stream, uint32_t flags) {
+int wos_solve_var(wos_scene* s, const wos_solver_params* prm, const float* pts, int64_t n, int64_t index_base,
+                  int64_t index_stride, float* p, float* grad, float* p_var, float* grad_var, int32_t* n_est,
+                  int32_t* steps, wos_stats* stats, void* stream, uint32_t flags) {
   if (!s || !prm) return fail(WOS_E_INVALID, "wos_solve: null scene/params");
   if (n < 0) return fail(WOS_E_INVALID, "wos_solve: negative point count");
   if (n > 0 && (!pts || !p || !grad)) return fail(WOS_E_INVALID, "wos_solve: null point/output buffer");
@@ -924,8 +945,17 @@ int wos_solve(wos_scene* s, const wos_solver_params* prm, const float* pts, int6
   HIP_TRY(hipSetDevice(s->device));
   DevCtx& c = g_ctx[s->device];
   std::lock_guard<std::mutex> lk(c.mu);
-  return solve_locked(s, prm, pts, n, index_base, index_stride, p, grad, n_est, steps, stats, stream, flags,
-                      SolveExtra{});
+  SolveExtra ex;
+  ex.p_var = p_var;
+  ex.grad_var = grad_var;
+  return solve_locked(s, prm, pts, n, index_base, index_stride, p, grad, n_est, steps, stats, stream, flags, ex);
+}
+
+int wos_solve(wos_scene* s, const wos_solver_params* prm, const float* pts, int64_t n, int64_t index_base,
+              int64_t index_stride, float* p, float* grad, int32_t* n_est, int32_t* steps, wos_stats* stats,
+              void* stream, uint32_t flags) {
+  return wos_solve_var(s, prm, pts, n, index_base, index_stride, p, grad, nullptr, nullptr, n_est, steps, stats,
+                       stream, flags);
 }
 
 }  // extern "C"
@@ -1009,6 +1039,8 @@ int solve_locked(wos_scene* s, const wos_solver_params* prm, const float* pts, i
   float* d_g = grad;
   int32_t* d_nest = n_est;
   int32_t* d_steps = steps;
+  float* d_pvar = ex.p_var;
+  float* d_gvar = ex.grad_var;
   const bool dev_ptrs = (flags & WOS_PTRS_DEVICE) != 0;
   if (!dev_ptrs && n > 0) {
     int rc = ensure_workspace(c, dim, (size_t)n);
@@ -1017,6 +1049,12 @@ int solve_locked(wos_scene* s, const wos_solver_params* prm, const float* pts, i
     d_pts = c.d_pts; d_p = c.d_p; d_g = c.d_g;
     d_nest = n_est ? c.d_nest : nullptr;
     d_steps = steps ? c.d_steps : nullptr;
+    if (ex.p_var || ex.grad_var) {
+      rc = ensure_var_workspace(c, (size_t)n);
+      if (rc != WOS_OK) return rc;
+      d_pvar = ex.p_var ? c.d_pvar : nullptr;
+      d_gvar = ex.grad_var ? c.d_gvar : nullptr;
+    }
   }
 
   // Points are solved in chunks whose walk tasks fit the task workspace.
@@ -1110,7 +1148,8 @@ int solve_locked(wos_scene* s, const wos_solver_params* prm, const float* pts, i
                               shmem_walk, geom_floats_walk, st));
     HIP_TRY(hipEventRecord(ev[2], st));
     HIP_TRY(wos::launch_fold(dim, dp, tk, nb, d_p + b0, d_g + b0 * dim, d_nest ? d_nest + b0 : nullptr,
-                             d_steps ? d_steps + b0 : nullptr, st));
+                             d_steps ? d_steps + b0 : nullptr, d_pvar ? d_pvar + b0 : nullptr,
+                             d_gvar ? d_gvar + b0 * dim : nullptr, st));
     HIP_TRY(hipEventRecord(ev[3], st));
   }
   HIP_TRY(hipEventRecord(q.ev1, st));
@@ -1121,6 +1160,10 @@ int solve_locked(wos_scene* s, const wos_solver_params* prm, const float* pts, i
     HIP_TRY(hipMemcpyAsync(grad, d_g, (size_t)n * dim * sizeof(float), hipMemcpyDeviceToHost, st));
     if (n_est) HIP_TRY(hipMemcpyAsync(n_est, d_nest, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     if (steps) HIP_TRY(hipMemcpyAsync(steps, d_steps, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    if (ex.p_var)
+      HIP_TRY(hipMemcpyAsync(ex.p_var, d_pvar, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (ex.grad_var)
+      HIP_TRY(hipMemcpyAsync(ex.grad_var, d_gvar, (size_t)n * dim * sizeof(float), hipMemcpyDeviceToHost, st));
   }
   HIP_TRY(hipEventRecord(q.done, st));
   HIP_TRY(hipEventRecord(c.done, st));

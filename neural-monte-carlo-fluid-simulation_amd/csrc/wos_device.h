@@ -4548,13 +4548,22 @@ __global__ __launch_bounds__(kFoldPoints) void wos_fold_kernel(const DevParams p
 // IEEE divisions per point (round 4, DESIGN).  Not for the derivative output (BVC's Dirichlet
 // samples, DevTasks::deriv): wos_fold_kernel keeps that.  Both dimensions since its staging is
 // software-pipelined (before that, 2D's five-float records folded faster one thread per point).
+//
+// VAR: quad lane c also carries its component's M2 on the same pass -- after mean += delta / fN,
+// M2 += delta * (val - mean), two separate operations (SampleStatistics::update,
+// walk_on_stars.h:863-868) -- and the outputs are the reference's getters (walk_on_stars.h:811-831):
+// pv_out[i] = solM2 / max(1, nSol - 1), gv_out[i*DIM+k] = gM2[k] / max(1, nGrad - 1) (nGrad == nSol
+// here), masked exactly like their means and 0 for points that are not estimated.  Either pointer
+// may be null.  VAR = false is the code without any of it.
 constexpr int kFold4Points = 64;  // points per 256-thread block
-template <int DIM>
+template <int DIM, bool VAR = false>
 __global__ __launch_bounds__(4 * kFold4Points) void wos_fold4_kernel(const DevParams prm, const DevTasks tk, int64_t n,
                                                                      float* __restrict__ p_out,
                                                                      float* __restrict__ g_out,
                                                                      int32_t* __restrict__ nest_out,
-                                                                     int32_t* __restrict__ steps_out) {
+                                                                     int32_t* __restrict__ steps_out,
+                                                                     float* __restrict__ pv_out,
+                                                                     float* __restrict__ gv_out) {
   constexpr int NF = 3 + 2 * DIM;  // code | total | first | bdir[DIM] | sdir[DIM]
   constexpr int CH = kFoldChunkD<DIM>;
   constexpr int LD = CH + 1;
@@ -4576,6 +4585,7 @@ __global__ __launch_bounds__(4 * kFold4Points) void wos_fold4_kernel(const DevPa
   const bool comp = c <= DIM;
   const int fb = c >= 1 && comp ? 3 + (c - 1) : 3, fs = c >= 1 && comp ? 3 + DIM + (c - 1) : 3;
   float mean = 0.0f, sFirst = 0.0f, cvb = 0.0f, cvs = 0.0f;
+  float m2 = 0.0f;  // VAR only
   int sN = 0;
   uint32_t steps = 0;
   // software pipeline: the block's next chunk of records is loaded into registers (UE slots per
@@ -4637,6 +4647,10 @@ __global__ __launch_bounds__(4 * kFold4Points) void wos_fold4_kernel(const DevPa
         const float val = c == 0 ? total : be + se;
         const float delta = val - mean;
         mean += delta / fN;
+        if constexpr (VAR) {
+          const float d2 = val - mean;
+          m2 += delta * d2;
+        }
         sFirst += first;
       }
     }
@@ -4649,6 +4663,14 @@ __global__ __launch_bounds__(4 * kFold4Points) void wos_fold4_kernel(const DevPa
     if (steps_out) steps_out[i] = (int32_t)steps;
   } else {
     g_out[i * DIM + (c - 1)] = (ps & kPtMaskG) ? 0.0f : mean;
+  }
+  if constexpr (VAR) {
+    const float var = m2 / (float)(sN > 2 ? sN - 1 : 1);  // max(1, n - 1)
+    if (c == 0) {
+      if (pv_out) pv_out[i] = (ps & kPtMaskP) ? 0.0f : var;
+    } else {
+      if (gv_out) gv_out[i * DIM + (c - 1)] = (ps & kPtMaskG) ? 0.0f : var;
+    }
   }
 }
 

@@ -72,9 +72,14 @@ template __global__ void wos_fold_kernel<2>(const DevParams, const DevTasks, int
 template __global__ void wos_fold_kernel<3>(const DevParams, const DevTasks, int64_t, float*, float*, int32_t*,
                                             int32_t*);
 template __global__ void wos_fold4_kernel<3>(const DevParams, const DevTasks, int64_t, float*, float*, int32_t*,
-                                             int32_t*);
+                                             int32_t*, float*, float*);
 template __global__ void wos_fold4_kernel<2>(const DevParams, const DevTasks, int64_t, float*, float*, int32_t*,
-                                             int32_t*);
+                                             int32_t*, float*, float*);
+// the same with the per-point variances (wos_solve_var)
+template __global__ void wos_fold4_kernel<3, true>(const DevParams, const DevTasks, int64_t, float*, float*,
+                                                   int32_t*, int32_t*, float*, float*);
+template __global__ void wos_fold4_kernel<2, true>(const DevParams, const DevTasks, int64_t, float*, float*,
+                                                   int32_t*, int32_t*, float*, float*);
 
 // math self-test kernel (parity of the deterministic math with the CPU oracle)
 __global__ void wos_math_selftest_kernel(int which, const double* x, double* out, int64_t n) {
@@ -196,17 +201,25 @@ hipError_t launch_walks(int dim, const DevScene& sc, const DevParams& prm, const
 }
 
 hipError_t launch_fold(int dim, const DevParams& prm, const DevTasks& tk, int64_t n, float* p, float* g,
-                       int32_t* nest, int32_t* steps, hipStream_t s) {
+                       int32_t* nest, int32_t* steps, float* p_var, float* g_var, hipStream_t s) {
   // the quad fold (pipelined staging), both dimensions: profiles/r5zm_ab_fold_pipe.log, r5zn_ab_fold4_2d.log
   if (tk.deriv == nullptr) {
     const int g4 = (int)((n + kFold4Points - 1) / kFold4Points);
     if (g4 < 1) return hipSuccess;
-    if (dim == 3)
-      hipLaunchKernelGGL(wos_fold4_kernel<3>, dim3(g4), dim3(4 * kFold4Points), 0, s, prm, tk, n, p, g, nest, steps);
-    else
-      hipLaunchKernelGGL(wos_fold4_kernel<2>, dim3(g4), dim3(4 * kFold4Points), 0, s, prm, tk, n, p, g, nest, steps);
+    const dim3 blk(4 * kFold4Points);
+    if (p_var || g_var) {  // the variance instantiation only when a variance is asked for
+      if (dim == 3)
+        hipLaunchKernelGGL((wos_fold4_kernel<3, true>), dim3(g4), blk, 0, s, prm, tk, n, p, g, nest, steps, p_var, g_var);
+      else
+        hipLaunchKernelGGL((wos_fold4_kernel<2, true>), dim3(g4), blk, 0, s, prm, tk, n, p, g, nest, steps, p_var, g_var);
+    } else if (dim == 3) {
+      hipLaunchKernelGGL((wos_fold4_kernel<3>), dim3(g4), blk, 0, s, prm, tk, n, p, g, nest, steps, nullptr, nullptr);
+    } else {
+      hipLaunchKernelGGL((wos_fold4_kernel<2>), dim3(g4), blk, 0, s, prm, tk, n, p, g, nest, steps, nullptr, nullptr);
+    }
     return hipGetLastError();
   }
+  if (p_var || g_var) return hipErrorInvalidValue;  // the derivative fold carries no variance
   const int grid = (int)((n + kFoldPoints - 1) / kFoldPoints);
   if (grid < 1) return hipSuccess;
   if (dim == 2)

@@ -27,8 +27,9 @@ hipError_t launch_lpt_order(const DevTasks& tk, int64_t n, hipStream_t s);
 hipError_t launch_walks(int dim, const DevScene& sc, const DevParams& prm, const DevTasks& tk, int64_t base,
                         int64_t stride, unsigned long long* counters, unsigned int* tqueue, int grid, size_t shmem,
                         int geom_floats, hipStream_t s);
+// p_var / g_var (either may be null): the per-point variances, quad fold only (tk.deriv == nullptr)
 hipError_t launch_fold(int dim, const DevParams& prm, const DevTasks& tk, int64_t n, float* p, float* g,
-                       int32_t* nest, int32_t* steps, hipStream_t s);
+                       int32_t* nest, int32_t* steps, float* p_var, float* g_var, hipStream_t s);
 // per-wave LDS scratch of the first-ball kernel
 size_t first_ball_wave_lds_bytes(int lhs_floats, int n_pairs);
 int first_ball_points_per_wave(int n_pairs);

@@ -97,7 +97,7 @@ class Stats(C.Structure):
 # exported symbols, exactly those declared in include/wos.h
 EXPORTS = (
     "wos_load_obj", "wos_mesh_free", "wos_scene_create", "wos_scene_destroy",
-    "wos_scene_get_info", "wos_scene_set_source", "wos_release_caches", "wos_default_params", "wos_solve",
+    "wos_scene_get_info", "wos_scene_set_source", "wos_release_caches", "wos_default_params", "wos_solve", "wos_solve_var",
     "wos_solve_stats", "wos_default_bvc_params", "wos_bvc",
     "wos_selftest_math", "wos_last_error", "wos_abi_version", "wos_device_count", "wos_set_max_batch_tasks",
 )
@@ -135,6 +135,10 @@ def load():
     L.wos_solve.argtypes = [C.c_void_p, C.POINTER(SolverParams), C.c_void_p, C.c_int64, C.c_int64,
                             C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                             C.POINTER(Stats), C.c_void_p, C.c_uint32]
+    L.wos_solve_var.restype = C.c_int
+    L.wos_solve_var.argtypes = [C.c_void_p, C.POINTER(SolverParams), C.c_void_p, C.c_int64, C.c_int64,
+                                C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                C.c_void_p, C.POINTER(Stats), C.c_void_p, C.c_uint32]
     L.wos_solve_stats.restype = C.c_int
     L.wos_solve_stats.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(Stats)]
     L.wos_default_bvc_params.restype = None

@@ -23,7 +23,10 @@ def sharded_projection(solve_local, pts, rank, world, dim, group=None, device=No
 
     solve_local(local_pts, index_base, index_stride) -> (p [n_local], grad [n_local, dim])
     as torch tensors on `device` (any device the process group's backend accepts).
-    Returns full (p [N], grad [N, dim]) torch tensors on every rank.
+    Returns full (p [N], grad [N, dim]) torch tensors on every rank.  A solve_local that
+    returns four tensors (p, grad, p_var [n_local], grad_var [n_local, dim]) -- a solve
+    with variance=True -- gets four full tensors back, through the same single collective
+    with 2 + 2 * dim columns.
 
     One code path for every backend: the shard, padded to n_pad rows, goes through ONE
     `all_gather_into_tensor` into a (world * n_pad, 1 + dim) buffer (RCCL over xGMI with
@@ -37,19 +40,26 @@ def sharded_projection(solve_local, pts, rank, world, dim, group=None, device=No
     n = pts.shape[0]
     idx, n_pad = shard(n, rank, world)
     local = pts[rank::world]
-    p, g = solve_local(local, rank, world)
-    p = torch.as_tensor(p, device=device)
-    g = torch.as_tensor(g, device=device).reshape(-1, dim)
+    res = tuple(solve_local(local, rank, world))
+    if len(res) not in (2, 4):
+        raise ValueError(f"solve_local must return (p, grad) or (p, grad, p_var, grad_var), got {len(res)} values")
+    # columns: p | grad[dim] (| p_var | grad_var[dim])
+    widths = (1, dim) * (len(res) // 2)
+    cols = [torch.as_tensor(t, device=device).reshape(-1, w) for t, w in zip(res, widths)]
+    p = cols[0]
+    ncol = sum(widths)
     gathered = world > 1 or force_gather
     # gloo has no device collectives: a gloo group (CPU rehearsal of the N-rank path,
     # ranks sharing one GPU) stages the shard through host memory
     staged = gathered and p.device.type != "cpu" and dist.get_backend(group) == "gloo"
     bdev = torch.device("cpu") if staged else p.device
-    send = torch.zeros(n_pad, 1 + dim, dtype=torch.float32, device=bdev)
-    send[: idx.size, 0] = p.to(bdev)
-    send[: idx.size, 1:] = g.to(bdev)
+    send = torch.zeros(n_pad, ncol, dtype=torch.float32, device=bdev)
+    c0 = 0
+    for t, w in zip(cols, widths):
+        send[: idx.size, c0:c0 + w] = t.to(bdev)
+        c0 += w
     if gathered:
-        buf = torch.empty(world * n_pad, 1 + dim, dtype=torch.float32, device=bdev)
+        buf = torch.empty(world * n_pad, ncol, dtype=torch.float32, device=bdev)
         dist.all_gather_into_tensor(buf, send, group=group)
         if staged:
             buf = buf.to(p.device)
@@ -57,8 +67,12 @@ def sharded_projection(solve_local, pts, rank, world, dim, group=None, device=No
         buf = send
     # (world, n_pad) blocks -> point order r + world * j; the padded rows (j >= count of
     # rank r) are exactly the indices >= n
-    full = buf.view(world, n_pad, 1 + dim).transpose(0, 1).reshape(world * n_pad, 1 + dim)[:n]
-    return full[:, 0].contiguous(), full[:, 1:].contiguous()
+    full = buf.view(world, n_pad, ncol).transpose(0, 1).reshape(world * n_pad, ncol)[:n]
+    out, c0 = [], 0
+    for w in widths:
+        out.append(full[:, c0].contiguous() if w == 1 else full[:, c0:c0 + w].contiguous())
+        c0 += w
+    return tuple(out)
 
 
 def make_gather(world, dist, n_local, n_pad, dim, dev, torch):

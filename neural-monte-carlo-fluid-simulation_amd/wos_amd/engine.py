@@ -241,9 +241,12 @@ class WosScene:
                 "bbox_min": list(i.bbox_min)[:i.dim], "bbox_max": list(i.bbox_max)[:i.dim]}
 
     def solve(self, pts, params=None, *, index_base=0, index_stride=1, counts=False, stream=None,
-              sync=True):
+              sync=True, variance=False):
         """Solve at query points.  Returns (p [N], grad [N,dim], stats dict[, n_est, steps])
-        as numpy arrays for host input, torch tensors for GPU tensor input.  With GPU tensors
+        as numpy arrays for host input, torch tensors for GPU tensor input.  With variance=True
+        the tuple is (p, grad, p_var [N], grad_var [N,dim], stats dict[, n_est, steps]): the
+        reference's per-walk sample variances M2 / max(1, n_est - 1) (wos_solve_var,
+        walk_on_stars.h:811-831), masked like their means.  With GPU tensors
         and sync=False the solve is only enqueued on the stream: the stats dict then holds
         just "ticket"; solve_stats(ticket) waits for that solve and returns the full dict.
         `stream`: a torch.cuda.Stream or a raw hipStream_t handle (default: torch's current
@@ -261,6 +264,8 @@ class WosScene:
             g = torch.empty(n, self.dim, dtype=torch.float32, device=x.device)
             ne = torch.empty(n, dtype=torch.int32, device=x.device) if counts else None
             sp = torch.empty(n, dtype=torch.int32, device=x.device) if counts else None
+            pv = torch.empty(n, dtype=torch.float32, device=x.device) if variance else None
+            gv = torch.empty(n, self.dim, dtype=torch.float32, device=x.device) if variance else None
             cur = torch.cuda.current_stream(x.device)
             ts = None
             if stream is None:
@@ -274,14 +279,20 @@ class WosScene:
                 # produced x, the allocator's last user of p / g)
                 ts.wait_stream(cur)
             flags = _lib.WOS_PTRS_DEVICE | (0 if sync else _lib.WOS_ASYNC)
-            check(L.wos_solve(self._h, C.byref(params), x.data_ptr(), n, index_base, index_stride,
-                              p.data_ptr(), g.data_ptr(), ne.data_ptr() if counts else None,
-                              sp.data_ptr() if counts else None, C.byref(st), s, flags), "wos_solve")
+            if variance:
+                check(L.wos_solve_var(self._h, C.byref(params), x.data_ptr(), n, index_base, index_stride,
+                                      p.data_ptr(), g.data_ptr(), pv.data_ptr(), gv.data_ptr(),
+                                      ne.data_ptr() if counts else None, sp.data_ptr() if counts else None,
+                                      C.byref(st), s, flags), "wos_solve_var")
+            else:
+                check(L.wos_solve(self._h, C.byref(params), x.data_ptr(), n, index_base, index_stride,
+                                  p.data_ptr(), g.data_ptr(), ne.data_ptr() if counts else None,
+                                  sp.data_ptr() if counts else None, C.byref(st), s, flags), "wos_solve")
             if not sync and ts is not None:
                 # the buffers were allocated on torch's current stream but the enqueued
                 # solve uses them on `stream`: keep the caching allocator from handing
                 # their memory out again before that stream has finished with them
-                for t in (x, p, g, ne, sp):
+                for t in (x, p, g, ne, sp, pv, gv):
                     if t is not None:
                         t.record_stream(ts)
         else:
@@ -295,10 +306,18 @@ class WosScene:
             g = np.empty((n, self.dim), np.float32)
             ne = np.empty(n, np.int32) if counts else None
             sp = np.empty(n, np.int32) if counts else None
-            check(L.wos_solve(self._h, C.byref(params), x.ctypes.data, n, index_base, index_stride,
-                              p.ctypes.data, g.ctypes.data, ne.ctypes.data if counts else None,
-                              sp.ctypes.data if counts else None, C.byref(st), stream, 0), "wos_solve")
-        out = (p, g, st.as_dict())
+            pv = np.empty(n, np.float32) if variance else None
+            gv = np.empty((n, self.dim), np.float32) if variance else None
+            if variance:
+                check(L.wos_solve_var(self._h, C.byref(params), x.ctypes.data, n, index_base, index_stride,
+                                      p.ctypes.data, g.ctypes.data, pv.ctypes.data, gv.ctypes.data,
+                                      ne.ctypes.data if counts else None, sp.ctypes.data if counts else None,
+                                      C.byref(st), stream, 0), "wos_solve_var")
+            else:
+                check(L.wos_solve(self._h, C.byref(params), x.ctypes.data, n, index_base, index_stride,
+                                  p.ctypes.data, g.ctypes.data, ne.ctypes.data if counts else None,
+                                  sp.ctypes.data if counts else None, C.byref(st), stream, 0), "wos_solve")
+        out = (p, g, pv, gv, st.as_dict()) if variance else (p, g, st.as_dict())
         if counts:
             out = out + (ne, sp)
         return out

@@ -153,26 +153,32 @@ class PressureProjector:
     def _set_source(self, div):
         self.scene._scene.set_source(div)
 
-    def _solve_points(self, x, index_base, index_stride):
-        return self.scene._scene.solve(x, self.params, index_base=index_base, index_stride=index_stride)
+    def _solve_points(self, x, index_base, index_stride, variance=False):
+        if not variance:
+            return self.scene._scene.solve(x, self.params, index_base=index_base, index_stride=index_stride)
+        return self.scene._scene.solve(x, self.params, index_base=index_base, index_stride=index_stride,
+                                       variance=True)
 
-    def solve(self, div):
+    def solve(self, div, variance=False):
         """wost_pressure (model_split.py:185-202) with device tensors in and out; with a
-        process group, this rank's stride shard + one all-gather (wos_amd.dist)."""
+        process group, this rank's stride shard + one all-gather (wos_amd.dist).
+        variance=True: (p, grad_p, p_var, grad_var) -- the per-walk sample variances of
+        WosScene.solve(..., variance=True), gathered by the same collective."""
         self._set_source(div)
+        kw = {"variance": True} if variance else {}
         if self.group is None and not self.force_gather:
-            p, g, st = self._solve_points(self.samples, 0, 1)
+            *out, st = self._solve_points(self.samples, 0, 1, **kw)
             self.last_stats = st
-            return p, g
+            return tuple(out)
         import torch.distributed as tdist
         from . import dist as _dist
         group = self.group if self.group is not None else tdist.group.WORLD
         rank, world = tdist.get_rank(group), tdist.get_world_size(group)
 
         def solve_local(local, base, stride):
-            p, g, st = self._solve_points(local.contiguous(), base, stride)
+            *out, st = self._solve_points(local.contiguous(), base, stride, **kw)
             self.last_stats = st  # this rank's shard
-            return p, g
+            return tuple(out)
 
         return _dist.sharded_projection(solve_local, self.samples, rank, world, self.dim, group=group,
                                         device=self.device, force_gather=self.force_gather)

@@ -162,22 +162,26 @@ class Scene:
         self._scene.set_source(source)
 
 
-def wost(scene, solverConfig, outputConfig, pts, return_numpy=False):
+def wost(scene, solverConfig, outputConfig, pts, return_numpy=False, return_variance=False):
     """runWalkOnStars_sampled (demo.cpp:119-205) / runWalkOnStars_3d: returns
     (points, p, grad) as nested lists (numpy arrays if return_numpy; torch
-    tensors when pts is a CUDA tensor)."""
+    tensors when pts is a CUDA tensor).  return_variance (extension, like return_numpy):
+    (points, p, grad, p_var, grad_var) in the same container type -- the estimator's
+    per-walk sample variances (getEstimatedSolutionVariance / getEstimatedGradientVariance,
+    walk_on_stars.h:811-831), masked like p and grad."""
     _required(outputConfig, "gridRes")  # required even by the sampled path (demo.cpp:132)
     params = _engine.solver_params(solverConfig, outputConfig)
+    kw = {"variance": True} if return_variance else {}
     if _engine._is_torch(pts) and pts.is_cuda:
-        p, g, stats = scene._scene.solve(pts, params)
+        *out, stats = scene._scene.solve(pts, params, **kw)
         scene.last_stats = stats
-        return pts, p, g
+        return (pts, *out)
     x = np.ascontiguousarray(np.asarray(pts, dtype=np.float32).reshape(-1, scene.dim))
-    p, g, stats = scene._scene.solve(x, params)
+    *out, stats = scene._scene.solve(x, params, **kw)
     scene.last_stats = stats
     if return_numpy:
-        return x, p, g
-    return x.tolist(), p.tolist(), g.tolist()
+        return (x, *out)
+    return (x.tolist(), *(a.tolist() for a in out))
 
 
 def _write_image(path, img):
