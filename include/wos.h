@@ -107,6 +107,29 @@ int wos_scene_destroy(wos_scene *scene);
 int wos_scene_set_source(wos_scene *scene, const float *source, const int32_t *dims,
                          int32_t on_device, void *stream);
 
+/* Several source fields on one set of walks (added within ABI 10: new entry points only).  The
+ * reference's estimator is generic in its value type (WalkOnStars<T, DIM>, PDE<T, DIM>,
+ * walk_on_stars.h:32-50, pde.h:14-27); a walk itself never looks at the source, so up to
+ * WOS_MAX_CHANNELS right-hand sides on one geometry -- the components of a vector-valued solve, the
+ * members of an ensemble -- share every walk (common random numbers) for little more than the price
+ * of one.  Contract: channel c of wos_solve_channels equals, bit for bit, wos_solve_var on the same
+ * scene with source c and the constant Dirichlet value g_c.
+ *   source            planar [C][H][W] (2D) or [C][X][Y][Z] (3D); dims as wos_scene_set_source
+ *   dirichlet_values  host array of C constants g_c, or NULL: every channel uses the scene's
+ *                     Dirichlet data.  Image-valued Dirichlet and Neumann data stay scalar and apply
+ *                     to every channel; non-NULL dirichlet_values on a scene with a Dirichlet image
+ *                     is WOS_E_INVALID
+ *   n_channels        1..WOS_MAX_CHANNELS, else WOS_E_INVALID
+ * The planar input is packed into one 16-byte texel per grid cell by a kernel on `stream`, ordered
+ * like wos_scene_set_source's copy (one channel: that copy).  wos_scene_set_source returns the
+ * scene to one channel and to its own Dirichlet data.  While a scene holds more than one channel,
+ * wos_solve, wos_solve_var and wos_bvc return WOS_E_INVALID (they never solve channel 0 silently). */
+#define WOS_MAX_CHANNELS 4
+int wos_scene_set_source_channels(wos_scene *scene, const float *source, int32_t n_channels,
+                                  const int32_t *dims, const float *dirichlet_values,
+                                  int32_t on_device, void *stream);
+int32_t wos_scene_channels(const wos_scene *scene);   /* source channels the scene holds (>= 1) */
+
 /* Scenes share a per-device solve workspace and a cache of prepared geometries
  * (keyed by content), so the reference's per-step Scene(...) costs neither a
  * workspace allocation nor a re-preparation.  This releases both for `device`
@@ -114,7 +137,8 @@ int wos_scene_set_source(wos_scene *scene, const float *source, const int32_t *d
 int wos_release_caches(int32_t device);
 
 /* Walk tasks per batch (ABI 10).  A solve runs its points in batches of at most this many walk
- * tasks (the per-device workspace holds one batch: 60 B per task); default 2^28 = 16 GB at most,
+ * tasks (the per-device workspace holds one batch: 60 B per task, plus 12 B for every source
+ * channel beyond the first -- 60 + 12 (C - 1), wos_solve_channels); default 2^28 = 16 GB at most,
  * sized for a 288 GB MI355X (fewer batches, fewer ramp-downs of the persistent kernels).  A
  * caller that shares the GPU with other work can cap it.  max_tasks <= 0: the default; else
  * clamped to [2^16, 2^30].  Returns the previous value.  Results do not depend on it. */
@@ -221,6 +245,18 @@ int wos_solve_var(wos_scene *scene, const wos_solver_params *params,
                   const float *pts, int64_t n, int64_t index_base, int64_t index_stride,
                   float *p, float *grad, float *p_var, float *grad_var, int32_t *n_est, int32_t *steps,
                   wos_stats *stats, void *stream, uint32_t flags);
+
+/* wos_solve_var on a scene with n_channels source channels (wos_scene_set_source_channels; n_channels
+ * must equal wos_scene_channels, else WOS_E_INVALID).  Outputs are channel-major:
+ *   p[C][n], grad[C][n*dim], and the optional p_var[C][n], grad_var[C][n*dim];
+ *   n_est[n], steps[n] are the walks' and therefore shared by the channels.
+ * Masks, points that are not estimated and the variance masking rule apply to each channel as in
+ * wos_solve_var; wos_stats counts the walks once.  Host pointers, WOS_PTRS_DEVICE and WOS_ASYNC
+ * work as there, batches included.  With one channel this is wos_solve_var. */
+int wos_solve_channels(wos_scene *scene, const wos_solver_params *params,
+                       const float *pts, int64_t n, int64_t index_base, int64_t index_stride,
+                       int32_t n_channels, float *p, float *grad, float *p_var, float *grad_var,
+                       int32_t *n_est, int32_t *steps, wos_stats *stats, void *stream, uint32_t flags);
 
 /* Boundary value caching: the reference's `bvc(scene, solver, output)`
  * (bindings/zombie/demo/demo.cpp:265-363, exported at :396), replaced here.

@@ -366,6 +366,9 @@ struct wos_scene {
   wos::DevScene dev{};
   float* d_source = nullptr;
   size_t source_cap = 0;  // floats
+  float* d_planar = nullptr;  // staging of a host source with several channels, before the texel pack
+  size_t planar_cap = 0;      // floats
+  float g_dirichlet = 0.0f;   // wos_scene_desc.dirichlet_value (per-channel constants may replace dev's)
   float* d_dimg = nullptr;  // image-valued Dirichlet data (wos_scene_desc.dirichlet_image)
   float* d_nimg = nullptr;  // image-valued Neumann data (wos_scene_desc.neumann_image)
   std::mutex mu;          // solve vs set_source on the same scene
@@ -548,6 +551,9 @@ int wos_scene_create(const wos_scene_desc* d, int32_t device, wos_scene** out) {
   }
   ds.absorption = d->absorption;
   ds.g_dirichlet = d->dirichlet_value;
+  s->g_dirichlet = d->dirichlet_value;
+  ds.n_channels = 1;
+  for (int c = 0; c < wos::kMaxChannels; c++) ds.g_ch[c] = d->dirichlet_value;
   ds.dimg = s->d_dimg;
   for (int k = 0; k < 2; k++) ds.ddims[k] = ndimg ? d->dirichlet_image_dims[k] : 0;
   for (int k = 0; k < 4; k++) ds.dbox[k] = ndimg ? d->dirichlet_image_box[k] : 0.0f;
@@ -585,8 +591,77 @@ int wos_scene_set_source(wos_scene* s, const float* source, const int32_t* dims,
   const int nsd = s->dev.dim == 2 ? 2 : 3;
   s->dev.source = s->d_source;
   for (int k = 0; k < 3; k++) s->dev.sdims[k] = k < nsd ? dims[k] : 1;
+  // back to one channel with the scene's own Dirichlet data
+  s->dev.n_channels = 1;
+  s->dev.g_dirichlet = s->g_dirichlet;
+  for (int c = 0; c < wos::kMaxChannels; c++) s->dev.g_ch[c] = s->g_dirichlet;
   return WOS_OK;
 }
+
+int wos_scene_set_source_channels(wos_scene* s, const float* source, int32_t n_channels, const int32_t* dims,
+                                  const float* dirichlet_values, int32_t on_device, void* stream) {
+  if (!s || !source || !dims) return fail(WOS_E_INVALID, "wos_scene_set_source_channels: null argument");
+  if (n_channels < 1 || n_channels > WOS_MAX_CHANNELS)
+    return fail(WOS_E_INVALID, "wos_scene_set_source_channels: n_channels must be 1.." + std::to_string(WOS_MAX_CHANNELS) +
+                                   ", got " + std::to_string(n_channels));
+  if (dirichlet_values && s->d_dimg)
+    return fail(WOS_E_INVALID, "wos_scene_set_source_channels: per-channel dirichlet_values cannot be combined with "
+                               "the scene's Dirichlet image (image-valued data is shared by the channels)");
+  if (n_channels == 1) {  // today's plain copy
+    int rc = wos_scene_set_source(s, source, dims, on_device, stream);
+    if (rc != WOS_OK) return rc;
+    if (dirichlet_values) {
+      std::lock_guard<std::mutex> lock(s->mu);
+      s->dev.g_dirichlet = dirichlet_values[0];
+      for (int c = 0; c < wos::kMaxChannels; c++) s->dev.g_ch[c] = dirichlet_values[0];
+    }
+    return WOS_OK;
+  }
+  size_t cells = 0;
+  if (check_source_dims(s->dev.dim, dims, &cells) != WOS_OK)
+    return fail(WOS_E_INVALID, "wos_scene_set_source_channels: bad source dims");
+  std::lock_guard<std::mutex> lock(s->mu);
+  HIP_TRY(hipSetDevice(s->device));
+  hipStream_t st = (hipStream_t)stream;
+  DevCtx& c = g_ctx[s->device];
+  {
+    std::lock_guard<std::mutex> lk(c.mu);
+    HIP_TRY(ctx_order(c, st));  // a solve on another stream may still read the old grid
+  }
+  const size_t ntex = cells * wos::kMaxChannels, nplanar = cells * (size_t)n_channels;
+  if (ntex > s->source_cap || (!on_device && nplanar > s->planar_cap)) HIP_TRY(hipStreamSynchronize(st));
+  if (ntex > s->source_cap) {
+    hipFree(s->d_source);
+    s->d_source = nullptr;
+    s->source_cap = 0;
+    s->dev.source = nullptr;
+    HIP_TRY(hipMalloc((void**)&s->d_source, ntex * sizeof(float)));
+    s->source_cap = ntex;
+  }
+  const float* planar = source;
+  if (!on_device) {
+    if (nplanar > s->planar_cap) {
+      hipFree(s->d_planar);
+      s->d_planar = nullptr;
+      s->planar_cap = 0;
+      HIP_TRY(hipMalloc((void**)&s->d_planar, nplanar * sizeof(float)));
+      s->planar_cap = nplanar;
+    }
+    HIP_TRY(hipMemcpyAsync(s->d_planar, source, nplanar * sizeof(float), hipMemcpyHostToDevice, st));
+    planar = s->d_planar;
+  }
+  HIP_TRY(wos::launch_source_pack(planar, s->d_source, (int64_t)cells, n_channels, st));
+  const int nsd = s->dev.dim == 2 ? 2 : 3;
+  s->dev.source = s->d_source;
+  for (int k = 0; k < 3; k++) s->dev.sdims[k] = k < nsd ? dims[k] : 1;
+  s->dev.n_channels = n_channels;
+  s->dev.g_dirichlet = s->g_dirichlet;
+  for (int ch = 0; ch < wos::kMaxChannels; ch++)
+    s->dev.g_ch[ch] = (dirichlet_values && ch < n_channels) ? dirichlet_values[ch] : s->g_dirichlet;
+  return WOS_OK;
+}
+
+int32_t wos_scene_channels(const wos_scene* s) { return s ? s->dev.n_channels : 0; }
 
 int wos_scene_destroy(wos_scene* s) {
   if (!s) return WOS_OK;
@@ -597,6 +672,7 @@ int wos_scene_destroy(wos_scene* s) {
     std::lock_guard<std::mutex> lk(c.mu);
     if (c.inflight) hipEventSynchronize(c.done);  // an async solve may still read the source
     hipFree(s->d_source);
+    hipFree(s->d_planar);
     hipFree(s->d_dimg);
     hipFree(s->d_nimg);
   }
@@ -680,9 +756,12 @@ int ensure_var_workspace(DevCtx& c, size_t npts) {
 
 
 int ensure_tasks_in(float*& d_tasks, int64_t& task_cap, int32_t*& d_pstate, int64_t& pstate_cap, int dim,
-                    int64_t tasks, int64_t points) {
-  // sized for 3D records so either dimension fits
+                    int64_t tasks, int64_t points, int channels = 1) {
+  // sized for 3D records so either dimension fits; task_cap counts one-channel tasks (tf floats),
+  // so a batch with several channels asks for its float count in those units
   const int tf = std::max(wos::task_floats(dim), wos::task_floats(3));
+  const int tfc = std::max(wos::task_floats(dim, channels), wos::task_floats(3, channels));
+  if (channels > 1) tasks = (tasks * tfc + tf - 1) / tf;
   if (tasks > task_cap) {
     hipFree(d_tasks);
     d_tasks = nullptr; task_cap = 0;
@@ -698,22 +777,24 @@ int ensure_tasks_in(float*& d_tasks, int64_t& task_cap, int32_t*& d_pstate, int6
   return WOS_OK;
 }
 
-int ensure_tasks(DevCtx& c, int dim, int64_t tasks, int64_t points) {
-  return ensure_tasks_in(c.d_tasks, c.task_cap, c.d_pstate, c.pstate_cap, dim, tasks, points);
+int ensure_tasks(DevCtx& c, int dim, int64_t tasks, int64_t points, int channels = 1) {
+  return ensure_tasks_in(c.d_tasks, c.task_cap, c.d_pstate, c.pstate_cap, dim, tasks, points, channels);
 }
 
 // SoA views into a task workspace for a chunk of T tasks
-wos::DevTasks task_view_in(float* d_tasks, int32_t* d_pstate, int64_t pstate_cap, int dim, int64_t T, int32_t wpp) {
+// (channels: the [C][T] arrays tsrc, first and total of a solve with several source channels)
+wos::DevTasks task_view_in(float* d_tasks, int32_t* d_pstate, int64_t pstate_cap, int dim, int64_t T, int32_t wpp,
+                           int channels = 1) {
   wos::DevTasks tk{};
   float* f = d_tasks;
   tk.pt = f; f += dim * T;
   tk.thr = f; f += T;
-  tk.tsrc = f; f += T;
+  tk.tsrc = f; f += channels * T;
   tk.dd = f; f += T;
-  tk.first = f; f += T;
+  tk.first = f; f += channels * T;
   tk.bdir = f; f += dim * T;
   tk.sdir = f; f += dim * T;
-  tk.total = f; f += T;
+  tk.total = f; f += channels * T;
   tk.code = (uint32_t*)f;
   tk.pstate = d_pstate;
   tk.perm = (uint32_t*)(d_pstate + pstate_cap);
@@ -726,8 +807,8 @@ wos::DevTasks task_view_in(float* d_tasks, int32_t* d_pstate, int64_t pstate_cap
   return tk;
 }
 
-wos::DevTasks task_view(DevCtx& c, int dim, int64_t T, int32_t wpp) {
-  return task_view_in(c.d_tasks, c.d_pstate, c.pstate_cap, dim, T, wpp);
+wos::DevTasks task_view(DevCtx& c, int dim, int64_t T, int32_t wpp, int channels = 1) {
+  return task_view_in(c.d_tasks, c.d_pstate, c.pstate_cap, dim, T, wpp, channels);
 }
 
 // Stream priorities of boundary value caching's walk sets: the Dirichlet samples' solve and
@@ -920,11 +1001,16 @@ struct SolveExtra {
   // wos_solve_var: the variances out (host or device pointers like p and grad; null: not asked for)
   float* p_var = nullptr;
   float* grad_var = nullptr;
+  // wos_solve_channels: the scene's source channels; every output is channel-major ([C][n], [C][n*dim])
+  int channels = 1;
 };
 
 int solve_locked(wos_scene* s, const wos_solver_params* prm, const float* pts, int64_t n, int64_t index_base,
                  int64_t index_stride, float* p, float* grad, int32_t* n_est, int32_t* steps, wos_stats* stats,
                  void* stream, uint32_t flags, const SolveExtra& ex);
+int solve_checked(wos_scene* s, const wos_solver_params* prm, const float* pts, int64_t n, int64_t index_base,
+                  int64_t index_stride, int32_t n_channels, float* p, float* grad, float* p_var, float* grad_var,
+                  int32_t* n_est, int32_t* steps, wos_stats* stats, void* stream, uint32_t flags);
 
 }  // namespace
 
@@ -933,6 +1019,30 @@ extern "C" {
 int wos_solve_var(wos_scene* s, const wos_solver_params* prm, const float* pts, int64_t n, int64_t index_base,
                   int64_t index_stride, float* p, float* grad, float* p_var, float* grad_var, int32_t* n_est,
                   int32_t* steps, wos_stats* stats, void* stream, uint32_t flags) {
+  return solve_checked(s, prm, pts, n, index_base, index_stride, 0, p, grad, p_var, grad_var, n_est, steps, stats,
+                       stream, flags);
+}
+
+int wos_solve_channels(wos_scene* s, const wos_solver_params* prm, const float* pts, int64_t n, int64_t index_base,
+                       int64_t index_stride, int32_t n_channels, float* p, float* grad, float* p_var,
+                       float* grad_var, int32_t* n_est, int32_t* steps, wos_stats* stats, void* stream,
+                       uint32_t flags) {
+  if (n_channels < 1 || n_channels > WOS_MAX_CHANNELS)
+    return fail(WOS_E_INVALID, "wos_solve_channels: n_channels must be 1.." + std::to_string(WOS_MAX_CHANNELS) +
+                                   ", got " + std::to_string(n_channels));
+  return solve_checked(s, prm, pts, n, index_base, index_stride, n_channels, p, grad, p_var, grad_var, n_est, steps,
+                       stats, stream, flags);
+}
+
+}  // extern "C"
+
+namespace {
+
+// the argument checks of every solve entry point; n_channels 0: wos_solve / wos_solve_var,
+// which refuse a scene that holds several channels
+int solve_checked(wos_scene* s, const wos_solver_params* prm, const float* pts, int64_t n, int64_t index_base,
+                  int64_t index_stride, int32_t n_channels, float* p, float* grad, float* p_var, float* grad_var,
+                  int32_t* n_est, int32_t* steps, wos_stats* stats, void* stream, uint32_t flags) {
   if (!s || !prm) return fail(WOS_E_INVALID, "wos_solve: null scene/params");
   if (n < 0) return fail(WOS_E_INVALID, "wos_solve: negative point count");
   if (n > 0 && (!pts || !p || !grad)) return fail(WOS_E_INVALID, "wos_solve: null point/output buffer");
@@ -945,11 +1055,22 @@ int wos_solve_var(wos_scene* s, const wos_solver_params* prm, const float* pts, 
   HIP_TRY(hipSetDevice(s->device));
   DevCtx& c = g_ctx[s->device];
   std::lock_guard<std::mutex> lk(c.mu);
+  if (n_channels == 0 && s->dev.n_channels > 1)
+    return fail(WOS_E_INVALID, "wos_solve: the scene holds " + std::to_string(s->dev.n_channels) +
+                                   " source channels; use wos_solve_channels (or wos_scene_set_source for one)");
+  if (n_channels != 0 && n_channels != s->dev.n_channels)
+    return fail(WOS_E_INVALID, "wos_solve_channels: n_channels " + std::to_string(n_channels) +
+                                   " differs from the scene's " + std::to_string(s->dev.n_channels));
   SolveExtra ex;
   ex.p_var = p_var;
   ex.grad_var = grad_var;
+  ex.channels = s->dev.n_channels;
   return solve_locked(s, prm, pts, n, index_base, index_stride, p, grad, n_est, steps, stats, stream, flags, ex);
 }
+
+}  // namespace
+
+extern "C" {
 
 int wos_solve(wos_scene* s, const wos_solver_params* prm, const float* pts, int64_t n, int64_t index_base,
               int64_t index_stride, float* p, float* grad, int32_t* n_est, int32_t* steps, wos_stats* stats,
@@ -1042,15 +1163,16 @@ int solve_locked(wos_scene* s, const wos_solver_params* prm, const float* pts, i
   float* d_pvar = ex.p_var;
   float* d_gvar = ex.grad_var;
   const bool dev_ptrs = (flags & WOS_PTRS_DEVICE) != 0;
+  const int C = ex.channels;  // outputs [C][n] / [C][n*dim]: the staging holds C * n points
   if (!dev_ptrs && n > 0) {
-    int rc = ensure_workspace(c, dim, (size_t)n);
+    int rc = ensure_workspace(c, dim, (size_t)n * C);
     if (rc != WOS_OK) return rc;
     HIP_TRY(hipMemcpyAsync(c.d_pts, pts, (size_t)n * dim * sizeof(float), hipMemcpyHostToDevice, st));
     d_pts = c.d_pts; d_p = c.d_p; d_g = c.d_g;
     d_nest = n_est ? c.d_nest : nullptr;
     d_steps = steps ? c.d_steps : nullptr;
     if (ex.p_var || ex.grad_var) {
-      rc = ensure_var_workspace(c, (size_t)n);
+      rc = ensure_var_workspace(c, (size_t)n * C);
       if (rc != WOS_OK) return rc;
       d_pvar = ex.p_var ? c.d_pvar : nullptr;
       d_gvar = ex.grad_var ? c.d_gvar : nullptr;
@@ -1084,15 +1206,15 @@ int solve_locked(wos_scene* s, const wos_solver_params* prm, const float* pts, i
   const int64_t n_chunks = n > 0 ? (n + chunk - 1) / chunk : 0;
   int grid_fb = 0, grid_walk = 0, bpc_fb = 0, bpc_walk = 0;
   if (n > 0) {
-    int rc = ensure_tasks(c, dim, chunk * wpp, chunk);
+    int rc = ensure_tasks(c, dim, chunk * wpp, chunk, C);
     if (rc != WOS_OK) return rc;
-    HIP_TRY(wos::occupancy_blocks_per_cu(0, dim, false, shmem_fb, &bpc_fb, dp.robust != 0));
+    HIP_TRY(wos::occupancy_blocks_per_cu(0, dim, false, shmem_fb, &bpc_fb, dp.robust != 0, C > 1));
     // the stratified samples' jump constants in LDS, unless they cost the first-ball kernel a block per CU
     const int jn = std::min(2 * (2 * dp.n_pairs) * (dim - 1), wos::kLhsJumpMax);
     const size_t shmem_j = shmem_fb + (size_t)jn * 2 * sizeof(uint64_t);
     int bpc_j = 0;
     if (jn > 0 && shmem_j <= kLdsDynamicMax)
-      HIP_TRY(wos::occupancy_blocks_per_cu(0, dim, false, shmem_j, &bpc_j, dp.robust != 0));
+      HIP_TRY(wos::occupancy_blocks_per_cu(0, dim, false, shmem_j, &bpc_j, dp.robust != 0, C > 1));
     if (WOS_LHS_JUMP_STAGE && jn > 0 && bpc_j >= bpc_fb) {
       dp.lhs_jump_n = jn;
       shmem_fb_run = shmem_j;
@@ -1101,7 +1223,7 @@ int solve_locked(wos_scene* s, const wos_solver_params* prm, const float* pts, i
     grid_fb = (int)std::min<int64_t>((fb_waves + wos::kWavesPerBlockHost - 1) / wos::kWavesPerBlockHost,
                                      (int64_t)std::max(1, bpc_fb) * std::max(1, c.num_cus));
     // the walk instantiation launch_walks will dispatch (tail spreading has its own LDS and state)
-    HIP_TRY(wos::occupancy_walk_blocks_per_cu(dim, dsc.geom_global != 0, dp, shmem_walk, &bpc_walk));
+    HIP_TRY(wos::occupancy_walk_blocks_per_cu(dim, dsc.geom_global != 0, dp, shmem_walk, &bpc_walk, C > 1));
     grid_walk = std::max(1, bpc_walk) * std::max(1, c.num_cus);
   }
   const uint64_t ticket = c.next_ticket++;
@@ -1125,7 +1247,7 @@ int solve_locked(wos_scene* s, const wos_solver_params* prm, const float* pts, i
     const int64_t b0 = k * chunk;
     hipEvent_t* ev = &q.bev[4 * k];
     const int64_t nb = std::min(chunk, n - b0);
-    wos::DevTasks tk = task_view(c, dim, nb * wpp, (int32_t)wpp);
+    wos::DevTasks tk = task_view(c, dim, nb * wpp, (int32_t)wpp, C);
     tk.ddir = ex.ddir ? ex.ddir + b0 * dim : nullptr;
     tk.deriv = ex.deriv ? ex.deriv + b0 : nullptr;
     const int64_t bbase = index_base + b0 * index_stride;
@@ -1147,23 +1269,30 @@ int solve_locked(wos_scene* s, const wos_solver_params* prm, const float* pts, i
     HIP_TRY(wos::launch_walks(dim, dsc, dp, tk, bbase, index_stride, c.d_counters, q_tasks, walk_grid,
                               shmem_walk, geom_floats_walk, st));
     HIP_TRY(hipEventRecord(ev[2], st));
-    HIP_TRY(wos::launch_fold(dim, dp, tk, nb, d_p + b0, d_g + b0 * dim, d_nest ? d_nest + b0 : nullptr,
-                             d_steps ? d_steps + b0 : nullptr, d_pvar ? d_pvar + b0 : nullptr,
-                             d_gvar ? d_gvar + b0 * dim : nullptr, st));
+    // one fold per channel: only total and first differ, code / bdir / sdir are the walks'
+    for (int ch = 0; ch < C; ch++) {
+      wos::DevTasks tkc = tk;
+      tkc.total = tk.total + (int64_t)ch * tk.T;
+      tkc.first = tk.first + (int64_t)ch * tk.T;
+      const int64_t o1 = (int64_t)ch * n + b0, od = ((int64_t)ch * n + b0) * dim;
+      HIP_TRY(wos::launch_fold(dim, dp, tkc, nb, d_p + o1, d_g + od, (d_nest && ch == 0) ? d_nest + b0 : nullptr,
+                               (d_steps && ch == 0) ? d_steps + b0 : nullptr, d_pvar ? d_pvar + o1 : nullptr,
+                               d_gvar ? d_gvar + od : nullptr, st));
+    }
     HIP_TRY(hipEventRecord(ev[3], st));
   }
   HIP_TRY(hipEventRecord(q.ev1, st));
   HIP_TRY(hipMemcpyAsync(q.h_cnt, c.d_counters, wos::kNumCounters * sizeof(unsigned long long),
                          hipMemcpyDeviceToHost, st));
   if (!dev_ptrs && n > 0) {
-    HIP_TRY(hipMemcpyAsync(p, d_p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(grad, d_g, (size_t)n * dim * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(p, d_p, (size_t)n * C * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(grad, d_g, (size_t)n * C * dim * sizeof(float), hipMemcpyDeviceToHost, st));
     if (n_est) HIP_TRY(hipMemcpyAsync(n_est, d_nest, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     if (steps) HIP_TRY(hipMemcpyAsync(steps, d_steps, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     if (ex.p_var)
-      HIP_TRY(hipMemcpyAsync(ex.p_var, d_pvar, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipMemcpyAsync(ex.p_var, d_pvar, (size_t)n * C * sizeof(float), hipMemcpyDeviceToHost, st));
     if (ex.grad_var)
-      HIP_TRY(hipMemcpyAsync(ex.grad_var, d_gvar, (size_t)n * dim * sizeof(float), hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipMemcpyAsync(ex.grad_var, d_gvar, (size_t)n * C * dim * sizeof(float), hipMemcpyDeviceToHost, st));
   }
   HIP_TRY(hipEventRecord(q.done, st));
   HIP_TRY(hipEventRecord(c.done, st));
@@ -1252,6 +1381,9 @@ int wos_bvc(wos_scene* s, const wos_solver_params* prm, const wos_bvc_params* bp
       return fail(WOS_E_INVALID, "wos_bvc: grid_box needs both extents 0 (the scene's box) or both finite and > 0");
   }
   std::lock_guard<std::mutex> lock(s->mu);
+  if (s->dev.n_channels > 1)
+    return fail(WOS_E_INVALID, "wos_bvc: the scene holds " + std::to_string(s->dev.n_channels) +
+                                   " source channels; boundary value caching is single-channel");
   Geom& geom = *s->geom;
   const wos::HostScene& host = geom.host;
   if (host.dim != 2) return fail(WOS_E_INVALID, "wos_bvc: boundary value caching is 2D (the reference exports it from the 2D module only)");

@@ -1023,16 +1023,16 @@ __device__ __forceinline__ void probe_sink(T v) {
 #endif
 
 // PDE source lookup: scene.h:194-198 + image.h:53-58 (2D), scene_3d.h:120-126 (3D)
+// the grid cell of x
 template <int DIM>
-__device__ __forceinline__ float source_value(const DevScene& sc, const float* x) {
-  if (sc.source == nullptr || WOS_ACCT_NOTEX) return 0.0f;
+__device__ __forceinline__ size_t source_cell(const DevScene& sc, const float* x) {
   if constexpr (DIM == 2) {
     float ux = (x[0] - sc.pmin[0]) / sc.ext[0];
     float uy = (x[1] - sc.pmin[1]) / sc.ext[1];
     int h = sc.sdims[0], w = sc.sdims[1];
     int i = sclamp(cvt_trunc(uy * (float)h), 0, h - 1);
     int j = sclamp(cvt_trunc(ux * (float)w), 0, w - 1);
-    return sc.source[(size_t)i * w + j];
+    return (size_t)i * w + j;
   } else {
     int X = sc.sdims[0], Y = sc.sdims[1], Z = sc.sdims[2];
     float ux = (x[0] - sc.pmin[0]) / sc.ext[0];
@@ -1041,7 +1041,33 @@ __device__ __forceinline__ float source_value(const DevScene& sc, const float* x
     int i = sclamp(cvt_trunc(ux * (float)X), 0, X - 1);
     int j = sclamp(cvt_trunc(uy * (float)Y), 0, Y - 1);
     int k = sclamp(cvt_trunc(uz * (float)Z), 0, Z - 1);
-    return sc.source[((size_t)i * Y + j) * Z + k];
+    return ((size_t)i * Y + j) * Z + k;
+  }
+}
+
+template <int DIM>
+__device__ __forceinline__ float source_value(const DevScene& sc, const float* x) {
+  if (sc.source == nullptr || WOS_ACCT_NOTEX) return 0.0f;
+  return sc.source[source_cell<DIM>(sc, x)];
+}
+
+// Several source fields on one set of walks (wos_solve_channels): NC is 1 (the scalar code,
+// DevScene::source is the plain grid) or kMaxChannels -- the multi-channel instantiations,
+// whose DevScene::source holds one 16-byte texel [cell][kMaxChannels] per grid cell (channels
+// beyond DevScene::n_channels are +0), so a lookup stays one load from one cache line.
+// Every channel repeats the scalar code's float operations in their order.
+template <int DIM, int NC>
+__device__ __forceinline__ void source_values(const DevScene& sc, const float* x, float* out) {
+  if constexpr (NC == 1) {
+    out[0] = source_value<DIM>(sc, x);
+  } else {
+    static_assert(NC == 4, "one float4 texel per cell");
+    if (sc.source == nullptr || WOS_ACCT_NOTEX) {
+      for (int c = 0; c < NC; c++) out[c] = 0.0f;
+      return;
+    }
+    const float4 v = reinterpret_cast<const float4*>(sc.source)[source_cell<DIM>(sc, x)];
+    out[0] = v.x; out[1] = v.y; out[2] = v.z; out[3] = v.w;
   }
 }
 
@@ -2135,24 +2161,26 @@ __device__ __forceinline__ void sample_volume_wave(const DevParams& prm, bool ac
 // ---------------------------------------------------------------------------
 // walk (walk_on_stars.h:135-329)
 // ---------------------------------------------------------------------------
-template <int DIM>
+// NC source channels (source_values): only totalSource and the deferred texel are per channel,
+// everything a walk decides on is shared
+template <int DIM, int NC = 1>
 struct WalkState {
   float pt[DIM], n[DIM], prevDir[DIM];
   float prevDist, throughput;
   bool onNeumann;
   int walkLength;
-  float totalNeumann, totalSource;
+  float totalNeumann, totalSource[NC];
   // the source contribution of the last step, added once its texel has arrived:
   // totalSource += pThr * (pNrm * pTex) in the reference's order (walk_on_stars.h:270-275)
-  float pThr, pNrm, pTex;
+  float pThr, pNrm, pTex[NC];
   bool pend;
 };
 
 // Fold a deferred source contribution into totalSource (a no-op without one)
-template <int DIM>
-__device__ __forceinline__ void flush_source(WalkState<DIM>& st) {
+template <int DIM, int NC>
+__device__ __forceinline__ void flush_source(WalkState<DIM, NC>& st) {
   if (st.pend) {
-    st.totalSource += st.pThr * (st.pNrm * st.pTex);
+    for (int c = 0; c < NC; c++) st.totalSource[c] += st.pThr * (st.pNrm * st.pTex[c]);
     st.pend = false;
   }
 }
@@ -2254,9 +2282,9 @@ __device__ __forceinline__ int fcpw_stochastic_pick(const DevScene& sc, const fl
 // non-finite; only then the stochastic sample is evaluated -- at every step with
 // image-valued h (DevScene::nimg).  flip: this step flipped the walk's normal
 // (flipNormalOrientation, double-sided scenes); prec: silhouettePrecision.
-template <int DIM, bool RB>
+template <int DIM, bool RB, int NC>
 __device__ __forceinline__ void neumann_term(const DevScene& sc, const float* prims, const Gfn<DIM, RB>& g,
-                                             WalkState<DIM>& st, float R, const float* rn, bool flip, float prec) {
+                                             WalkState<DIM, NC>& st, float R, const float* rn, bool flip, float prec) {
   constexpr int PS = Layout<DIM>::prim;
   const int np = sc.n_prims;
   const float* x = st.pt;
@@ -2327,9 +2355,9 @@ __device__ __forceinline__ void neumann_term(const DevScene& sc, const float* pr
 //   star_radius_wave -- (convergent, all lanes) computeStarRadius;
 //   walk_step_end    -- ball update, direction, ray, source sample, move, roulette.
 // Returns -1 while the walk continues, else its termination code.
-template <int DIM>
+template <int DIM, int NC>
 __device__ __forceinline__ int walk_step_begin(const DevScene& sc, const DevParams& prm, float dirichletDist,
-                                               WalkState<DIM>& st, bool* flip, bool* query, float firstR = 0.0f) {
+                                               WalkState<DIM, NC>& st, bool* flip, bool* query, float firstR = 0.0f) {
   if (!(dirichletDist > prm.epsilon_shell)) return WC_DIRICHLET;
   *flip = false;
   // first step of a boundary-start walk: the precomputed first sphere radius
@@ -2346,9 +2374,9 @@ __device__ __forceinline__ int walk_step_begin(const DevScene& sc, const DevPara
 }
 
 // ball + direction + ray origin; the ray query follows (walk_on_stars.h:169-210)
-template <int DIM, bool RB>
+template <int DIM, bool RB, int NC>
 __device__ __forceinline__ float walk_step_mid(const DevParams& prm, float dirichletDist, Pcg32& smp, Gfn<DIM, RB>& g,
-                                               WalkState<DIM>& st, uint32_t* steps, bool query, float starQ,
+                                               WalkState<DIM, NC>& st, uint32_t* steps, bool query, float starQ,
                                                float* dir, float* org, float firstR = 0.0f) {
   float starRadius = dirichletDist;
   if (firstR > 0.0f) {
@@ -2379,9 +2407,9 @@ __device__ __forceinline__ float walk_step_mid(const DevParams& prm, float diric
 // the source sample (convergent, sample_volume_wave) and walk_step_tail follow
 // NEU = false: the instantiation for scenes whose Neumann term is provably +0 at every
 // step (DevParams::neumann_inert) -- the term's code is compiled out, the draws stay
-template <int DIM, bool RB, bool NEU = true>
+template <int DIM, bool RB, bool NEU = true, int NC>
 __device__ __forceinline__ void walk_step_end(const DevScene& sc, const DevParams& prm, const LGeom& G,
-                                              Pcg32& smp, Gfn<DIM, RB>& g, WalkState<DIM>& st, float starRadius,
+                                              Pcg32& smp, Gfn<DIM, RB>& g, WalkState<DIM, NC>& st, float starRadius,
                                               const float* dir, const float* org, bool hit, Hit& ip, bool flip) {
   const int np = sc.n_prims;
   const float* prims = G.prim;
@@ -2403,17 +2431,17 @@ __device__ __forceinline__ void walk_step_end(const DevScene& sc, const DevParam
 }
 
 // after the source sample (walk_on_stars.h:270-327)
-template <int DIM, bool RB>
+template <int DIM, bool RB, int NC>
 __device__ __forceinline__ int walk_step_tail(const DevScene& sc, const LGeom& G, const DevParams& prm,
                                               float& dirichletDist,
-                                              Pcg32& smp, Gfn<DIM, RB>& g, WalkState<DIM>& st, const float* dir,
+                                              Pcg32& smp, Gfn<DIM, RB>& g, WalkState<DIM, NC>& st, const float* dir,
                                               bool hit, const Hit& ip, const float* sp) {
   if (!prm.ignore_source) {
     flush_source<DIM>(st);
     if (g.r <= ip.d) {
       st.pNrm = g.norm();
       st.pThr = st.throughput;
-      st.pTex = source_value<DIM>(sc, sp);
+      source_values<DIM, NC>(sc, sp, st.pTex);
       st.pend = true;
     }
   }
@@ -3329,7 +3357,7 @@ __device__ __forceinline__ void build_lhs(const DevParams& prm, const unsigned l
 // 2D first balls: K0, I0, K1, I1 at the sampled radius from one fused Bessel evaluation
 // (pdf and gradient norm), and the second member reuses the first's gradient norm when its
 // radius is the same float -- identical values, fewer double-precision exp / sqrt / divisions
-template <int DIM, bool RB>
+template <int DIM, bool RB, int NC = 1>
 __device__ __forceinline__ void first_balls(const DevScene& sc, const DevParams& prm, const DevTasks& tk,
                                             const float* x, float firstR, const float* strat, int64_t gidx,
                                             bool active, int w, int64_t t0, bool yuk0, uint32_t* iters,
@@ -3363,7 +3391,8 @@ __device__ __forceinline__ void first_balls(const DevScene& sc, const DevParams&
     DIAG_T0(t_mem);
     const int64_t t = t0 + a;
     Gfn<DIM, RB> g = g0;
-    float throughput = 1.0f, totalSource = 0.0f, firstSource = 0.0f;
+    float throughput = 1.0f, totalSource[NC], firstSource[NC];
+    for (int c = 0; c < NC; c++) { totalSource[c] = 0.0f; firstSource[c] = 0.0f; }
     float sdir[DIM], bdir[DIM];
     for (int k = 0; k < DIM; k++) sdir[k] = 0.0f;
     if (!prm.ignore_source) {
@@ -3417,9 +3446,13 @@ __device__ __forceinline__ void first_balls(const DevScene& sc, const DevParams&
         g.r = normv<DIM>(sdv);
       }
       float gnorm = g.norm();
-      float contrib = gnorm * source_value<DIM>(sc, g.yVol);
-      totalSource += throughput * contrib;
-      firstSource = contrib;
+      float tex[NC];
+      source_values<DIM, NC>(sc, g.yVol, tex);
+      for (int c = 0; c < NC; c++) {
+        float contrib = gnorm * tex[c];
+        totalSource[c] += throughput * contrib;
+        firstSource[c] = contrib;
+      }
       float gr[DIM];
       if (DIM == 2 && g.yukawa == 1 && g.r == r_a) {
         // gradient() with the norm of member a's identical radius (same value)
@@ -3491,14 +3524,24 @@ __device__ __forceinline__ void first_balls(const DevScene& sc, const DevParams&
     DIAG_ADD(a == 0 ? D_FB_MA : D_FB_MB, t_mem);
     if (!active) continue;
     DIAG_T0(t_st);
-    tk.first[t] = firstSource;
+    if constexpr (NC == 1) {
+      tk.first[t] = firstSource[0];
+    } else {
+      for (int c = 0; c < NC; c++)
+        if (c < sc.n_channels) tk.first[(int64_t)c * T + t] = firstSource[c];
+    }
     for (int k = 0; k < DIM; k++) {
       tk.bdir[k * T + t] = bdir[k];
       tk.sdir[k * T + t] = sdir[k];
       tk.pt[k * T + t] = g.ySurf[k];
     }
     tk.thr[t] = throughput;
-    tk.tsrc[t] = totalSource;
+    if constexpr (NC == 1) {
+      tk.tsrc[t] = totalSource[0];
+    } else {
+      for (int c = 0; c < NC; c++)
+        if (c < sc.n_channels) tk.tsrc[(int64_t)c * T + t] = totalSource[c];
+    }
     // without Dirichlet geometry the distance is the bbox far corner of the walk start,
     // recomputed by the walk kernel from the same floats instead of stored and reloaded
     if (sc.n_dprims > 0) {
@@ -3718,7 +3761,8 @@ __global__ __launch_bounds__(256) void wos_point_setup_kernel(const DevScene sc,
 // (wos_robust.hip), so the reference-semantics kernels carry none of its code.
 // wos_point_setup_kernel ran first: point i's state and first-ball radius are read
 // from pstate / prad (no geometry is staged: the first balls query none).
-template <int DIM, bool RB = false>
+// NC: source channels (1, or kMaxChannels: source_values).
+template <int DIM, bool RB = false, int NC = 1>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(DIM == 2 ? WOS_FB_WAVES_PER_EU2 : WOS_FB_WAVES_PER_EU))) void wos_first_ball_kernel(
     const DevScene sc, const DevParams prm, const float* __restrict__ pts, int64_t n, int64_t base, int64_t stride,
     const DevTasks tk, unsigned long long* __restrict__ counters, unsigned int* __restrict__ work, int lhs_floats) {
@@ -3846,7 +3890,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(DIM == 2
     const int wend = P > 1 ? 1 : npairs;
     for (int w0 = 0; w0 < wend; w0 += kWave) {
       const int w = w0 + wl;
-      first_balls<DIM, RB>(sc, prm, tk, x, firstR, strat, gidx, estimate && w < npairs, w,
+      first_balls<DIM, RB, NC>(sc, prm, tk, x, firstR, strat, gidx, estimate && w < npairs, w,
                            (int64_t)pidx * tk.wpp + (int64_t)w * prm.n_anti, yuk0, &c_iters, rejL, lane,
                            pb, tk.ddir ? tk.ddir + (int64_t)pidx * DIM : nullptr);
     }
@@ -3878,10 +3922,10 @@ __device__ __forceinline__ void wave_priority(int level) {
 // ---- kernel 2: walks ---------------------------------------------------------
 // The state a walk task starts from (the hand-out of walk_on_stars.h:494-579 after
 // the first ball; BSTART: estimateSolution's boundary start, :437-439) ...
-template <int DIM, bool BSTART, bool RB>
+template <int DIM, bool BSTART, bool RB, int NC>
 __device__ __forceinline__ void walk_start(const DevScene& sc, const DevParams& prm, const DevTasks& tk, int64_t t,
-                                           uint32_t pidx, uint32_t w, const float* v_pt, float v_thr, float v_tsrc,
-                                           float v_dd, int64_t base, int64_t stride, bool yuk0, WalkState<DIM>& st,
+                                           uint32_t pidx, uint32_t w, const float* v_pt, float v_thr, const float* v_tsrc,
+                                           float v_dd, int64_t base, int64_t stride, bool yuk0, WalkState<DIM, NC>& st,
                                            Gfn<DIM, RB>& g, Pcg32& ws, float& ddist, uint32_t& wsteps, float& firstR) {
   for (int kk = 0; kk < DIM; kk++) { st.pt[kk] = v_pt[kk]; st.n[kk] = 0.0f; st.prevDir[kk] = 0.0f; }
   // prevDir/prevDist only matter once the walk stands on a Neumann boundary,
@@ -3891,7 +3935,7 @@ __device__ __forceinline__ void walk_start(const DevScene& sc, const DevParams& 
   st.onNeumann = false;
   st.walkLength = 0;
   st.totalNeumann = 0.0f;
-  st.totalSource = v_tsrc;
+  for (int c = 0; c < NC; c++) st.totalSource[c] = v_tsrc[c];
   st.pend = false;
   ddist = v_dd;
   g.init(yuk0, sc.absorption);
@@ -3914,9 +3958,9 @@ __device__ __forceinline__ void walk_start(const DevScene& sc, const DevParams& 
 // One iteration of the walk loop for every lane of the wave (convergent): the lanes
 // with active == false take part in the cooperative queries only.  Returns the
 // termination code (>= 0) or -1 while the walk continues.
-template <int DIM, bool GG, bool BSTART, bool RB, bool NEU = true>
+template <int DIM, bool GG, bool BSTART, bool RB, bool NEU = true, int NC>
 __device__ __forceinline__ int walk_iteration(const DevScene& sc, const DevParams& prm, const LGeom& G, bool active,
-                                              WalkState<DIM>& st, Gfn<DIM, RB>& gc, Pcg32& ws, float& ddist,
+                                              WalkState<DIM, NC>& st, Gfn<DIM, RB>& gc, Pcg32& ws, float& ddist,
                                               uint32_t& wsteps, float& firstR, StarLDS<DIM>* starL,
                                               RayLDS<DIM>* rayL, RejLDS* rejL, uint32_t* c_iters, int lane) {
   DIAG_T0(t_step);
@@ -3983,15 +4027,24 @@ __device__ __forceinline__ int walk_iteration(const DevScene& sc, const DevParam
 }
 
 // the record of a finished walk (walk_on_stars.h:583-585: escaped and over-length walks are dropped)
-template <int DIM>
+template <int DIM, int NC>
 __device__ __forceinline__ void walk_finish(const DevScene& sc, const DevParams& prm, const DevTasks& tk, int64_t t,
-                                            int code, WalkState<DIM>& st, uint32_t wsteps, unsigned int* s_ctr) {
+                                            int code, WalkState<DIM, NC>& st, uint32_t wsteps, unsigned int* s_ctr) {
   flush_source<DIM>(st);
   const bool recorded = code == WC_DIRICHLET || code == WC_RR;
   if (recorded) {
     const float term = (code == WC_DIRICHLET && !prm.ignore_dirichlet) ? dirichlet_value<DIM>(sc, st.pt) : 0.0f;
-    const float tot = st.throughput * term + st.totalNeumann + st.totalSource;
-    if (!WOS_ACCT_NOREC) tk.total[t] = tot;
+    if constexpr (NC == 1) {
+      const float tot = st.throughput * term + st.totalNeumann + st.totalSource[0];
+      if (!WOS_ACCT_NOREC) tk.total[t] = tot;
+    } else {
+      // channel c's Dirichlet constant g_c (DevScene::g_ch; image-valued data is shared by the channels)
+      const bool own_g = code == WC_DIRICHLET && !prm.ignore_dirichlet && sc.dimg == nullptr;
+      for (int c = 0; c < NC; c++) {
+        const float tot = st.throughput * (own_g ? sc.g_ch[c] : term) + st.totalNeumann + st.totalSource[c];
+        if (!WOS_ACCT_NOREC && c < sc.n_channels) tk.total[(int64_t)c * tk.T + t] = tot;
+      }
+    }
   }
   if (!WOS_ACCT_NOREC) tk.code[t] = (wsteps << 1) | (recorded ? 1u : 0u);
   DIAG_MAX(D_WMAXLEN, wsteps);
@@ -4053,16 +4106,17 @@ constexpr int kSpreadMax = 32;  // walks per hand-over
 // absorption is the scene's, and its ball -- c, R, r, y*, muR and the Bessel members -- is rebuilt
 // by update_ball before any use in the next step: walk_iteration), the PCG32 state, ddist,
 // wsteps, task
-template <int DIM>
-constexpr int walk_pack_words() { return (3 * DIM + 6 + 4) + 1 + 2 + 3; }
+template <int DIM, int NC = 1>
+constexpr int walk_pack_words() { return (3 * DIM + 6 + 4 + 2 * (NC - 1)) + 1 + 2 + 3; }
 // every member is moved (the struct sizes, bools padded to a word, match the counts)
 static_assert(sizeof(WalkState<2>) == 4 * (3 * 2 + 6 + 4), "WalkState<2> members");
 static_assert(sizeof(WalkState<3>) == 4 * (3 * 3 + 6 + 4), "WalkState<3> members");
+static_assert(sizeof(WalkState<2, kMaxChannels>) == 4 * (3 * 2 + 6 + 4 + 2 * (kMaxChannels - 1)), "WalkState<2, NC> members");
 static_assert(sizeof(Gfn<2, false>) == 4 * (1 + 3 * 2 + 9) && sizeof(Gfn<3, true>) == 4 * (1 + 3 * 3 + 9), "Gfn members");
 static_assert(sizeof(Pcg32) == 8, "Pcg32 state");
 // one walk's state into / out of mailbox slot `slot` (word-major, kSpreadMax slots per word)
-template <int DIM, bool RB>
-__device__ __forceinline__ void spread_put(uint32_t* mb, int slot, const WalkState<DIM>& st, const Gfn<DIM, RB>& g,
+template <int DIM, bool RB, int NC>
+__device__ __forceinline__ void spread_put(uint32_t* mb, int slot, const WalkState<DIM, NC>& st, const Gfn<DIM, RB>& g,
                                            const Pcg32& ws, float ddist, float firstR, uint32_t wsteps, uint32_t t) {
   int q = 0;
   auto put = [&](uint32_t v) {
@@ -4071,23 +4125,29 @@ __device__ __forceinline__ void spread_put(uint32_t* mb, int slot, const WalkSta
   auto putf = [&](float v) { put(__float_as_uint(v)); };
   for (int k = 0; k < DIM; k++) { putf(st.pt[k]); putf(st.n[k]); putf(st.prevDir[k]); }
   putf(st.prevDist); putf(st.throughput); put(st.onNeumann ? 1u : 0u); put((uint32_t)st.walkLength);
-  putf(st.totalNeumann); putf(st.totalSource);
-  putf(st.pThr); putf(st.pNrm); putf(st.pTex); put(st.pend ? 1u : 0u);
+  putf(st.totalNeumann);
+  for (int c = 0; c < NC; c++) putf(st.totalSource[c]);
+  putf(st.pThr); putf(st.pNrm);
+  for (int c = 0; c < NC; c++) putf(st.pTex[c]);
+  put(st.pend ? 1u : 0u);
   put((uint32_t)g.yukawa);
   put((uint32_t)ws.state); put((uint32_t)(ws.state >> 32));
   (void)firstR;  // 0 after every step (a boundary-start walk's first-sphere radius is used once)
   putf(ddist); put(wsteps); put(t);
 }
-template <int DIM, bool RB>
-__device__ __forceinline__ void spread_get(const uint32_t* mb, int slot, WalkState<DIM>& st, Gfn<DIM, RB>& g,
+template <int DIM, bool RB, int NC>
+__device__ __forceinline__ void spread_get(const uint32_t* mb, int slot, WalkState<DIM, NC>& st, Gfn<DIM, RB>& g,
                                            Pcg32& ws, float& ddist, float& firstR, uint32_t& wsteps, int64_t& t) {
   int q = 0;
   auto get = [&]() { return mb[(q++) * kSpreadMax + slot]; };
   auto getf = [&]() { return __uint_as_float(get()); };
   for (int k = 0; k < DIM; k++) { st.pt[k] = getf(); st.n[k] = getf(); st.prevDir[k] = getf(); }
   st.prevDist = getf(); st.throughput = getf(); st.onNeumann = get() != 0u; st.walkLength = (int)get();
-  st.totalNeumann = getf(); st.totalSource = getf();
-  st.pThr = getf(); st.pNrm = getf(); st.pTex = getf(); st.pend = get() != 0u;
+  st.totalNeumann = getf();
+  for (int c = 0; c < NC; c++) st.totalSource[c] = getf();
+  st.pThr = getf(); st.pNrm = getf();
+  for (int c = 0; c < NC; c++) st.pTex[c] = getf();
+  st.pend = get() != 0u;
   g.yukawa = (int)get();
   const uint32_t lo = get(), hi = get();
   ws.state = ((uint64_t)hi << 32) | lo;
@@ -4107,7 +4167,8 @@ struct SpreadLDS {
 // BSTART: the tasks are boundary-start walks (estimateSolution, walk_on_stars.h:353-464:
 // start normal, first sphere radius, on-Neumann flag from DevTasks::n0/r0/sflags, no
 // first ball, walk stream tag 6) -- boundary value caching (wos_bvc.hip).
-template <int DIM, bool GG, bool BSTART = false, bool RB = false, bool NEU = true, bool SPR = false>
+// NC: source channels carried by every walk (1, or kMaxChannels: source_values).
+template <int DIM, bool GG, bool BSTART = false, bool RB = false, bool NEU = true, bool SPR = false, int NC = 1>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(DIM == 2 ? WOS_WALK_WAVES_PER_EU : WOS_WALK_WAVES_PER_EU3))) void wos_walk_kernel(
     const DevScene sc_arg, const DevParams prm_arg, const DevTasks tk_arg, int64_t base, int64_t stride,
     unsigned long long* __restrict__ counters, unsigned int* __restrict__ tqueue, int geom_floats) {
@@ -4117,7 +4178,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(DIM == 2
   const DevScene& sc = sc_arg;
   const DevParams& prm = prm_arg;
   const DevTasks& tk = tk_arg;
-  static_assert(walk_pack_words<DIM>() * kSpreadMax * 4 <= (int)walk_scratch_bytes<DIM>(), "mailbox fits the scratch");
+  static_assert(walk_pack_words<DIM, NC>() * kSpreadMax * 4 <= (int)walk_scratch_bytes<DIM>(), "mailbox fits the scratch");
+  static_assert(!(BSTART && NC != 1), "boundary-start walks carry one channel");
   constexpr bool kSpread = SPR;
   const int lane = threadIdx.x & (kWave - 1);
   stage_geometry<DIM, GG>(sc, smem, true);
@@ -4231,7 +4293,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(DIM == 2
   };
   refill(tk);
   int64_t t = -1;           // this lane's task
-  WalkState<DIM> st;
+  WalkState<DIM, NC> st;
   Gfn<DIM, RB> g;
   Pcg32 ws;
   float ddist = 0.0f;
@@ -4262,11 +4324,17 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(DIM == 2
         const uint32_t v_pk = (uint32_t)__shfl((int)(s_t | (s_ok ? 0x80000000u : 0u)), src);
         const uint32_t v_t = v_pk & 0x7FFFFFFFu;
         const uint32_t v_ok = v_pk >> 31;
-        float v_pt[DIM], v_thr = 0.0f, v_tsrc = 0.0f, v_dd = 0.0f;
+        float v_pt[DIM], v_thr = 0.0f, v_tsrc[NC], v_dd = 0.0f;
+        for (int c = 0; c < NC; c++) v_tsrc[c] = 0.0f;
         if (t < 0 && rank < take && v_ok) {  // the task record from memory, at hand-out
           for (int kk = 0; kk < DIM; kk++) v_pt[kk] = tk.pt[kk * tk.T + v_t];
           v_thr = tk.thr[v_t];
-          v_tsrc = tk.tsrc[v_t];
+          if constexpr (NC == 1) {
+            v_tsrc[0] = tk.tsrc[v_t];
+          } else {
+            for (int c = 0; c < NC; c++)
+              if (c < sc.n_channels) v_tsrc[c] = tk.tsrc[(int64_t)c * tk.T + v_t];
+          }
           // boundary-start walks (BVC) always carry a stored distance
           v_dd = (BSTART || sc.n_dprims > 0) ? tk.dd[v_t] : bbox_far_dist<DIM>(sc, v_pt);
         }

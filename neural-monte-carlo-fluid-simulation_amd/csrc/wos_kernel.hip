@@ -129,6 +129,8 @@ hipError_t launch_first_balls(int dim, const DevScene& sc, const DevParams& prm,
                               unsigned int* work, int grid, size_t shmem, int lhs_floats, hipStream_t s) {
   if (prm.robust)
     return launch_first_balls_rb(dim, sc, prm, pts, n, base, stride, tk, counters, work, grid, shmem, lhs_floats, s);
+  if (sc.n_channels > 1)
+    return launch_first_balls_mc(dim, sc, prm, pts, n, base, stride, tk, counters, work, grid, shmem, lhs_floats, s);
   if (dim == 2)
     hipLaunchKernelGGL(wos_first_ball_kernel<2>, dim3(grid), dim3(kBlock), shmem, s, sc, prm, pts, n, base, stride, tk,
                        counters, work, lhs_floats);
@@ -171,6 +173,8 @@ hipError_t launch_walks(int dim, const DevScene& sc, const DevParams& prm, const
                         int geom_floats, hipStream_t s) {
   if (prm.robust)
     return launch_walks_rb(dim, false, sc, prm, tk, base, stride, counters, tqueue, grid, shmem, geom_floats, s);
+  if (sc.n_channels > 1)
+    return launch_walks_mc(dim, sc, prm, tk, base, stride, counters, tqueue, grid, shmem, geom_floats, s);
 #define WOS_LAUNCH_WALK(D, G)                                                                                    \
   do {                                                                                                           \
     if (prm.neumann_inert)                                                                                       \
@@ -239,8 +243,10 @@ int first_ball_points_per_wave(int n_pairs) { return fb_points_per_wave(n_pairs)
 
 size_t walk_wave_lds_bytes(int dim) { return dim == 2 ? walk_scratch_bytes<2>() : walk_scratch_bytes<3>(); }
 
-hipError_t occupancy_blocks_per_cu(int which, int dim, bool geom_global, size_t shmem, int* blocks, bool robust) {
-  if (robust) return occupancy_rb(which, dim, geom_global, shmem, blocks);
+hipError_t occupancy_blocks_per_cu(int which, int dim, bool geom_global, size_t shmem, int* blocks, bool robust,
+                                   bool multi) {
+  if (robust) return occupancy_rb(which, dim, geom_global, shmem, blocks, multi);
+  if (multi && which == 0) return occupancy_first_ball_mc(dim, shmem, blocks);
   if (which == 0)
     return dim == 2 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, wos_first_ball_kernel<2>, kBlock, shmem)
                     : hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, wos_first_ball_kernel<3>, kBlock, shmem);
@@ -253,8 +259,10 @@ hipError_t occupancy_blocks_per_cu(int which, int dim, bool geom_global, size_t 
 
 // residency of the walk instantiation launch_walks dispatches for these parameters (the
 // tail-spreading and Neumann-inert kernels differ in static LDS and registers)
-hipError_t occupancy_walk_blocks_per_cu(int dim, bool geom_global, const DevParams& prm, size_t shmem, int* blocks) {
-  if (prm.robust) return occupancy_rb(1, dim, geom_global, shmem, blocks);
+hipError_t occupancy_walk_blocks_per_cu(int dim, bool geom_global, const DevParams& prm, size_t shmem, int* blocks,
+                                        bool multi) {
+  if (prm.robust) return occupancy_rb(1, dim, geom_global, shmem, blocks, multi);
+  if (multi) return occupancy_walk_mc(dim, geom_global, prm, shmem, blocks);
 #define WOS_OCC(K) hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, K, kBlock, shmem)
   const bool inert = prm.neumann_inert != 0;
   if (dim == 2) {

@@ -37,9 +37,11 @@ int first_ball_points_per_wave(int n_pairs);
 size_t walk_wave_lds_bytes(int dim);
 // which: 0 first-ball kernel, 1 walk kernel (the instantiation for LDS-staged or global geometry);
 // robust: the robust-float instantiations (wos_robust.hip)
+// multi: the instantiations of a scene with several source channels (DevScene::n_channels > 1)
 hipError_t occupancy_blocks_per_cu(int which, int dim, bool geom_global, size_t shmem, int* blocks,
-                                   bool robust = false);
-hipError_t occupancy_walk_blocks_per_cu(int dim, bool geom_global, const DevParams& prm, size_t shmem, int* blocks);
+                                   bool robust = false, bool multi = false);
+hipError_t occupancy_walk_blocks_per_cu(int dim, bool geom_global, const DevParams& prm, size_t shmem, int* blocks,
+                                        bool multi = false);
 void diag_dump(const char* tag);  // WOS_DIAG builds: print + reset the walk-kernel diagnostics
 void diag_dump_bstart(const char* tag);  // ... of the boundary-start walk kernels (wos_bvc.hip)
 void diag_print(const char* tag, const void* sym);
@@ -73,5 +75,25 @@ hipError_t launch_walks_rb(int dim, bool bstart, const DevScene& sc, const DevPa
                            int64_t base, int64_t stride, unsigned long long* counters, unsigned int* tqueue, int grid,
                            size_t shmem, int geom_floats, hipStream_t s);
 // which: 0 first-ball, 1 walk, 2 boundary-start walk
-hipError_t occupancy_rb(int which, int dim, bool geom_global, size_t shmem, int* blocks);
+hipError_t occupancy_rb(int which, int dim, bool geom_global, size_t shmem, int* blocks, bool multi = false);
+// several source channels on one set of walks (wos_channels.hip): the first-ball and walk
+// instantiations with kMaxChannels channels; the launchers above dispatch here when
+// sc.n_channels > 1 (robust float semantics: wos_channels_rb.hip, reached through wos_robust.hip's launchers)
+hipError_t launch_first_balls_mc(int dim, const DevScene& sc, const DevParams& prm, const float* pts, int64_t n,
+                                 int64_t base, int64_t stride, const DevTasks& tk, unsigned long long* counters,
+                                 unsigned int* work, int grid, size_t shmem, int lhs_floats, hipStream_t s);
+hipError_t launch_walks_mc(int dim, const DevScene& sc, const DevParams& prm, const DevTasks& tk, int64_t base,
+                           int64_t stride, unsigned long long* counters, unsigned int* tqueue, int grid, size_t shmem,
+                           int geom_floats, hipStream_t s);
+hipError_t occupancy_first_ball_mc(int dim, size_t shmem, int* blocks);
+hipError_t occupancy_walk_mc(int dim, bool geom_global, const DevParams& prm, size_t shmem, int* blocks);
+hipError_t launch_first_balls_rb_mc(int dim, const DevScene& sc, const DevParams& prm, const float* pts, int64_t n,
+                                    int64_t base, int64_t stride, const DevTasks& tk, unsigned long long* counters,
+                                    unsigned int* work, int grid, size_t shmem, int lhs_floats, hipStream_t s);
+hipError_t launch_walks_rb_mc(int dim, const DevScene& sc, const DevParams& prm, const DevTasks& tk, int64_t base,
+                              int64_t stride, unsigned long long* counters, unsigned int* tqueue, int grid,
+                              size_t shmem, int geom_floats, hipStream_t s);
+hipError_t occupancy_rb_mc(int which, int dim, bool geom_global, size_t shmem, int* blocks);  // which: 0, 1
+// planar [channels][cells] -> texels [cells][kMaxChannels] (channels beyond `channels`: +0)
+hipError_t launch_source_pack(const float* planar, float* texels, int64_t cells, int channels, hipStream_t s);
 }  // namespace wos

@@ -26,10 +26,11 @@ WOS_RB_WALK(3, true, false);
 WOS_RB_WALK(2, false, true);  // boundary value caching (boundary-start walks)
 WOS_RB_WALK(2, true, true);
 #undef WOS_RB_WALK
-
 hipError_t launch_first_balls_rb(int dim, const DevScene& sc, const DevParams& prm, const float* pts, int64_t n,
                                  int64_t base, int64_t stride, const DevTasks& tk, unsigned long long* counters,
                                  unsigned int* work, int grid, size_t shmem, int lhs_floats, hipStream_t s) {
+  if (sc.n_channels > 1)  // several source channels: wos_channels_rb.hip
+    return launch_first_balls_rb_mc(dim, sc, prm, pts, n, base, stride, tk, counters, work, grid, shmem, lhs_floats, s);
   if (dim == 2)
     hipLaunchKernelGGL((wos_first_ball_kernel<2, true>), dim3(grid), dim3(kBlock), shmem, s, sc, prm, pts, n, base,
                        stride, tk, counters, work, lhs_floats);
@@ -45,6 +46,10 @@ hipError_t launch_walks_rb(int dim, bool bstart, const DevScene& sc, const DevPa
 #define WOS_LAUNCH_WALK(D, G, B)                                                                                  \
   hipLaunchKernelGGL((wos_walk_kernel<D, G, B, true>), dim3(grid), dim3(kBlock), shmem, s, sc, prm, tk, base, stride, \
                      counters, tqueue, geom_floats)
+  if (sc.n_channels > 1) {
+    if (bstart) return hipErrorInvalidValue;  // boundary value caching is single-channel
+    return launch_walks_rb_mc(dim, sc, prm, tk, base, stride, counters, tqueue, grid, shmem, geom_floats, s);
+  }
   if (bstart) {
     if (dim != 2) return hipErrorInvalidValue;
     if (sc.geom_global) WOS_LAUNCH_WALK(2, true, true); else WOS_LAUNCH_WALK(2, false, true);
@@ -57,8 +62,9 @@ hipError_t launch_walks_rb(int dim, bool bstart, const DevScene& sc, const DevPa
   return hipGetLastError();
 }
 
-hipError_t occupancy_rb(int which, int dim, bool geom_global, size_t shmem, int* blocks) {
+hipError_t occupancy_rb(int which, int dim, bool geom_global, size_t shmem, int* blocks, bool multi) {
 #define WOS_OCC(K) hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, K, kBlock, shmem)
+  if (multi && which != 2) return occupancy_rb_mc(which, dim, geom_global, shmem, blocks);
   switch (which) {
     case 0:
       return dim == 2 ? WOS_OCC((wos_first_ball_kernel<2, true>)) : WOS_OCC((wos_first_ball_kernel<3, true>));

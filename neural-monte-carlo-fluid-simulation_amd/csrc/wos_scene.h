@@ -12,7 +12,8 @@
 //           2D  [p.xy n0.xy n1.xy miss pad]                    (8 floats)
 //           3D  [pa.xyz pb.xyz n0.xyz n1.xyz miss pad pad pad] (16 floats)
 //   dprim/dpaux : same as prim/paux for the (optional) Dirichlet boundary
-//   source: the -div(u) grid, row-major; 2D (H rows ~ y, W cols ~ x), 3D (X,Y,Z)
+//   source: the -div(u) grid, row-major; 2D (H rows ~ y, W cols ~ x), 3D (X,Y,Z);
+//           with n_channels > 1 texel-interleaved, [cell][kMaxChannels] (unused channels +0)
 //   pgroup/sgroup: padded boxes of kGroup consecutive prims / silhouettes
 //           (8 / 16 floats, see kSGroupStride), used only to skip whole groups
 //
@@ -25,6 +26,8 @@ namespace wos {
 constexpr int kPrimStride2 = 4, kPrimStride3 = 9;
 constexpr int kAuxStride2 = 6, kAuxStride3 = 21;
 constexpr int kSilStride2 = 8, kSilStride3 = 16;
+// most source channels of one solve (WOS_MAX_CHANNELS): one 16-byte texel per grid cell
+constexpr int kMaxChannels = 4;
 // culling groups: kGroup consecutive primitives (or silhouette candidates) share
 // one padded bounding box record [min.xyz pad max.xyz pad]; silhouette groups add
 // a bounding sphere and the cone of their adjacent normals:
@@ -105,6 +108,10 @@ struct DevScene {
   int32_t dgrid_off_words;
   int32_t dgrid_n[2];
   float dgrid_min[2], dgrid_inv[2];
+  // source channels (wos_scene_set_source_channels; 1: the plain grid) and channel c's
+  // Dirichlet constant (g_dirichlet unless given per channel; unused with dimg)
+  int32_t n_channels;
+  float g_ch[kMaxChannels];
 };
 
 struct DevParams {
@@ -160,12 +167,12 @@ constexpr float kRejTabScale = 8.0f;
 struct DevTasks {
   float* pt;        // [DIM][T] walk start: the first ball's boundary sample
   float* thr;       // [T] throughput after the first ball
-  float* tsrc;      // [T] source contribution of the first ball
+  float* tsrc;      // [C][T] source contribution of the first ball (C = DevScene::n_channels)
   float* dd;        // [T] Dirichlet distance at pt
-  float* first;     // [T] record: first-ball source value (control variate)
+  float* first;     // [C][T] record: first-ball source value (control variate)
   float* bdir;      // [DIM][T] record: boundary gradient direction
   float* sdir;      // [DIM][T] record: source gradient direction
-  float* total;     // [T] record: walk total
+  float* total;     // [C][T] record: walk total
   uint32_t* code;   // [T] record: (steps << 1) | recorded
   int32_t* pstate;  // [n] bit0 estimated, bit1 mask p, bit2 mask grad p, bits 8..12 cost bucket
   uint32_t* perm;   // [n] walk-queue order of the points (longest expected walks first)
@@ -192,8 +199,9 @@ struct DevTasks {
   float* deriv;
 };
 
-// floats per task: start state pt[DIM] thr tsrc dd, record first bdir[DIM] sdir[DIM] total code
-constexpr int task_floats(int dim) { return 3 * dim + 6; }
+// floats per task: start state pt[DIM] thr tsrc dd, record first bdir[DIM] sdir[DIM] total code;
+// every source channel beyond the first adds its own tsrc, first and total
+constexpr int task_floats(int dim, int channels = 1) { return 3 * dim + 6 + 3 * (channels - 1); }
 constexpr int kCostBuckets = 32;
 
 }  // namespace wos

@@ -14,6 +14,7 @@ WOS_OK = 0
 WOS_E_CAPACITY = -4
 WOS_PTRS_DEVICE = 0x1
 WOS_ASYNC = 0x2
+MAX_CHANNELS = 4  # include/wos.h WOS_MAX_CHANNELS
 
 
 class WosError(RuntimeError):
@@ -100,6 +101,7 @@ EXPORTS = (
     "wos_scene_get_info", "wos_scene_set_source", "wos_release_caches", "wos_default_params", "wos_solve", "wos_solve_var",
     "wos_solve_stats", "wos_default_bvc_params", "wos_bvc",
     "wos_selftest_math", "wos_last_error", "wos_abi_version", "wos_device_count", "wos_set_max_batch_tasks",
+    "wos_scene_set_source_channels", "wos_scene_channels", "wos_solve_channels",
 )
 
 _lib = None
@@ -139,6 +141,15 @@ def load():
     L.wos_solve_var.argtypes = [C.c_void_p, C.POINTER(SolverParams), C.c_void_p, C.c_int64, C.c_int64,
                                 C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                 C.c_void_p, C.POINTER(Stats), C.c_void_p, C.c_uint32]
+    L.wos_scene_set_source_channels.restype = C.c_int
+    L.wos_scene_set_source_channels.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32),
+                                                C.POINTER(C.c_float), C.c_int32, C.c_void_p]
+    L.wos_scene_channels.restype = C.c_int32
+    L.wos_scene_channels.argtypes = [C.c_void_p]
+    L.wos_solve_channels.restype = C.c_int
+    L.wos_solve_channels.argtypes = [C.c_void_p, C.POINTER(SolverParams), C.c_void_p, C.c_int64, C.c_int64,
+                                     C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.POINTER(Stats), C.c_void_p, C.c_uint32]
     L.wos_solve_stats.restype = C.c_int
     L.wos_solve_stats.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(Stats)]
     L.wos_default_bvc_params.restype = None

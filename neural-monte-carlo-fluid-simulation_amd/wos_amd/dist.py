@@ -26,7 +26,10 @@ def sharded_projection(solve_local, pts, rank, world, dim, group=None, device=No
     Returns full (p [N], grad [N, dim]) torch tensors on every rank.  A solve_local that
     returns four tensors (p, grad, p_var [n_local], grad_var [n_local, dim]) -- a solve
     with variance=True -- gets four full tensors back, through the same single collective
-    with 2 + 2 * dim columns.
+    with 2 + 2 * dim columns.  A solve_local that returns channel-major tensors -- p [C, n_local],
+    grad [C, n_local, dim] (and the variances alike): several source channels on one set of
+    walks -- gets channel-major full tensors back, p [C, N], grad [C, N, dim], still through
+    the one collective, whose rows are then C * (1 + dim) columns wide (doubled with variance).
 
     One code path for every backend: the shard, padded to n_pad rows, goes through ONE
     `all_gather_into_tensor` into a (world * n_pad, 1 + dim) buffer (RCCL over xGMI with
@@ -43,9 +46,14 @@ def sharded_projection(solve_local, pts, rank, world, dim, group=None, device=No
     res = tuple(solve_local(local, rank, world))
     if len(res) not in (2, 4):
         raise ValueError(f"solve_local must return (p, grad) or (p, grad, p_var, grad_var), got {len(res)} values")
-    # columns: p | grad[dim] (| p_var | grad_var[dim])
-    widths = (1, dim) * (len(res) // 2)
-    cols = [torch.as_tensor(t, device=device).reshape(-1, w) for t, w in zip(res, widths)]
+    res = tuple(torch.as_tensor(t, device=device) for t in res)
+    # channel-major results (grad [C, n_local, dim]): point-major rows with the channels side by side
+    nch = res[1].shape[0] if res[1].ndim == 3 else 0
+    if nch:
+        res = tuple(t.reshape(nch, idx.size, -1).permute(1, 0, 2) for t in res)
+    # columns: p | grad[dim] (| p_var | grad_var[dim]); with channels p[C] | grad[C][dim] (| ...)
+    widths = tuple(w * max(nch, 1) for w in (1, dim) * (len(res) // 2))
+    cols = [t.reshape(-1, w) for t, w in zip(res, widths)]
     p = cols[0]
     ncol = sum(widths)
     gathered = world > 1 or force_gather
@@ -69,8 +77,12 @@ def sharded_projection(solve_local, pts, rank, world, dim, group=None, device=No
     # rank r) are exactly the indices >= n
     full = buf.view(world, n_pad, ncol).transpose(0, 1).reshape(world * n_pad, ncol)[:n]
     out, c0 = [], 0
-    for w in widths:
-        out.append(full[:, c0].contiguous() if w == 1 else full[:, c0:c0 + w].contiguous())
+    for k, w in enumerate(widths):
+        if nch:  # back to channel-major: p [C, N], grad [C, N, dim]
+            t = full[:, c0:c0 + w].reshape(n, nch, w // nch).permute(1, 0, 2)
+            out.append(t[..., 0].contiguous() if k % 2 == 0 else t.contiguous())
+        else:
+            out.append(full[:, c0].contiguous() if w == 1 else full[:, c0:c0 + w].contiguous())
         c0 += w
     return tuple(out)
 

@@ -99,13 +99,30 @@ def _is_torch(x):
     return type(x).__module__.startswith("torch")
 
 
+def _check_source_shape(shape, dim):
+    """(has a channel axis, channels) of a source of this shape; WosError if it fits neither form."""
+    shape = tuple(int(s) for s in shape)
+    if len(shape) == dim:
+        return False, 1
+    if len(shape) == dim + 1:
+        if not 1 <= shape[0] <= _lib.MAX_CHANNELS:
+            raise WosError(f"a source with a channel axis holds 1..{_lib.MAX_CHANNELS} channels, got shape {shape}")
+        return True, shape[0]
+    raise WosError(f"source grid must be {dim}-D, or {dim + 1}-D with a leading channel axis, got shape {shape}")
+
+
 class WosScene:
     """Geometry + source field resident on one GPU."""
 
     def __init__(self, vertices, prims, source=None, absorption=0.0, *, dvertices=None, dprims=None,
                  dirichlet_value=0.0, dirichlet_image=None, dirichlet_image_box=None, neumann_image=None,
-                 neumann_image_box=None, watertight=True, double_sided=False, device=0):
-        """dirichlet_image (2D, optional): g as an image [H, W] (row ~ y) over the rectangle
+                 neumann_image_box=None, watertight=True, double_sided=False, device=0, dirichlet_values=None):
+        """source: the grid [H, W] / [X, Y, Z], or several source fields on one set of walks,
+        [C, H, W] / [C, X, Y, Z] with C <= 4 (wos_scene_set_source_channels): solve() then returns
+        every output with the same leading channel axis (for C = 1 too), channel c bit for bit
+        the solve of source c alone.  dirichlet_values (optional, with a channel axis): the
+        constant g_c of every channel instead of dirichlet_value.
+        dirichlet_image (2D, optional): g as an image [H, W] (row ~ y) over the rectangle
         dirichlet_image_box = (x0, y0, ex, ey), evaluated at each walk's projection onto the
         Dirichlet boundary (the upstream demo's pde.dirichlet, scene.h:202-207); replaces the
         constant dirichlet_value.  neumann_image (2D, optional): the Neumann data h as an image
@@ -159,6 +176,12 @@ class WosScene:
         d.is_watertight = int(bool(watertight))
         d.is_double_sided = int(bool(double_sided))
         self.source_shape = None
+        self._channel_axis = False
+        chan_source = None
+        if source is not None and _check_source_shape(tuple(source.shape), self.dim)[0]:
+            chan_source, source = source, None  # set after the scene exists (set_source)
+        elif dirichlet_values is not None:
+            raise WosError("dirichlet_values needs a source with a leading channel axis")
         if source is not None:
             if _is_torch(source) and source.is_cuda:
                 src = source.detach().to(dtype=__import__("torch").float32).contiguous()
@@ -183,6 +206,11 @@ class WosScene:
         check(L.wos_scene_create(C.byref(d), self.device, C.byref(h)), "wos_scene_create")
         self._h = h
         del keep
+        if chan_source is not None:
+            self.set_source(chan_source, dirichlet_values=dirichlet_values)
+            if _is_torch(chan_source) and chan_source.is_cuda:
+                # like wos_scene_create's copy: done when the constructor returns
+                __import__("torch").cuda.current_stream(chan_source.device).synchronize()
 
     @staticmethod
     def _image(img, box, name):
@@ -199,13 +227,28 @@ class WosScene:
             raise WosError(f"{name} must be 2-D, got shape {tuple(out.shape)}")
         return out, on_dev
 
-    def set_source(self, source, stream=None):
+    @property
+    def channels(self):
+        """Source channels the scene holds (1 for a source without a channel axis)."""
+        return int(_lib.load().wos_scene_channels(self._h))
+
+    def set_source(self, source, stream=None, *, dirichlet_values=None):
         """Replace the source grid (-div u) in place: the geometry stays resident.
         `source` is a numpy array or a torch tensor (a CUDA tensor is copied
         device-to-device on torch's current stream, no host round trip).  Replaces
-        the reference's per-step Scene(sceneConfig, div) (model_split.py:191)."""
+        the reference's per-step Scene(sceneConfig, div) (model_split.py:191).
+        A source with one extra leading axis, [C, ...] with C <= 4, makes the scene
+        multi-channel (see __init__); dirichlet_values: C constants g_c, or None for the
+        scene's own Dirichlet data.  A source without the axis returns it to one channel."""
         L = _lib.load()
         dims = (C.c_int32 * 3)(0, 0, 0)
+        axis, nch = _check_source_shape(tuple(source.shape), self.dim)
+        if dirichlet_values is not None:
+            if not axis:
+                raise WosError("dirichlet_values needs a source with a leading channel axis")
+            gv = np.ascontiguousarray(dirichlet_values, dtype=np.float32).reshape(-1)
+            if gv.shape[0] != nch:
+                raise WosError(f"dirichlet_values must hold one constant per channel ({nch}), got {gv.shape[0]}")
         if _is_torch(source) and source.is_cuda:
             import torch
             src = source.detach().to(dtype=torch.float32).contiguous()
@@ -219,14 +262,19 @@ class WosScene:
             src = np.ascontiguousarray(source, dtype=np.float32)
             shape = src.shape
             ptr, on_dev = src.ctypes.data, 0
-        if len(shape) != self.dim:
-            raise WosError(f"source grid must be {self.dim}-D, got shape {shape}")
-        for k in range(len(shape)):
-            dims[k] = int(shape[k])
-        check(L.wos_scene_set_source(self._h, ptr, dims, on_dev, stream), "wos_scene_set_source")
+        grid = shape[1:] if axis else shape
+        for k in range(len(grid)):
+            dims[k] = int(grid[k])
+        if axis:
+            gp = gv.ctypes.data_as(C.POINTER(C.c_float)) if dirichlet_values is not None else None
+            check(L.wos_scene_set_source_channels(self._h, ptr, nch, dims, gp, on_dev, stream),
+                  "wos_scene_set_source_channels")
+        else:
+            check(L.wos_scene_set_source(self._h, ptr, dims, on_dev, stream), "wos_scene_set_source")
         # the copy is ordered on `stream`: keep the buffer alive until the next replacement
         self._src_keep = src
         self.source_shape = tuple(int(x) for x in shape)
+        self._channel_axis = axis
 
     @classmethod
     def from_obj(cls, path, dim, source=None, absorption=0.0, flip_orientation=False, normalize=False, **kw):
@@ -249,23 +297,27 @@ class WosScene:
         walk_on_stars.h:811-831), masked like their means.  With GPU tensors
         and sync=False the solve is only enqueued on the stream: the stats dict then holds
         just "ticket"; solve_stats(ticket) waits for that solve and returns the full dict.
+        A scene whose source has a channel axis [C, ...] returns p [C, N], grad [C, N, dim] and
+        the variances alike (wos_solve_channels); n_est and steps stay [N], shared by the channels.
         `stream`: a torch.cuda.Stream or a raw hipStream_t handle (default: torch's current
         stream)."""
         L = _lib.load()
         params = params if params is not None else solver_params()
         st = Stats()
+        nch = self.channels if self._channel_axis else 0
+        lead = (nch,) if self._channel_axis else ()
         if _is_torch(pts) and pts.is_cuda:
             import torch
             x = pts.detach().to(torch.float32).contiguous()
             n = x.shape[0]
             if x.ndim != 2 or x.shape[1] != self.dim:
                 raise WosError(f"points must be [N,{self.dim}]")
-            p = torch.empty(n, dtype=torch.float32, device=x.device)
-            g = torch.empty(n, self.dim, dtype=torch.float32, device=x.device)
+            p = torch.empty(lead + (n,), dtype=torch.float32, device=x.device)
+            g = torch.empty(lead + (n, self.dim), dtype=torch.float32, device=x.device)
             ne = torch.empty(n, dtype=torch.int32, device=x.device) if counts else None
             sp = torch.empty(n, dtype=torch.int32, device=x.device) if counts else None
-            pv = torch.empty(n, dtype=torch.float32, device=x.device) if variance else None
-            gv = torch.empty(n, self.dim, dtype=torch.float32, device=x.device) if variance else None
+            pv = torch.empty(lead + (n,), dtype=torch.float32, device=x.device) if variance else None
+            gv = torch.empty(lead + (n, self.dim), dtype=torch.float32, device=x.device) if variance else None
             cur = torch.cuda.current_stream(x.device)
             ts = None
             if stream is None:
@@ -279,7 +331,13 @@ class WosScene:
                 # produced x, the allocator's last user of p / g)
                 ts.wait_stream(cur)
             flags = _lib.WOS_PTRS_DEVICE | (0 if sync else _lib.WOS_ASYNC)
-            if variance:
+            if self._channel_axis:
+                check(L.wos_solve_channels(self._h, C.byref(params), x.data_ptr(), n, index_base, index_stride, nch,
+                                           p.data_ptr(), g.data_ptr(), pv.data_ptr() if variance else None,
+                                           gv.data_ptr() if variance else None, ne.data_ptr() if counts else None,
+                                           sp.data_ptr() if counts else None, C.byref(st), s, flags),
+                      "wos_solve_channels")
+            elif variance:
                 check(L.wos_solve_var(self._h, C.byref(params), x.data_ptr(), n, index_base, index_stride,
                                       p.data_ptr(), g.data_ptr(), pv.data_ptr(), gv.data_ptr(),
                                       ne.data_ptr() if counts else None, sp.data_ptr() if counts else None,
@@ -302,13 +360,19 @@ class WosScene:
             if x.ndim != 2 or x.shape[1] != self.dim:
                 raise WosError(f"points must be [N,{self.dim}]")
             n = x.shape[0]
-            p = np.empty(n, np.float32)
-            g = np.empty((n, self.dim), np.float32)
+            p = np.empty(lead + (n,), np.float32)
+            g = np.empty(lead + (n, self.dim), np.float32)
             ne = np.empty(n, np.int32) if counts else None
             sp = np.empty(n, np.int32) if counts else None
-            pv = np.empty(n, np.float32) if variance else None
-            gv = np.empty((n, self.dim), np.float32) if variance else None
-            if variance:
+            pv = np.empty(lead + (n,), np.float32) if variance else None
+            gv = np.empty(lead + (n, self.dim), np.float32) if variance else None
+            if self._channel_axis:
+                check(L.wos_solve_channels(self._h, C.byref(params), x.ctypes.data, n, index_base, index_stride, nch,
+                                           p.ctypes.data, g.ctypes.data, pv.ctypes.data if variance else None,
+                                           gv.ctypes.data if variance else None, ne.ctypes.data if counts else None,
+                                           sp.ctypes.data if counts else None, C.byref(st), stream, 0),
+                      "wos_solve_channels")
+            elif variance:
                 check(L.wos_solve_var(self._h, C.byref(params), x.ctypes.data, n, index_base, index_stride,
                                       p.ctypes.data, g.ctypes.data, pv.ctypes.data, gv.ctypes.data,
                                       ne.ctypes.data if counts else None, sp.ctypes.data if counts else None,

@@ -163,7 +163,10 @@ class PressureProjector:
         """wost_pressure (model_split.py:185-202) with device tensors in and out; with a
         process group, this rank's stride shard + one all-gather (wos_amd.dist).
         variance=True: (p, grad_p, p_var, grad_var) -- the per-walk sample variances of
-        WosScene.solve(..., variance=True), gathered by the same collective."""
+        WosScene.solve(..., variance=True), gathered by the same collective.
+        A `div` with a leading channel axis, (C, ...) with C <= 4, solves the C source fields
+        on one set of walks and returns channel-major outputs, p [C, N] and grad_p [C, N, dim]
+        (the variances alike) -- with a process group still through one all-gather."""
         self._set_source(div)
         kw = {"variance": True} if variance else {}
         if self.group is None and not self.force_gather:

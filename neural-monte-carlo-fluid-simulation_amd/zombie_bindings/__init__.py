@@ -89,6 +89,21 @@ def _junction_near_misses(v, dv, rel=1e-6):
     return n
 
 
+def _obj_dim(path):
+    """2 for an OBJ of line segments (`l` records, scene.h:104-145), 3 for one of faces (`f`),
+    None if it has neither or cannot be read here (the loader reports that)."""
+    try:
+        with open(path, "r", errors="replace") as f:
+            for line in f:
+                if line.startswith("l "):
+                    return 2
+                if line.startswith("f "):
+                    return 3
+    except OSError:
+        pass
+    return None
+
+
 def _read_pfm(path):
     """readPFM (image.h:105-149): file row order, double-precision grayscale."""
     return _image.read_pfm(path)
@@ -111,6 +126,11 @@ class Scene:
         if not hasattr(src, "shape"):
             src = np.asarray(src, dtype=np.float32)
         dim = len(src.shape)
+        # extension: several source fields on one set of walks -- a (C, H, W) / (C, X, Y, Z) source
+        # with C <= 4, told from a plain grid by the boundary mesh's own dimension; wost() then
+        # returns p, grad (and the variances) with a leading channel axis
+        if source is not None and dim in (3, 4) and _obj_dim(boundary) == dim - 1:
+            dim -= 1
         if dim not in (2, 3):
             raise ValueError(f"source must be a 2D (H,W) or 3D (X,Y,Z) grid, got shape {tuple(src.shape)}")
         self.dim = dim
@@ -168,7 +188,8 @@ def wost(scene, solverConfig, outputConfig, pts, return_numpy=False, return_vari
     tensors when pts is a CUDA tensor).  return_variance (extension, like return_numpy):
     (points, p, grad, p_var, grad_var) in the same container type -- the estimator's
     per-walk sample variances (getEstimatedSolutionVariance / getEstimatedGradientVariance,
-    walk_on_stars.h:811-831), masked like p and grad."""
+    walk_on_stars.h:811-831), masked like p and grad.  A scene built from a (C, ...) source
+    returns the same containers with a leading channel axis: p [C][N], grad [C][N][dim]."""
     _required(outputConfig, "gridRes")  # required even by the sampled path (demo.cpp:132)
     params = _engine.solver_params(solverConfig, outputConfig)
     kw = {"variance": True} if return_variance else {}
