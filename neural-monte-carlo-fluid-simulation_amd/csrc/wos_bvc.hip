@@ -8,7 +8,8 @@
 //                              (walk_on_stars.h:400-419, the star radius from the
 //                              sample itself, wave-cooperative) and its walk tasks;
 //   wos_walk_kernel<2,GG,true> the walks of estimateSolution (walk_on_stars.h:422-463)
-//                              on the solve's persistent walk kernel;
+//                              on the solve's persistent walk kernel (launch_walks with
+//                              a boundary-start KernelVariant);
 //   wos_bvc_fold_kernel        the Welford mean of each sample's recorded walks;
 //   wos_bvc_splat_kernel       Splatter::splat (splatter.h:43-247): every evaluation
 //                              point (one lane) folds the cached samples in order,
@@ -19,6 +20,7 @@
 #include "wos_bvc.h"
 #include "wos_device.h"
 #include "wos_launch.h"
+#include "wos_select.h"
 
 namespace wos {
 
@@ -400,10 +402,15 @@ __global__ __launch_bounds__(kSplatPts * kSplatWaves) void wos_bvc_splat_kernel(
   else grad_out[2 * i + (wave - 1)] = v;
 }
 
-template __global__ void wos_walk_kernel<2, false, true>(const DevScene, const DevParams, const DevTasks, int64_t,
-                                                           int64_t, unsigned long long*, unsigned int*, int);
-template __global__ void wos_walk_kernel<2, true, true>(const DevScene, const DevParams, const DevTasks, int64_t,
-                                                          int64_t, unsigned long long*, unsigned int*, int);
+// This unit's walk kernels (wos_select.h): the reference-semantics boundary-start walks,
+// run by launch_walks (wos_kernel.hip); the robust ones are wos_robust.hip's.
+#define UNIT_WALKS(X) X(2, false, true, false, true, false, 1) X(2, true, true, false, true, false, 1)
+UNIT_WALKS(WOS_WALK_INSTANTIATE)
+UnitKernels unit_kernels_bstart(const KernelVariant& v) {
+  UnitKernels k;
+  UNIT_WALKS(WOS_WALK_SELECT)
+  return k;
+}
 
 // ---- host launchers ----------------------------------------------------------
 void diag_dump_bstart(const char* tag) { diag_print(tag, HIP_SYMBOL(g_diag)); }
@@ -432,26 +439,6 @@ hipError_t launch_bvc_fd(const DevScene& sc, const float* pts, const float* sol,
   if (n <= 0) return hipSuccess;
   hipLaunchKernelGGL(wos_bvc_fd_kernel, dim3((int)((n + 255) / 256)), dim3(256), 0, s, sc, pts, sol, n, dn);
   return hipGetLastError();
-}
-
-hipError_t launch_walks_bstart(const DevScene& sc, const DevParams& prm, const DevTasks& tk, int64_t base,
-                               int64_t stride, unsigned long long* counters, unsigned int* tqueue, int grid,
-                               size_t shmem, int geom_floats, hipStream_t s) {
-  if (prm.robust)
-    return launch_walks_rb(2, true, sc, prm, tk, base, stride, counters, tqueue, grid, shmem, geom_floats, s);
-  if (sc.geom_global)
-    hipLaunchKernelGGL((wos_walk_kernel<2, true, true>), dim3(grid), dim3(kBlock), shmem, s, sc, prm, tk, base, stride,
-                       counters, tqueue, geom_floats);
-  else
-    hipLaunchKernelGGL((wos_walk_kernel<2, false, true>), dim3(grid), dim3(kBlock), shmem, s, sc, prm, tk, base,
-                       stride, counters, tqueue, geom_floats);
-  return hipGetLastError();
-}
-
-hipError_t occupancy_walk_bstart(bool geom_global, size_t shmem, int* blocks, bool robust) {
-  if (robust) return occupancy_rb(2, 2, geom_global, shmem, blocks);
-  return geom_global ? hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, wos_walk_kernel<2, true, true>, kBlock, shmem)
-                     : hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, wos_walk_kernel<2, false, true>, kBlock, shmem);
 }
 
 hipError_t launch_bvc_fold(const DevTasks& tk, int64_t nb, float* sol, int32_t* nest, hipStream_t s) {

@@ -1202,19 +1202,21 @@ int solve_locked(wos_scene* s, const wos_solver_params* prm, const float* pts, i
 #ifdef WOS_ACCT_NOSPREAD
   dp.tail_spread = 0;  // HBM-accounting build: the walk kernel without tail spreading (no scratch)
 #endif
+  // the first-ball and walk instantiations of this solve: launched and sized through the same key
+  const wos::KernelVariant kv = wos::kernel_variant(dim, dsc, dp, false);
   const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(n, g_max_batch_tasks.load() / wpp));
   const int64_t n_chunks = n > 0 ? (n + chunk - 1) / chunk : 0;
   int grid_fb = 0, grid_walk = 0, bpc_fb = 0, bpc_walk = 0;
   if (n > 0) {
     int rc = ensure_tasks(c, dim, chunk * wpp, chunk, C);
     if (rc != WOS_OK) return rc;
-    HIP_TRY(wos::occupancy_blocks_per_cu(0, dim, false, shmem_fb, &bpc_fb, dp.robust != 0, C > 1));
+    HIP_TRY(wos::occupancy_blocks_per_cu(kv, 0, shmem_fb, &bpc_fb));
     // the stratified samples' jump constants in LDS, unless they cost the first-ball kernel a block per CU
     const int jn = std::min(2 * (2 * dp.n_pairs) * (dim - 1), wos::kLhsJumpMax);
     const size_t shmem_j = shmem_fb + (size_t)jn * 2 * sizeof(uint64_t);
     int bpc_j = 0;
     if (jn > 0 && shmem_j <= kLdsDynamicMax)
-      HIP_TRY(wos::occupancy_blocks_per_cu(0, dim, false, shmem_j, &bpc_j, dp.robust != 0, C > 1));
+      HIP_TRY(wos::occupancy_blocks_per_cu(kv, 0, shmem_j, &bpc_j));
     if (WOS_LHS_JUMP_STAGE && jn > 0 && bpc_j >= bpc_fb) {
       dp.lhs_jump_n = jn;
       shmem_fb_run = shmem_j;
@@ -1222,8 +1224,8 @@ int solve_locked(wos_scene* s, const wos_solver_params* prm, const float* pts, i
     const int64_t fb_waves = (chunk + wos::first_ball_points_per_wave(dp.n_pairs) - 1) / wos::first_ball_points_per_wave(dp.n_pairs);
     grid_fb = (int)std::min<int64_t>((fb_waves + wos::kWavesPerBlockHost - 1) / wos::kWavesPerBlockHost,
                                      (int64_t)std::max(1, bpc_fb) * std::max(1, c.num_cus));
-    // the walk instantiation launch_walks will dispatch (tail spreading has its own LDS and state)
-    HIP_TRY(wos::occupancy_walk_blocks_per_cu(dim, dsc.geom_global != 0, dp, shmem_walk, &bpc_walk, C > 1));
+    // of the walk instantiation launch_walks runs for kv (tail spreading has its own LDS and state)
+    HIP_TRY(wos::occupancy_blocks_per_cu(kv, 1, shmem_walk, &bpc_walk));
     grid_walk = std::max(1, bpc_walk) * std::max(1, c.num_cus);
   }
   const uint64_t ticket = c.next_ticket++;
@@ -1263,10 +1265,10 @@ int solve_locked(wos_scene* s, const wos_solver_params* prm, const float* pts, i
     HIP_TRY(hipEventRecord(ev[0], st));
     HIP_TRY(wos::launch_point_setup(dim, dfb, dp, d_pts + b0 * dim, nb, tk, st));
     HIP_TRY(wos::launch_lpt_order(tk, nb, st));
-    HIP_TRY(wos::launch_first_balls(dim, dfb, dp, d_pts + b0 * dim, nb, bbase, index_stride, tk, c.d_counters,
+    HIP_TRY(wos::launch_first_balls(kv, dfb, dp, d_pts + b0 * dim, nb, bbase, index_stride, tk, c.d_counters,
                                     q_points, grid_fb, shmem_fb_run, lhs_floats, st));
     HIP_TRY(hipEventRecord(ev[1], st));
-    HIP_TRY(wos::launch_walks(dim, dsc, dp, tk, bbase, index_stride, c.d_counters, q_tasks, walk_grid,
+    HIP_TRY(wos::launch_walks(kv, dsc, dp, tk, bbase, index_stride, c.d_counters, q_tasks, walk_grid,
                               shmem_walk, geom_floats_walk, st));
     HIP_TRY(hipEventRecord(ev[2], st));
     // one fold per channel: only total and first differ, code / bdir / sdir are the walks'
@@ -1677,11 +1679,12 @@ int wos_bvc(wos_scene* s, const wos_solver_params* prm, const wos_bvc_params* bp
     first_walk[k] = false;
     HIP_TRY(wos::launch_bvc_start(dsc, dp, pts_d, nrm_d, al_d, dd_d, np_, tk, on_neumann, tag, w.stream));
     int bpc = 0;
-    HIP_TRY(wos::occupancy_walk_bstart(dsc.geom_global != 0, wl.shmem_walk, &bpc, dp.robust != 0));
+    const wos::KernelVariant kv = wos::kernel_variant(2, dsc, dp, true);
+    HIP_TRY(wos::occupancy_blocks_per_cu(kv, 1, wl.shmem_walk, &bpc));
     const int grid = (int)std::min<int64_t>((int64_t)std::max(1, bpc) * std::max(1, c.num_cus), (tk.T + 63) / 64);
     unsigned int* q_tasks = (unsigned int*)(w.counters + wos::kTaskQueueSlot0);
-    HIP_TRY(wos::launch_walks_bstart(dsc, dp, tk, base, 1, w.counters, q_tasks, grid, wl.shmem_walk,
-                                     wl.geom_floats_walk, w.stream));
+    HIP_TRY(wos::launch_walks(kv, dsc, dp, tk, base, 1, w.counters, q_tasks, grid, wl.shmem_walk,
+                              wl.geom_floats_walk, w.stream));
     HIP_TRY(wos::launch_bvc_fold(tk, np_, sol_d, nest_d, w.stream));
     q.bpc_walk = bpc;
     return WOS_OK;

@@ -4,9 +4,16 @@
 // One projection = wos_point_setup_kernel, the walk-queue order (wos_lpt_scatter_kernel),
 // wos_first_ball_kernel, the persistent wos_walk_kernel and wos_fold_kernel (statistics
 // + masked outputs), all on the caller's stream.
+//
+// The first-ball and walk kernels are instantiated in five translation units (this one:
+// one channel, reference float semantics; wos_channels.hip, wos_robust.hip,
+// wos_channels_rb.hip, wos_bvc.hip).  Which one a solve runs is a KernelVariant
+// (wos_variant.h); launch_first_balls, launch_walks and occupancy_blocks_per_cu here ask
+// the units for its kernel (wos_select.h) and launch or query through that pointer.
 #include "wos_device.h"
 #include <algorithm>
 #include "wos_launch.h"
+#include "wos_select.h"
 
 namespace wos {
 
@@ -40,33 +47,33 @@ __global__ __launch_bounds__(256) void wos_lpt_scatter_kernel(const DevTasks tk,
   if (i < n) tk.perm[base[b] + local] = (uint32_t)i;
 }
 
-template __global__ void wos_first_ball_kernel<2>(const DevScene, const DevParams, const float*, int64_t, int64_t,
-                                                   int64_t, const DevTasks, unsigned long long*, unsigned int*, int);
-template __global__ void wos_first_ball_kernel<3>(const DevScene, const DevParams, const float*, int64_t, int64_t,
-                                                   int64_t, const DevTasks, unsigned long long*, unsigned int*, int);
+// This unit's first-ball and walk kernels (wos_select.h): one channel, reference float
+// semantics.  Walks <DIM, GG> with the Neumann term and Neumann-inert; 2D with LDS geometry
+// also tail-spreading (DevParams::tail_spread).
+#define UNIT_FIRST_BALLS(X) X(2, false, 1) X(3, false, 1)
+#define UNIT_WALKS(X)                         \
+  X(2, false, false, false, true, false, 1)   \
+  X(2, false, false, false, false, false, 1)  \
+  X(2, true, false, false, true, false, 1)    \
+  X(2, true, false, false, false, false, 1)   \
+  X(2, false, false, false, true, true, 1)    \
+  X(2, false, false, false, false, true, 1)   \
+  X(3, false, false, false, true, false, 1)   \
+  X(3, false, false, false, false, false, 1)  \
+  X(3, true, false, false, true, false, 1)    \
+  X(3, true, false, false, false, false, 1)
+UNIT_FIRST_BALLS(WOS_FIRST_BALL_INSTANTIATE)
 template __global__ void wos_point_setup_kernel<2>(const DevScene, const DevParams, const float*, int64_t,
                                                    const DevTasks);
 template __global__ void wos_point_setup_kernel<3>(const DevScene, const DevParams, const float*, int64_t,
                                                    const DevTasks);
-// walk kernels: <DIM, GG> with the Neumann term, and the Neumann-inert <DIM, GG, false, false, false>
-#define WOS_WALK(D, G)                                                                                            \
-  template __global__ void wos_walk_kernel<D, G>(const DevScene, const DevParams, const DevTasks, int64_t, int64_t, \
-                                                 unsigned long long*, unsigned int*, int);                        \
-  template __global__ void wos_walk_kernel<D, G, false, false, false>(const DevScene, const DevParams,            \
-                                                                      const DevTasks, int64_t, int64_t,           \
-                                                                      unsigned long long*, unsigned int*, int)
-WOS_WALK(2, false);
-WOS_WALK(2, true);
-// 2D, LDS geometry, the tail-spreading instantiations (DevParams::tail_spread)
-template __global__ void wos_walk_kernel<2, false, false, false, true, true>(const DevScene, const DevParams,
-                                                                            const DevTasks, int64_t, int64_t,
-                                                                            unsigned long long*, unsigned int*, int);
-template __global__ void wos_walk_kernel<2, false, false, false, false, true>(const DevScene, const DevParams,
-                                                                             const DevTasks, int64_t, int64_t,
-                                                                             unsigned long long*, unsigned int*, int);
-WOS_WALK(3, false);
-WOS_WALK(3, true);
-#undef WOS_WALK
+UNIT_WALKS(WOS_WALK_INSTANTIATE)
+UnitKernels unit_kernels_plain(const KernelVariant& v) {
+  UnitKernels k;
+  UNIT_FIRST_BALLS(WOS_FIRST_BALL_SELECT)
+  UNIT_WALKS(WOS_WALK_SELECT)
+  return k;
+}
 template __global__ void wos_fold_kernel<2>(const DevParams, const DevTasks, int64_t, float*, float*, int32_t*,
                                             int32_t*);
 template __global__ void wos_fold_kernel<3>(const DevParams, const DevTasks, int64_t, float*, float*, int32_t*,
@@ -124,19 +131,26 @@ __global__ void wos_math_selftest_kernel(int which, const double* x, double* out
 // ---------------------------------------------------------------------------
 // host-side launchers (called from wos_capi.hip)
 // ---------------------------------------------------------------------------
-hipError_t launch_first_balls(int dim, const DevScene& sc, const DevParams& prm, const float* pts, int64_t n,
-                              int64_t base, int64_t stride, const DevTasks& tk, unsigned long long* counters,
-                              unsigned int* work, int grid, size_t shmem, int lhs_floats, hipStream_t s) {
-  if (prm.robust)
-    return launch_first_balls_rb(dim, sc, prm, pts, n, base, stride, tk, counters, work, grid, shmem, lhs_floats, s);
-  if (sc.n_channels > 1)
-    return launch_first_balls_mc(dim, sc, prm, pts, n, base, stride, tk, counters, work, grid, shmem, lhs_floats, s);
-  if (dim == 2)
-    hipLaunchKernelGGL(wos_first_ball_kernel<2>, dim3(grid), dim3(kBlock), shmem, s, sc, prm, pts, n, base, stride, tk,
-                       counters, work, lhs_floats);
-  else
-    hipLaunchKernelGGL(wos_first_ball_kernel<3>, dim3(grid), dim3(kBlock), shmem, s, sc, prm, pts, n, base, stride, tk,
-                       counters, work, lhs_floats);
+// the kernels of a variant: every unit is asked, the one that owns an instantiation answers
+static UnitKernels kernels_of(const KernelVariant& v) {
+  UnitKernels k;
+  for (UnitKernels (*unit)(const KernelVariant&) : {unit_kernels_plain, unit_kernels_channels, unit_kernels_robust,
+                                                    unit_kernels_channels_rb, unit_kernels_bstart}) {
+    const UnitKernels u = unit(v);
+    if (u.first_ball) k.first_ball = u.first_ball;
+    if (u.walk) k.walk = u.walk;
+  }
+  return k;
+}
+
+hipError_t launch_first_balls(const KernelVariant& v, const DevScene& sc, const DevParams& prm, const float* pts,
+                              int64_t n, int64_t base, int64_t stride, const DevTasks& tk,
+                              unsigned long long* counters, unsigned int* work, int grid, size_t shmem, int lhs_floats,
+                              hipStream_t s) {
+  const FirstBallKernel kernel = kernels_of(v).first_ball;
+  if (!kernel) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), shmem, s, sc, prm, pts, n, base, stride, tk, counters, work,
+                     lhs_floats);
   return hipGetLastError();
 }
 
@@ -168,39 +182,13 @@ hipError_t launch_lpt_order(const DevTasks& tk, int64_t n, hipStream_t s) {
   return hipGetLastError();
 }
 
-hipError_t launch_walks(int dim, const DevScene& sc, const DevParams& prm, const DevTasks& tk, int64_t base,
-                        int64_t stride, unsigned long long* counters, unsigned int* tqueue, int grid, size_t shmem,
-                        int geom_floats, hipStream_t s) {
-  if (prm.robust)
-    return launch_walks_rb(dim, false, sc, prm, tk, base, stride, counters, tqueue, grid, shmem, geom_floats, s);
-  if (sc.n_channels > 1)
-    return launch_walks_mc(dim, sc, prm, tk, base, stride, counters, tqueue, grid, shmem, geom_floats, s);
-#define WOS_LAUNCH_WALK(D, G)                                                                                    \
-  do {                                                                                                           \
-    if (prm.neumann_inert)                                                                                       \
-      hipLaunchKernelGGL((wos_walk_kernel<D, G, false, false, false>), dim3(grid), dim3(kBlock), shmem, s, sc, \
-                         prm, tk, base, stride, counters, tqueue, geom_floats);                                  \
-    else                                                                                                         \
-      hipLaunchKernelGGL((wos_walk_kernel<D, G>), dim3(grid), dim3(kBlock), shmem, s, sc, prm, tk, base, stride,  \
-                         counters, tqueue, geom_floats);                                                         \
-  } while (0)
-  if (dim == 2) {
-    if (sc.geom_global) {
-      WOS_LAUNCH_WALK(2, true);
-    } else if (prm.tail_spread) {
-      if (prm.neumann_inert)
-        hipLaunchKernelGGL((wos_walk_kernel<2, false, false, false, false, true>), dim3(grid), dim3(kBlock), shmem, s,
-                           sc, prm, tk, base, stride, counters, tqueue, geom_floats);
-      else
-        hipLaunchKernelGGL((wos_walk_kernel<2, false, false, false, true, true>), dim3(grid), dim3(kBlock), shmem, s,
-                           sc, prm, tk, base, stride, counters, tqueue, geom_floats);
-    } else {
-      WOS_LAUNCH_WALK(2, false);
-    }
-  } else {
-    if (sc.geom_global) WOS_LAUNCH_WALK(3, true); else WOS_LAUNCH_WALK(3, false);
-  }
-#undef WOS_LAUNCH_WALK
+hipError_t launch_walks(const KernelVariant& v, const DevScene& sc, const DevParams& prm, const DevTasks& tk,
+                        int64_t base, int64_t stride, unsigned long long* counters, unsigned int* tqueue, int grid,
+                        size_t shmem, int geom_floats, hipStream_t s) {
+  const WalkKernel kernel = kernels_of(v).walk;
+  if (!kernel) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), shmem, s, sc, prm, tk, base, stride, counters, tqueue,
+                     geom_floats);
   return hipGetLastError();
 }
 
@@ -243,38 +231,13 @@ int first_ball_points_per_wave(int n_pairs) { return fb_points_per_wave(n_pairs)
 
 size_t walk_wave_lds_bytes(int dim) { return dim == 2 ? walk_scratch_bytes<2>() : walk_scratch_bytes<3>(); }
 
-hipError_t occupancy_blocks_per_cu(int which, int dim, bool geom_global, size_t shmem, int* blocks, bool robust,
-                                   bool multi) {
-  if (robust) return occupancy_rb(which, dim, geom_global, shmem, blocks, multi);
-  if (multi && which == 0) return occupancy_first_ball_mc(dim, shmem, blocks);
-  if (which == 0)
-    return dim == 2 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, wos_first_ball_kernel<2>, kBlock, shmem)
-                    : hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, wos_first_ball_kernel<3>, kBlock, shmem);
-  if (dim == 2)
-    return geom_global ? hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, wos_walk_kernel<2, true>, kBlock, shmem)
-                       : hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, wos_walk_kernel<2, false>, kBlock, shmem);
-  return geom_global ? hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, wos_walk_kernel<3, true>, kBlock, shmem)
-                     : hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, wos_walk_kernel<3, false>, kBlock, shmem);
-}
-
-// residency of the walk instantiation launch_walks dispatches for these parameters (the
-// tail-spreading and Neumann-inert kernels differ in static LDS and registers)
-hipError_t occupancy_walk_blocks_per_cu(int dim, bool geom_global, const DevParams& prm, size_t shmem, int* blocks,
-                                        bool multi) {
-  if (prm.robust) return occupancy_rb(1, dim, geom_global, shmem, blocks, multi);
-  if (multi) return occupancy_walk_mc(dim, geom_global, prm, shmem, blocks);
-#define WOS_OCC(K) hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, K, kBlock, shmem)
-  const bool inert = prm.neumann_inert != 0;
-  if (dim == 2) {
-    if (geom_global) return inert ? WOS_OCC((wos_walk_kernel<2, true, false, false, false>)) : WOS_OCC((wos_walk_kernel<2, true>));
-    if (prm.tail_spread)
-      return inert ? WOS_OCC((wos_walk_kernel<2, false, false, false, false, true>))
-                   : WOS_OCC((wos_walk_kernel<2, false, false, false, true, true>));
-    return inert ? WOS_OCC((wos_walk_kernel<2, false, false, false, false>)) : WOS_OCC((wos_walk_kernel<2, false>));
-  }
-  if (geom_global) return inert ? WOS_OCC((wos_walk_kernel<3, true, false, false, false>)) : WOS_OCC((wos_walk_kernel<3, true>));
-  return inert ? WOS_OCC((wos_walk_kernel<3, false, false, false, false>)) : WOS_OCC((wos_walk_kernel<3, false>));
-#undef WOS_OCC
+// residency of the very kernel the launchers above run for v (the instantiations differ in
+// registers and static LDS)
+hipError_t occupancy_blocks_per_cu(const KernelVariant& v, int which, size_t shmem, int* blocks) {
+  const UnitKernels k = kernels_of(v);
+  const void* kernel = which == 0 ? (const void*)k.first_ball : which == 1 ? (const void*)k.walk : nullptr;
+  if (!kernel) return hipErrorInvalidValue;
+  return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, kernel, kBlock, shmem);
 }
 
 void diag_dump(const char* tag) {

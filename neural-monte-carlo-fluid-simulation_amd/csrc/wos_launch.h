@@ -1,7 +1,11 @@
-// wos_launch.h -- host entry points of the kernels in wos_kernel.hip.
+// wos_launch.h -- host entry points of the kernels (wos_kernel.hip, wos_channels.hip, wos_bvc.hip).
+// The first-ball and walk kernels have many instantiations over five translation units;
+// the caller names the one it means with a KernelVariant (wos_variant.h, kernel_variant()),
+// and launch_first_balls, launch_walks and occupancy_blocks_per_cu all resolve it the same way.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "wos_scene.h"
+#include "wos_variant.h"
 
 namespace wos {
 constexpr int kBlockThreads = 256;
@@ -14,9 +18,10 @@ constexpr int kNumCounterSlots = kTaskQueueSlot0 + kMaxTaskQueues * 8;
 constexpr int kMainCounterSlots = kNumCounterSlots;  // the main solve's counter buffer
 
 // the first balls of every estimated point (after launch_point_setup)
-hipError_t launch_first_balls(int dim, const DevScene& sc, const DevParams& prm, const float* pts, int64_t n,
-                              int64_t base, int64_t stride, const DevTasks& tk, unsigned long long* counters,
-                              unsigned int* work, int grid, size_t shmem, int lhs_floats, hipStream_t s);
+hipError_t launch_first_balls(const KernelVariant& v, const DevScene& sc, const DevParams& prm, const float* pts,
+                              int64_t n, int64_t base, int64_t stride, const DevTasks& tk,
+                              unsigned long long* counters, unsigned int* work, int grid, size_t shmem, int lhs_floats,
+                              hipStream_t s);
 // per-point setup: pstate + first-ball radius + bucket histogram, before launch_lpt_order
 hipError_t launch_point_setup(int dim, const DevScene& sc, const DevParams& prm, const float* pts, int64_t n,
                               const DevTasks& tk, hipStream_t s);
@@ -24,9 +29,10 @@ hipError_t launch_point_setup(int dim, const DevScene& sc, const DevParams& prm,
 hipError_t launch_zero(unsigned long long* a, int n64, uint32_t* b, int n32, hipStream_t s);
 // bucket offsets + point permutation for the walk queue
 hipError_t launch_lpt_order(const DevTasks& tk, int64_t n, hipStream_t s);
-hipError_t launch_walks(int dim, const DevScene& sc, const DevParams& prm, const DevTasks& tk, int64_t base,
-                        int64_t stride, unsigned long long* counters, unsigned int* tqueue, int grid, size_t shmem,
-                        int geom_floats, hipStream_t s);
+// the walks of a solve, or (v.bstart) the boundary-start walks of boundary value caching
+hipError_t launch_walks(const KernelVariant& v, const DevScene& sc, const DevParams& prm, const DevTasks& tk,
+                        int64_t base, int64_t stride, unsigned long long* counters, unsigned int* tqueue, int grid,
+                        size_t shmem, int geom_floats, hipStream_t s);
 // p_var / g_var (either may be null): the per-point variances, quad fold only (tk.deriv == nullptr)
 hipError_t launch_fold(int dim, const DevParams& prm, const DevTasks& tk, int64_t n, float* p, float* g,
                        int32_t* nest, int32_t* steps, float* p_var, float* g_var, hipStream_t s);
@@ -35,13 +41,8 @@ size_t first_ball_wave_lds_bytes(int lhs_floats, int n_pairs);
 int first_ball_points_per_wave(int n_pairs);
 // per-wave LDS scratch of the walk kernel (after the staged geometry, 16-B aligned)
 size_t walk_wave_lds_bytes(int dim);
-// which: 0 first-ball kernel, 1 walk kernel (the instantiation for LDS-staged or global geometry);
-// robust: the robust-float instantiations (wos_robust.hip)
-// multi: the instantiations of a scene with several source channels (DevScene::n_channels > 1)
-hipError_t occupancy_blocks_per_cu(int which, int dim, bool geom_global, size_t shmem, int* blocks,
-                                   bool robust = false, bool multi = false);
-hipError_t occupancy_walk_blocks_per_cu(int dim, bool geom_global, const DevParams& prm, size_t shmem, int* blocks,
-                                        bool multi = false);
+// resident blocks per CU of the kernel launch_first_balls (which 0) / launch_walks (which 1) runs for v
+hipError_t occupancy_blocks_per_cu(const KernelVariant& v, int which, size_t shmem, int* blocks);
 void diag_dump(const char* tag);  // WOS_DIAG builds: print + reset the walk-kernel diagnostics
 void diag_dump_bstart(const char* tag);  // ... of the boundary-start walk kernels (wos_bvc.hip)
 void diag_print(const char* tag, const void* sym);
@@ -54,10 +55,6 @@ hipError_t launch_bvc_start(const DevScene& sc, const DevParams& prm, const floa
                             const uint8_t* aligned, const float* bdd, int64_t nb, const DevTasks& tk, int on_neumann,
                             uint32_t tag, hipStream_t s);
 hipError_t launch_bvc_fd(const DevScene& sc, const float* pts, const float* sol, int64_t n, float* dn, hipStream_t s);
-hipError_t launch_walks_bstart(const DevScene& sc, const DevParams& prm, const DevTasks& tk, int64_t base,
-                               int64_t stride, unsigned long long* counters, unsigned int* tqueue, int grid,
-                               size_t shmem, int geom_floats, hipStream_t s);
-hipError_t occupancy_walk_bstart(bool geom_global, size_t shmem, int* blocks, bool robust = false);
 hipError_t launch_bvc_fold(const DevTasks& tk, int64_t nb, float* sol, int32_t* nest, hipStream_t s);
 hipError_t launch_bvc_splat_list(const float* edd, const float* end_, const int32_t* ein, int64_t ne, float cutoff,
                                  float mask, int double_sided, uint32_t* list, uint32_t* count, hipStream_t s);
@@ -66,34 +63,6 @@ hipError_t launch_bvc_splat(const float* recs, int r0, int r1, int first, int la
                             float absorption, float radius_clamp, float reg, float* sol, float* grad, hipStream_t s);
 hipError_t launch_bvc_fill(float* recs, int64_t b0, int64_t b1, const float* bsol, const float* bdn,
                            const DevScene& sc, int ignore_neumann, hipStream_t s);
-// robust float semantics (wos_robust.hip): the same launches with Gfn<DIM, true>;
-// the launchers above dispatch here when prm.robust is set
-hipError_t launch_first_balls_rb(int dim, const DevScene& sc, const DevParams& prm, const float* pts, int64_t n,
-                                 int64_t base, int64_t stride, const DevTasks& tk, unsigned long long* counters,
-                                 unsigned int* work, int grid, size_t shmem, int lhs_floats, hipStream_t s);
-hipError_t launch_walks_rb(int dim, bool bstart, const DevScene& sc, const DevParams& prm, const DevTasks& tk,
-                           int64_t base, int64_t stride, unsigned long long* counters, unsigned int* tqueue, int grid,
-                           size_t shmem, int geom_floats, hipStream_t s);
-// which: 0 first-ball, 1 walk, 2 boundary-start walk
-hipError_t occupancy_rb(int which, int dim, bool geom_global, size_t shmem, int* blocks, bool multi = false);
-// several source channels on one set of walks (wos_channels.hip): the first-ball and walk
-// instantiations with kMaxChannels channels; the launchers above dispatch here when
-// sc.n_channels > 1 (robust float semantics: wos_channels_rb.hip, reached through wos_robust.hip's launchers)
-hipError_t launch_first_balls_mc(int dim, const DevScene& sc, const DevParams& prm, const float* pts, int64_t n,
-                                 int64_t base, int64_t stride, const DevTasks& tk, unsigned long long* counters,
-                                 unsigned int* work, int grid, size_t shmem, int lhs_floats, hipStream_t s);
-hipError_t launch_walks_mc(int dim, const DevScene& sc, const DevParams& prm, const DevTasks& tk, int64_t base,
-                           int64_t stride, unsigned long long* counters, unsigned int* tqueue, int grid, size_t shmem,
-                           int geom_floats, hipStream_t s);
-hipError_t occupancy_first_ball_mc(int dim, size_t shmem, int* blocks);
-hipError_t occupancy_walk_mc(int dim, bool geom_global, const DevParams& prm, size_t shmem, int* blocks);
-hipError_t launch_first_balls_rb_mc(int dim, const DevScene& sc, const DevParams& prm, const float* pts, int64_t n,
-                                    int64_t base, int64_t stride, const DevTasks& tk, unsigned long long* counters,
-                                    unsigned int* work, int grid, size_t shmem, int lhs_floats, hipStream_t s);
-hipError_t launch_walks_rb_mc(int dim, const DevScene& sc, const DevParams& prm, const DevTasks& tk, int64_t base,
-                              int64_t stride, unsigned long long* counters, unsigned int* tqueue, int grid,
-                              size_t shmem, int geom_floats, hipStream_t s);
-hipError_t occupancy_rb_mc(int which, int dim, bool geom_global, size_t shmem, int* blocks);  // which: 0, 1
 // planar [channels][cells] -> texels [cells][kMaxChannels] (channels beyond `channels`: +0)
 hipError_t launch_source_pack(const float* planar, float* texels, int64_t cells, int channels, hipStream_t s);
 }  // namespace wos

@@ -8,6 +8,24 @@
 #include <vector>
 
 #include "wos_host_scene.h"
+#include "wos_variant.h"
+
+// ---- the first-ball / walk kernel choice (csrc/wos_variant.h), tests/test_kernel_variants.py ----
+// out: dim, geom_global, bstart, robust, neumann, spread, channels, valid
+extern "C" void hs_kernel_variant(int dim, int robust, int n_channels, int geom_global, int neumann_inert,
+                                  int tail_spread, int bstart, int* out) {
+  wos::DevScene sc = {};
+  wos::DevParams prm = {};
+  sc.dim = dim;
+  sc.n_channels = n_channels;
+  sc.geom_global = geom_global;
+  prm.robust = robust;
+  prm.neumann_inert = neumann_inert;
+  prm.tail_spread = tail_spread;
+  const wos::KernelVariant v = wos::kernel_variant(dim, sc, prm, bstart != 0);
+  const int r[8] = {v.dim, v.geom_global, v.bstart, v.robust, v.neumann, v.spread, v.channels, v.valid};
+  std::copy(r, r + 8, out);
+}
 
 extern "C" int hs_prepare(int dim, const float* v, int nv, const int* ix, int np, int double_sided, float* prim,
                           int prim_cap, float* sil, int sil_cap, float* pg, int pg_cap, float* sg, int sg_cap,
