@@ -315,6 +315,40 @@ int wos_solve_stats(wos_scene *scene, uint64_t ticket, wos_stats *stats);
  * float pair of the rejection fast path. */
 int wos_selftest_math(int32_t which, const double *x, double *out, int64_t n, int32_t device);
 
+/* Device self-tests of the first-ball kernel's stratified sampler (generateStratifiedSamples,
+ * sampling.h:435-457), for the GPU-vs-oracle tests.  They run the kernel's own device
+ * functions on the LDS layout the kernel gives a wave.
+ *
+ * wos_selftest_lhs: the 2 n_pairs (dim - 1) stratified samples of each of the n point indices
+ * gidx (seed key `key`, the per-point stream of tag 0), out [n][2 n_pairs][dim - 1].  One wave
+ * builds the samples of plan[0] consecutive indices, as the kernel builds a pack of points.
+ * jump_lds = 1 stages the first min(draws, 512) jump constants in LDS as a solve does,
+ * 0 stages none (every draw reads the global table).
+ *
+ * wos_selftest_lhs_permute: runs one shuffle implementation on `count` caller-supplied tables.
+ * A table holds WOS_LHS_PACK_R1 ? 2 : 1 slots of values [nstrat][sd] and partners [sd][nstrat]
+ * (partner[i][j] in [j, nstrat)); `slots` of them are shuffled (the rest must come back as
+ * given), out like values.  An impl whose registers / scratch nstrat does not fit, sd outside
+ * 1..2 (the packed forms: 2) or a partner out of range is WOS_E_INVALID.
+ *
+ * wos_selftest_lhs_plan (host only, no device): what the kernels' constants select for
+ * n_pairs and dim -- out[0] points per wave, [1] 1 if one pass shuffles every slot and
+ * dimension (the packed forms), [2] the shuffle (WOS_LHS_*), [3] passes of the pair loop,
+ * [4] jump constants 0 all staged in LDS, 1 LDS then the global table, [5] LDS bytes per wave,
+ * [6] the dynamic LDS budget in bytes (a solve needs 4 x [5] <= [6]), [7] point packs per
+ * queue grab, [8] 64-stratum chunks of the register / LDS shuffle (0: serial); out holds 9. */
+#define WOS_LHS_REG1 0     /* lhs_permute_reg, one 64-lane chunk (nstrat <= 64) */
+#define WOS_LHS_REG2 1     /* lhs_permute_reg, two chunks (nstrat <= 128) */
+#define WOS_LHS_LDS 2      /* lhs_permute, pointer jumping in LDS (nstrat <= 256) */
+#define WOS_LHS_PACK_R1 3  /* lhs_permute_reg<2, 1, 4>: up to 2 slots x 2 dimensions at once */
+#define WOS_LHS_PACK_R2 4  /* lhs_permute_reg<2, 2, 2>: 1 slot x 2 dimensions at once */
+#define WOS_LHS_SERIAL 5   /* lane 0's loop (plan only) */
+int wos_selftest_lhs(uint64_t key, const int64_t *gidx, int64_t n, int32_t n_pairs, int32_t dim,
+                     int32_t jump_lds, float *out, int32_t device);
+int wos_selftest_lhs_permute(int32_t impl, const int32_t *partner, const float *values, int32_t nstrat,
+                             int32_t sd, int32_t slots, int32_t count, float *out, int32_t device);
+int wos_selftest_lhs_plan(int32_t n_pairs, int32_t dim, int32_t *out);
+
 const char *wos_last_error(void);
 int32_t wos_abi_version(void);
 int32_t wos_device_count(void);

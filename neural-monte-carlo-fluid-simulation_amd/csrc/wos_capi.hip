@@ -1817,4 +1817,98 @@ int wos_selftest_math(int32_t which, const double* x, double* out, int64_t n, in
   return WOS_OK;
 }
 
+int wos_selftest_lhs(uint64_t key, const int64_t* gidx, int64_t n, int32_t n_pairs, int32_t dim, int32_t jump_lds,
+                     float* out, int32_t device) {
+  if (!gidx || !out || n < 0 || n > (1 << 20) || n_pairs < 1 || n_pairs > (1 << 14) || (dim != 2 && dim != 3))
+    return fail(WOS_E_INVALID, "wos_selftest_lhs: bad argument");
+  if (n == 0) return WOS_OK;
+  // diagonal draws + shuffle draws, a table of exactly that many jump constants
+  const int draws = 2 * (2 * n_pairs) * (dim - 1);
+  const int jn = jump_lds ? std::min(draws, wos::kLhsJumpMax) : 0;
+  // (the probe launches without raising the kernel's dynamic LDS limit)
+  if (wos::lhs_selftest_lds_bytes(n_pairs, dim, jn) > 64 * 1024)
+    return fail(WOS_E_CAPACITY, "wos_selftest_lhs: n_pairs exceed the probe's LDS");
+  std::vector<uint64_t> t(2 * (size_t)draws);
+  uint64_t A = 1u, Cc = 0u;
+  for (int k = 0; k < draws; k++) {
+    t[2 * k] = A; t[2 * k + 1] = Cc;
+    A = A * wos::kPcgMult;
+    Cc = Cc * wos::kPcgMult + wos::kPcgInc;
+  }
+  const size_t nout = (size_t)n * 2 * n_pairs * (dim - 1);
+  HIP_TRY(hipSetDevice(device));
+  uint64_t* dj = nullptr;
+  long long* di = nullptr;
+  float* dout = nullptr;
+  hipError_t e = hipMalloc((void**)&dj, t.size() * sizeof(uint64_t));
+  if (e == hipSuccess) e = hipMalloc((void**)&di, n * sizeof(long long));
+  if (e == hipSuccess) e = hipMalloc((void**)&dout, nout * sizeof(float));
+  if (e == hipSuccess) e = hipMemcpy(dj, t.data(), t.size() * sizeof(uint64_t), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(di, gidx, n * sizeof(long long), hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    wos::DevParams dp{};
+    dp.n_pairs = n_pairs;
+    dp.n_walks = 2 * n_pairs;
+    dp.n_anti = 2;
+    dp.seed = key;
+    dp.jump = dj;
+    dp.n_jump = draws;
+    dp.lhs_jump_n = jn;
+    e = wos::launch_lhs_selftest(dim, dp, di, (int)n, dout, nullptr);
+  }
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = hipMemcpy(out, dout, nout * sizeof(float), hipMemcpyDeviceToHost);
+  hipFree(dj);
+  hipFree(di);
+  hipFree(dout);
+  if (e != hipSuccess) return fail(WOS_E_DEVICE, std::string("wos_selftest_lhs: ") + hipGetErrorString(e));
+  return WOS_OK;
+}
+
+int wos_selftest_lhs_permute(int32_t impl, const int32_t* partner, const float* values, int32_t nstrat, int32_t sd,
+                             int32_t slots, int32_t count, float* out, int32_t device) {
+  const int max_strata = wos::lhs_permute_selftest_max_strata(impl), cap = wos::lhs_permute_selftest_slots(impl);
+  const bool packed = impl == WOS_LHS_PACK_R1 || impl == WOS_LHS_PACK_R2;
+  if (!partner || !values || !out || count < 0 || count > (1 << 16))
+    return fail(WOS_E_INVALID, "wos_selftest_lhs_permute: bad argument");
+  if (max_strata == 0) return fail(WOS_E_INVALID, "wos_selftest_lhs_permute: unknown impl");
+  if (nstrat < 1 || nstrat > max_strata)
+    return fail(WOS_E_INVALID, "wos_selftest_lhs_permute: nstrat does not fit impl " + std::to_string(impl) + " (at most " +
+                                   std::to_string(max_strata) + ")");
+  if (sd < 1 || sd > 2 || (packed && sd != 2) || slots < 1 || slots > cap)
+    return fail(WOS_E_INVALID, "wos_selftest_lhs_permute: sd or slots do not fit impl " + std::to_string(impl));
+  if (count == 0) return WOS_OK;
+  const size_t per = (size_t)cap * nstrat * sd, total = per * count;
+  // the swap partner of step j is one of j .. nstrat - 1 (every slot's table is loaded)
+  for (size_t k = 0; k < total; k++) {
+    const int j = (int)(k % nstrat);
+    if (partner[k] < j || partner[k] >= nstrat)
+      return fail(WOS_E_INVALID, "wos_selftest_lhs_permute: partner out of range at " + std::to_string(k));
+  }
+  HIP_TRY(hipSetDevice(device));
+  int* dp = nullptr;
+  float *dv = nullptr, *dout = nullptr;
+  hipError_t e = hipMalloc((void**)&dp, total * sizeof(int));
+  if (e == hipSuccess) e = hipMalloc((void**)&dv, total * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc((void**)&dout, total * sizeof(float));
+  if (e == hipSuccess) e = hipMemcpy(dp, partner, total * sizeof(int), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(dv, values, total * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = wos::launch_lhs_permute_selftest(impl, dp, dv, nstrat, sd, slots, count, dout, nullptr);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = hipMemcpy(out, dout, total * sizeof(float), hipMemcpyDeviceToHost);
+  hipFree(dp);
+  hipFree(dv);
+  hipFree(dout);
+  if (e != hipSuccess) return fail(WOS_E_DEVICE, std::string("wos_selftest_lhs_permute: ") + hipGetErrorString(e));
+  return WOS_OK;
+}
+
+int wos_selftest_lhs_plan(int32_t n_pairs, int32_t dim, int32_t* out) {
+  if (!out || n_pairs < 1 || n_pairs > (1 << 20) || (dim != 2 && dim != 3))
+    return fail(WOS_E_INVALID, "wos_selftest_lhs_plan: bad argument");
+  wos::lhs_plan(n_pairs, dim, out);
+  out[6] = (int32_t)kLdsDynamicMax;
+  return WOS_OK;
+}
+
 }  // extern "C"

@@ -48,6 +48,17 @@ void diag_dump_bstart(const char* tag);  // ... of the boundary-start walk kerne
 void diag_print(const char* tag, const void* sym);
 hipError_t launch_math_selftest(int which, const double* x, double* out, int64_t n, hipStream_t s);
 
+// probes of the stratified sampler (wos_selftest.hip; include/wos.h wos_selftest_lhs*)
+// n indices' samples, out [n][2 n_pairs (dim - 1)]; prm: n_pairs, seed, jump, n_jump, lhs_jump_n
+hipError_t launch_lhs_selftest(int dim, const DevParams& prm, const long long* gidx, int n, float* out, hipStream_t s);
+size_t lhs_selftest_lds_bytes(int n_pairs, int dim, int jump_n);  // dynamic LDS of that launch
+// `count` tables of lhs_permute_selftest_slots(impl) slots each, shuffled by impl (WOS_LHS_*)
+hipError_t launch_lhs_permute_selftest(int impl, const int* partner, const float* values, int nstrat, int sd, int slots,
+                                       int count, float* out, hipStream_t s);
+int lhs_permute_selftest_slots(int impl);
+int lhs_permute_selftest_max_strata(int impl);  // 0: not a shuffle the probe runs
+void lhs_plan(int n_pairs, int dim, int32_t* out);  // wos_selftest_lhs_plan's out[0..8] but [6]
+
 // boundary value caching (wos_bvc.hip), 2D
 hipError_t launch_bvc_point_info(const DevScene& sc, const float* pts, int64_t n, float* dd, float* nd,
                                  int32_t* inside, float* src, hipStream_t s);

@@ -15,6 +15,8 @@ WOS_E_CAPACITY = -4
 WOS_PTRS_DEVICE = 0x1
 WOS_ASYNC = 0x2
 MAX_CHANNELS = 4  # include/wos.h WOS_MAX_CHANNELS
+# include/wos.h WOS_LHS_*: the stratified sampler's shuffles (wos_selftest_lhs_permute, wos_selftest_lhs_plan)
+LHS_REG1, LHS_REG2, LHS_LDS, LHS_PACK_R1, LHS_PACK_R2, LHS_SERIAL = range(6)
 
 
 class WosError(RuntimeError):
@@ -100,7 +102,7 @@ EXPORTS = (
     "wos_load_obj", "wos_mesh_free", "wos_scene_create", "wos_scene_destroy",
     "wos_scene_get_info", "wos_scene_set_source", "wos_release_caches", "wos_default_params", "wos_solve", "wos_solve_var",
     "wos_solve_stats", "wos_default_bvc_params", "wos_bvc",
-    "wos_selftest_math", "wos_last_error", "wos_abi_version", "wos_device_count", "wos_set_max_batch_tasks",
+    "wos_selftest_math", "wos_selftest_lhs", "wos_selftest_lhs_permute", "wos_selftest_lhs_plan", "wos_last_error", "wos_abi_version", "wos_device_count", "wos_set_max_batch_tasks",
     "wos_scene_set_source_channels", "wos_scene_channels", "wos_solve_channels",
 )
 
@@ -159,6 +161,14 @@ def load():
                           C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(Stats)]
     L.wos_selftest_math.restype = C.c_int
     L.wos_selftest_math.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]
+    L.wos_selftest_lhs.restype = C.c_int
+    L.wos_selftest_lhs.argtypes = [C.c_uint64, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                   C.c_int32]
+    L.wos_selftest_lhs_permute.restype = C.c_int
+    L.wos_selftest_lhs_permute.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                           C.c_int32, C.c_void_p, C.c_int32]
+    L.wos_selftest_lhs_plan.restype = C.c_int
+    L.wos_selftest_lhs_plan.argtypes = [C.c_int32, C.c_int32, C.c_void_p]
     L.wos_last_error.restype = C.c_char_p
     L.wos_last_error.argtypes = []
     L.wos_abi_version.restype = C.c_int32

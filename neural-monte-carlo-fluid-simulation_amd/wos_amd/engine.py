@@ -461,5 +461,50 @@ def selftest_math(which, x, device=0):
     return out
 
 
+def selftest_lhs(key, gidx, n_pairs, dim, jump_lds=True, device=0):
+    """The first-ball kernel's stratified samples of the point indices gidx, built by the
+    kernel's own device code (wos_selftest_lhs): float32 [n, 2 n_pairs, dim - 1]."""
+    gidx = np.ascontiguousarray(gidx, dtype=np.int64).reshape(-1)
+    out = np.empty((gidx.size, 2 * int(n_pairs), int(dim) - 1), np.float32)
+    check(_lib.load().wos_selftest_lhs(int(key), gidx.ctypes.data, gidx.size, int(n_pairs), int(dim),
+                                       int(bool(jump_lds)), out.ctypes.data, device), "wos_selftest_lhs")
+    return out
+
+
+def selftest_lhs_permute_slots(impl):
+    """Slots a table of wos_selftest_lhs_permute holds for shuffle implementation impl."""
+    return 2 if impl == _lib.LHS_PACK_R1 else 1
+
+
+def selftest_lhs_permute(impl, partner, values, slots=1, device=0):
+    """One shuffle implementation (_lib.LHS_*) of the stratified sampler on caller-supplied
+    tables (wos_selftest_lhs_permute).  partner: int32 [count, cap, sd, nstrat], values: float32
+    [count, cap, nstrat, sd] with cap = selftest_lhs_permute_slots(impl); the first `slots`
+    slots of every table are shuffled.  Returns the values after `for i: for j: swap(a[j, i],
+    a[partner[i][j], i])`, shaped like values."""
+    partner = np.ascontiguousarray(partner, dtype=np.int32)
+    values = np.ascontiguousarray(values, dtype=np.float32)
+    cap = selftest_lhs_permute_slots(impl)
+    if partner.ndim != 4 or values.ndim != 4 or partner.shape[1] != cap or \
+            values.shape != (partner.shape[0], cap, partner.shape[3], partner.shape[2]):
+        raise WosError(f"partner must be [count, {cap}, sd, nstrat] and values [count, {cap}, nstrat, sd]")
+    count, _, sd, nstrat = partner.shape
+    out = np.empty_like(values)
+    check(_lib.load().wos_selftest_lhs_permute(int(impl), partner.ctypes.data, values.ctypes.data, nstrat, sd,
+                                               int(slots), count, out.ctypes.data, device),
+          "wos_selftest_lhs_permute")
+    return out
+
+
+def selftest_lhs_plan(n_pairs, dim):
+    """What the kernels' constants select for the stratified samples of n_pairs pairs
+    (wos_selftest_lhs_plan; host only): a dict."""
+    out = np.zeros(9, np.int32)
+    check(_lib.load().wos_selftest_lhs_plan(int(n_pairs), int(dim), out.ctypes.data), "wos_selftest_lhs_plan")
+    keys = ("points_per_wave", "one_pass", "shuffle", "pair_passes", "jump_mixed", "wave_lds_bytes", "lds_budget",
+            "point_grab", "shuffle_chunks")
+    return {k: int(v) for k, v in zip(keys, out)}
+
+
 def device_count():
     return int(_lib.load().wos_device_count())

@@ -88,11 +88,11 @@ def _pair(cfg, oracle, dim=2):
     return osc, sc
 
 
-def _compare(oracle, osc, sc, cfg, pts, seed=0x5EED0001, schedule=0):
+def _compare(oracle, osc, sc, cfg, pts, seed=0x5EED0001, schedule=0, index_base=0, index_stride=1):
     prm_o = oracle.make_params(cfg["solver"], cfg["output"], seed=seed, math_mode=0)
-    p0, g0, ne0, st0, s0 = oracle.solve(osc, prm_o, pts)
+    p0, g0, ne0, st0, s0 = oracle.solve(osc, prm_o, pts, index_base=index_base, index_stride=index_stride)
     prm = solver_params(cfg["solver"], cfg["output"], seed=seed, schedule=schedule)
-    p1, g1, s1, ne1, st1 = sc.solve(pts, prm, counts=True)
+    p1, g1, s1, ne1, st1 = sc.solve(pts, prm, counts=True, index_base=index_base, index_stride=index_stride)
     np.testing.assert_array_equal(ne1, ne0)
     np.testing.assert_array_equal(st1, st0)
     assert_bits_equal(p1, p0)
