@@ -307,6 +307,51 @@ int wos_bvc(wos_scene *scene, const wos_solver_params *params, const wos_bvc_par
  * per device are held; older tickets return WOS_E_INVALID.  No reference analogue. */
 int wos_solve_stats(wos_scene *scene, uint64_t ticket, wos_stats *stats);
 
+/* ---- Walk tape: a solve's walks recorded once, replayed for every new source ----------
+ * A walk never looks at the source grid: radii, directions, source sample points, throughput,
+ * roulette and the recorded / dropped decision follow from geometry, lambda and the key alone.
+ * A tape keeps, for fixed (scene, params, pts, index_base, index_stride), everything about the
+ * walks but the source values: per walk the first ball's Green's function norm and source cell,
+ * one entry (cell, throughput, norm; 12 bytes) per step that samples inside the star, and the
+ * finish (code, throughput, Dirichlet term, Neumann total).  wos_tape_solve then redoes only the
+ * source products and sums for the scene's current source grid and runs the ordinary fold: bit
+ * for bit what wos_solve_channels (one channel: wos_solve_var) would return now for the recorded
+ * points, indices and parameters -- p, grad, p_var, grad_var, n_est and steps -- at the cost of
+ * streaming the tape.  The noise is frozen exactly as a fixed `seed` freezes it: re-record with a
+ * new key for fresh noise.  No reference analogue.
+ *
+ * wos_tape_record  blocking; pts host or WOS_PTRS_DEVICE (the only flag read).  Costs about two
+ *                  solves: a plain walk pass sizes every walk's slots, the recording pass fills
+ *                  them.  Batches follow wos_set_max_batch_tasks (one segment per batch; results
+ *                  do not depend on it).  max_bytes <= 0: no cap; a tape that would be larger
+ *                  returns WOS_E_CAPACITY and keeps nothing.  stats: the recorded walks' counters
+ *                  and the recording's device time.  robust_float = 1 and parameters wos_solve
+ *                  refuses are WOS_E_INVALID.  The scene may hold several channels: the tape does
+ *                  not depend on their count.
+ * wos_tape_solve   outputs, pointers, flags (WOS_ASYNC included), ticket and stream ordering as
+ *                  wos_solve_channels; n_channels must equal wos_scene_channels(scene).  Reads the
+ *                  scene's current source (ordered after a wos_scene_set_source* on another
+ *                  stream).  WOS_E_INVALID: another scene than the recorded one (by a process-unique
+ *                  serial, not the address), source dims other than the recorded ones (the tape
+ *                  stores cell indices), n_channels mismatch.  stats: the walk counters are the
+ *                  recorded ones; kernel_ms, walk_ms (the replay kernel) and fold_ms this call's.
+ * wos_tape_destroy frees the tape (valid after wos_release_caches and after the scene is gone:
+ *                  the tape shares the geometry and owns its device memory). */
+typedef struct wos_tape wos_tape;
+typedef struct wos_tape_info {
+    int32_t dim, n_walks, source_dims[3], device;
+    int64_t n_points, n_tasks, n_entries, max_entries_per_walk, bytes;
+    int32_t replay_chunk_entries;   /* entries the replay kernel stages per wave and pass */
+} wos_tape_info;
+int wos_tape_record(wos_scene *scene, const wos_solver_params *params, const float *pts, int64_t n,
+                    int64_t index_base, int64_t index_stride, int64_t max_bytes,
+                    wos_tape **out, wos_stats *stats, void *stream, uint32_t flags);
+int wos_tape_solve(wos_tape *tape, wos_scene *scene, int32_t n_channels,
+                   float *p, float *grad, float *p_var, float *grad_var,
+                   int32_t *n_est, int32_t *steps, wos_stats *stats, void *stream, uint32_t flags);
+int wos_tape_get_info(const wos_tape *tape, wos_tape_info *info);
+int wos_tape_destroy(wos_tape *tape);
+
 /* Device self-test of the deterministic math used by the kernel (for the
  * GPU-vs-oracle parity tests): which = 0 exp, 1 log, 2 sin, 3 cos, 4 atan,
  * 5 sqrt, 6 bessi0, 7 bessi1, 8 bessk0, 9 bessk1 (double); 10 expf, 11 logf,

@@ -357,11 +357,13 @@ int dir_grid(Geom& g, bool* ok) {
 static_assert(WOS_BATCH_LOG2 <= 30, "task indices carry a flag in bit 31 (wos_walk_kernel hand-out)");
 constexpr int64_t kDefaultBatchTasks = (int64_t)1 << WOS_BATCH_LOG2;
 std::atomic<int64_t> g_max_batch_tasks{kDefaultBatchTasks};  // wos_set_max_batch_tasks
+std::atomic<uint64_t> g_scene_serial{0};  // wos_scene::serial: what a walk tape knows its scene by
 
 }  // namespace
 
 struct wos_scene {
   int device = 0;
+  uint64_t serial = 0;  // process-unique, never reused (an address can be)
   std::shared_ptr<Geom> geom;
   wos::DevScene dev{};
   float* d_source = nullptr;
@@ -482,6 +484,7 @@ int wos_scene_create(const wos_scene_desc* d, int32_t device, wos_scene** out) {
   auto* s = new wos_scene();
   s->device = device;
   s->geom = geom;
+  s->serial = g_scene_serial.fetch_add(1) + 1;
   if (d->source) {
     hipError_t e = hipMalloc((void**)&s->d_source, nsrc * sizeof(float));
     if (e == hipSuccess)
@@ -1083,21 +1086,28 @@ int wos_solve(wos_scene* s, const wos_solver_params* prm, const float* pts, int6
 
 namespace {
 
-// wos_solve with the scene's and the device context's locks held
-int solve_locked(wos_scene* s, const wos_solver_params* prm, const float* pts, int64_t n, int64_t index_base,
-                 int64_t index_stride, float* p, float* grad, int32_t* n_est, int32_t* steps, wos_stats* stats,
-                 void* stream, uint32_t flags, const SolveExtra& ex) {
+// What a solve's kernels are launched with: decided from the scene and the parameters alone
+// (solve_plan), then sized for a batch of `chunk` points (solve_grids).  record: the walk
+// tape's recording kernels (wos_tape.hip) -- one channel, full Neumann term, no tail spreading.
+#ifndef WOS_LHS_JUMP_STAGE
+#define WOS_LHS_JUMP_STAGE 1
+#endif
+struct SolvePlan {
+  wos::DevParams dp{};
+  wos::DevScene dsc{}, dfb{};  // the scene as the walk / the first-ball kernel sees it
+  int geom_floats_walk = 0, lhs_floats = 0;
+  size_t shmem_walk = 0, shmem_fb = 0, shmem_fb_run = 0;
+  int64_t wpp = 0;
+  wos::KernelVariant kv{};
+  int grid_fb = 0, grid_walk = 0, bpc_fb = 0, bpc_walk = 0;
+};
+
+int solve_plan(DevCtx& c, wos_scene* s, const wos_solver_params* prm, const SolveExtra& ex, bool record, SolvePlan& P) {
   Geom& geom = *s->geom;
   const wos::HostScene& host = geom.host;
   const int dim = host.dim;
-  hipStream_t st = (hipStream_t)stream;
-  DevCtx& c = g_ctx[s->device];
-  {
-    int rc = ctx_ready(c, s->device);
-    if (rc != WOS_OK) return rc;
-  }
-
-  wos::DevParams dp = dev_params(prm);
+  wos::DevParams& dp = P.dp;
+  dp = dev_params(prm);
   dp.force_estimate = ex.force_estimate ? 1 : 0;
   dp.wave_prio = ex.wave_prio;
   {
@@ -1117,19 +1127,18 @@ int solve_locked(wos_scene* s, const wos_solver_params* prm, const float* pts, i
     int rc = walk_layout(s, prm, wl);
     if (rc != WOS_OK) return rc;
   }
-  wos::DevScene dsc = wl.dsc;
-  int geom_floats_walk = wl.geom_floats_walk;
-  size_t shmem_walk = wl.shmem_walk;
-  const int lhs_floats = ((2 * dp.n_pairs * (dim - 1)) + 3) & ~3;
+  wos::DevScene& dsc = P.dsc;
+  dsc = wl.dsc;
+  P.geom_floats_walk = wl.geom_floats_walk;
+  P.shmem_walk = wl.shmem_walk;
+  P.lhs_floats = ((2 * dp.n_pairs * (dim - 1)) + 3) & ~3;
   // the first-ball kernel stages no geometry (the point-setup kernel did the queries)
-  const size_t shmem_fb = wos::kWavesPerBlockHost * wos::first_ball_wave_lds_bytes(lhs_floats, dp.n_pairs);
-  size_t shmem_fb_run = shmem_fb;  // + the staged jump constants (dp.lhs_jump_n), decided below
-#ifndef WOS_LHS_JUMP_STAGE
-#define WOS_LHS_JUMP_STAGE 1
-#endif
+  P.shmem_fb = wos::kWavesPerBlockHost * wos::first_ball_wave_lds_bytes(P.lhs_floats, dp.n_pairs);
+  P.shmem_fb_run = P.shmem_fb;  // + the staged jump constants (dp.lhs_jump_n), decided in solve_grids
   // scenes beyond the LDS budget (or WOS_SCHED_GEOM_GLOBAL): geometry read from global
   // memory through L2, LDS for the per-wave scratch only
-  wos::DevScene dfb = s->dev;
+  wos::DevScene& dfb = P.dfb;
+  dfb = s->dev;
   // the first-ball kernel's walk-start Dirichlet distances read the cell grid too (global memory)
   dfb.dgrid = dsc.dgrid;
   dfb.dgrid_off_words = dsc.dgrid_off_words;
@@ -1139,18 +1148,105 @@ int solve_locked(wos_scene* s, const wos_solver_params* prm, const float* pts, i
     dfb.dgrid_inv[k] = dsc.dgrid_inv[k];
   }
   // (only the walk kernel stages geometry, so only its LDS decides)
-  if ((prm->schedule & WOS_SCHED_GEOM_GLOBAL) || shmem_walk > kLdsDynamicMax) {
+  if ((prm->schedule & WOS_SCHED_GEOM_GLOBAL) || P.shmem_walk > kLdsDynamicMax) {
     dfb.geom_global = 1;
     dsc.geom_global = 1;
-    geom_floats_walk = 0;
-    shmem_walk = wos::kWavesPerBlockHost * wos::walk_wave_lds_bytes(dim);
+    P.geom_floats_walk = 0;
+    P.shmem_walk = wos::kWavesPerBlockHost * wos::walk_wave_lds_bytes(dim);
   }
-  if (shmem_fb > kLdsDynamicMax)
+  if (P.shmem_fb > kLdsDynamicMax)
     return fail(WOS_E_CAPACITY, "wos_solve: nWalks exceed the LDS budget of the first-ball kernel (" +
-                                    std::to_string(shmem_fb) + " bytes of stratified samples per block)");
-  if (shmem_walk > kLdsDynamicMax)
+                                    std::to_string(P.shmem_fb) + " bytes of stratified samples per block)");
+  if (P.shmem_walk > kLdsDynamicMax)
     return fail(WOS_E_CAPACITY, "wos_solve: the walk kernel's per-wave scratch exceeds the LDS budget (" +
-                                    std::to_string(shmem_walk) + " bytes)");
+                                    std::to_string(P.shmem_walk) + " bytes)");
+
+  P.wpp = (int64_t)dp.n_pairs * dp.n_anti;
+  // The Neumann term (h == 0) is +0 at every step unless a ball's float members overflow
+  // (mu R > 85 is the kernels' gate).  In a watertight single-sided scene every estimated
+  // point and walk lies inside the boundary's bounding box, so R < its diagonal: below
+  // the gate the walk kernel runs without the term's code (bit-identical results;
+  // WOS_SCHED_FULL_NEUMANN keeps the full kernel).
+  {
+    double diag2 = 0.0;
+    for (int k = 0; k < 3; k++) diag2 += (double)host.ext[k] * host.ext[k];
+    const double mu_r = std::sqrt(std::max(0.0, (double)s->dev.absorption)) * std::sqrt(diag2) * 1.01;
+    // (image-valued h makes the term non-zero at every step: never inert)
+    dp.neumann_inert = (!dp.robust && s->dev.watertight && !s->dev.double_sided && mu_r < 80.0 && !s->dev.nimg &&
+                        !(prm->schedule & WOS_SCHED_FULL_NEUMANN)) ? 1 : 0;
+  }
+  // Walks handed to idle sibling waves once the queue is dry (the walk kernel's SPR
+  // instantiation): 2D scenes with LDS geometry (karman -4 %, its stride-8 shard -13 %,
+  // config C neutral); 3D pays more for the extra live state than its short tails return
+  // (profiles/r4zc_*, r4ze_*)
+  dp.tail_spread = (dim == 2 && !dp.robust && !dsc.geom_global && !(prm->schedule & WOS_SCHED_NO_TAIL_SPREAD)) ? 1 : 0;
+#ifdef WOS_ACCT_NOSPREAD
+  dp.tail_spread = 0;  // HBM-accounting build: the walk kernel without tail spreading (no scratch)
+#endif
+  if (record) {
+    dp.neumann_inert = 0;
+    dp.tail_spread = 0;
+    dsc.n_channels = 1;
+    dfb.n_channels = 1;
+  }
+  // the first-ball and walk instantiations of this solve: launched and sized through the same key
+  P.kv = wos::kernel_variant(dim, dsc, dp, false);
+  return WOS_OK;
+}
+
+// grids and residency for batches of `chunk` points (record: of the recording kernels)
+int solve_grids(DevCtx& c, int dim, int64_t chunk, bool record, SolvePlan& P) {
+  wos::DevParams& dp = P.dp;
+  const bool gg = P.dsc.geom_global != 0;
+  const auto occupancy = [&](int which, size_t shmem, int* blocks) {
+    return record ? wos::occupancy_rec_blocks_per_cu(dim, gg, which, shmem, blocks)
+                  : wos::occupancy_blocks_per_cu(P.kv, which, shmem, blocks);
+  };
+  HIP_TRY(occupancy(0, P.shmem_fb, &P.bpc_fb));
+  // the stratified samples' jump constants in LDS, unless they cost the first-ball kernel a block per CU
+  const int jn = std::min(2 * (2 * dp.n_pairs) * (dim - 1), wos::kLhsJumpMax);
+  const size_t shmem_j = P.shmem_fb + (size_t)jn * 2 * sizeof(uint64_t);
+  int bpc_j = 0;
+  if (jn > 0 && shmem_j <= kLdsDynamicMax) HIP_TRY(occupancy(0, shmem_j, &bpc_j));
+  if (WOS_LHS_JUMP_STAGE && jn > 0 && bpc_j >= P.bpc_fb) {
+    dp.lhs_jump_n = jn;
+    P.shmem_fb_run = shmem_j;
+  }
+  const int64_t fb_waves = (chunk + wos::first_ball_points_per_wave(dp.n_pairs) - 1) / wos::first_ball_points_per_wave(dp.n_pairs);
+  P.grid_fb = (int)std::min<int64_t>((fb_waves + wos::kWavesPerBlockHost - 1) / wos::kWavesPerBlockHost,
+                                     (int64_t)std::max(1, P.bpc_fb) * std::max(1, c.num_cus));
+  // of the walk instantiation launch_walks runs for kv (tail spreading has its own LDS and state)
+  HIP_TRY(occupancy(1, P.shmem_walk, &P.bpc_walk));
+  P.grid_walk = std::max(1, P.bpc_walk) * std::max(1, c.num_cus);
+  return WOS_OK;
+}
+
+// wos_solve with the scene's and the device context's locks held
+int solve_locked(wos_scene* s, const wos_solver_params* prm, const float* pts, int64_t n, int64_t index_base,
+                 int64_t index_stride, float* p, float* grad, int32_t* n_est, int32_t* steps, wos_stats* stats,
+                 void* stream, uint32_t flags, const SolveExtra& ex) {
+  Geom& geom = *s->geom;
+  const wos::HostScene& host = geom.host;
+  const int dim = host.dim;
+  hipStream_t st = (hipStream_t)stream;
+  DevCtx& c = g_ctx[s->device];
+  {
+    int rc = ctx_ready(c, s->device);
+    if (rc != WOS_OK) return rc;
+  }
+
+  // the kernels' parameters, scene views and LDS layout of this solve
+  SolvePlan plan;
+  {
+    int rc = solve_plan(c, s, prm, ex, false, plan);
+    if (rc != WOS_OK) return rc;
+  }
+  wos::DevParams& dp = plan.dp;
+  const wos::DevScene& dsc = plan.dsc;
+  const wos::DevScene& dfb = plan.dfb;
+  const int geom_floats_walk = plan.geom_floats_walk, lhs_floats = plan.lhs_floats;
+  const size_t shmem_walk = plan.shmem_walk;
+  const wos::KernelVariant kv = plan.kv;
 
   // the shared workspace may still be in use by a solve enqueued on another stream
   HIP_TRY(ctx_order(c, st));
@@ -1181,53 +1277,16 @@ int solve_locked(wos_scene* s, const wos_solver_params* prm, const float* pts, i
 
   // Points are solved in chunks whose walk tasks fit the task workspace.
   const int64_t wpp = (int64_t)dp.n_pairs * dp.n_anti;
-  // The Neumann term (h == 0) is +0 at every step unless a ball's float members overflow
-  // (mu R > 85 is the kernels' gate).  In a watertight single-sided scene every estimated
-  // point and walk lies inside the boundary's bounding box, so R < its diagonal: below
-  // the gate the walk kernel runs without the term's code (bit-identical results;
-  // WOS_SCHED_FULL_NEUMANN keeps the full kernel).
-  {
-    double diag2 = 0.0;
-    for (int k = 0; k < 3; k++) diag2 += (double)host.ext[k] * host.ext[k];
-    const double mu_r = std::sqrt(std::max(0.0, (double)s->dev.absorption)) * std::sqrt(diag2) * 1.01;
-    // (image-valued h makes the term non-zero at every step: never inert)
-    dp.neumann_inert = (!dp.robust && s->dev.watertight && !s->dev.double_sided && mu_r < 80.0 && !s->dev.nimg &&
-                        !(prm->schedule & WOS_SCHED_FULL_NEUMANN)) ? 1 : 0;
-  }
-  // Walks handed to idle sibling waves once the queue is dry (the walk kernel's SPR
-  // instantiation): 2D scenes with LDS geometry (karman -4 %, its stride-8 shard -13 %,
-  // config C neutral); 3D pays more for the extra live state than its short tails return
-  // (profiles/r4zc_*, r4ze_*)
-  dp.tail_spread = (dim == 2 && !dp.robust && !dsc.geom_global && !(prm->schedule & WOS_SCHED_NO_TAIL_SPREAD)) ? 1 : 0;
-#ifdef WOS_ACCT_NOSPREAD
-  dp.tail_spread = 0;  // HBM-accounting build: the walk kernel without tail spreading (no scratch)
-#endif
-  // the first-ball and walk instantiations of this solve: launched and sized through the same key
-  const wos::KernelVariant kv = wos::kernel_variant(dim, dsc, dp, false);
   const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(n, g_max_batch_tasks.load() / wpp));
   const int64_t n_chunks = n > 0 ? (n + chunk - 1) / chunk : 0;
-  int grid_fb = 0, grid_walk = 0, bpc_fb = 0, bpc_walk = 0;
   if (n > 0) {
     int rc = ensure_tasks(c, dim, chunk * wpp, chunk, C);
     if (rc != WOS_OK) return rc;
-    HIP_TRY(wos::occupancy_blocks_per_cu(kv, 0, shmem_fb, &bpc_fb));
-    // the stratified samples' jump constants in LDS, unless they cost the first-ball kernel a block per CU
-    const int jn = std::min(2 * (2 * dp.n_pairs) * (dim - 1), wos::kLhsJumpMax);
-    const size_t shmem_j = shmem_fb + (size_t)jn * 2 * sizeof(uint64_t);
-    int bpc_j = 0;
-    if (jn > 0 && shmem_j <= kLdsDynamicMax)
-      HIP_TRY(wos::occupancy_blocks_per_cu(kv, 0, shmem_j, &bpc_j));
-    if (WOS_LHS_JUMP_STAGE && jn > 0 && bpc_j >= bpc_fb) {
-      dp.lhs_jump_n = jn;
-      shmem_fb_run = shmem_j;
-    }
-    const int64_t fb_waves = (chunk + wos::first_ball_points_per_wave(dp.n_pairs) - 1) / wos::first_ball_points_per_wave(dp.n_pairs);
-    grid_fb = (int)std::min<int64_t>((fb_waves + wos::kWavesPerBlockHost - 1) / wos::kWavesPerBlockHost,
-                                     (int64_t)std::max(1, bpc_fb) * std::max(1, c.num_cus));
-    // of the walk instantiation launch_walks runs for kv (tail spreading has its own LDS and state)
-    HIP_TRY(wos::occupancy_blocks_per_cu(kv, 1, shmem_walk, &bpc_walk));
-    grid_walk = std::max(1, bpc_walk) * std::max(1, c.num_cus);
+    rc = solve_grids(c, dim, chunk, false, plan);
+    if (rc != WOS_OK) return rc;
   }
+  const int grid_fb = plan.grid_fb, grid_walk = plan.grid_walk, bpc_fb = plan.bpc_fb, bpc_walk = plan.bpc_walk;
+  const size_t shmem_fb_run = plan.shmem_fb_run;
   const uint64_t ticket = c.next_ticket++;
   StatSlot& q = c.slot[ticket % kStatSlots];
   while ((int64_t)q.bev.size() < 4 * n_chunks) {
@@ -1350,6 +1409,424 @@ int wos_solve_stats(wos_scene* s, uint64_t ticket, wos_stats* stats) {
   if (q.ticket != ticket) return unknown();
   HIP_TRY(hipEventSynchronize(q.done));
   return fill_stats(q, stats);
+}
+
+}  // extern "C"
+
+// ---- walk tape (include/wos.h; kernels in wos_tape.hip) ----------------------------------
+// One segment per batch of points.  Per task (T = points * walks per point), one allocation:
+//   float  bdir[dim][T] sdir[dim][T] gnorm[T] thr_end[T] term[T] tneu[T]
+//   u32    code[T] cell0[T] cnt[T] slot[T + 1]      i32 pstate[points]
+// = 8 (dim + 4) bytes per walk (2D 48, 3D 56), and per entry slot 12 bytes: cell, pThr, pNrm.
+struct TapeSeg {
+  int64_t nb = 0, T = 0;  // points, tasks
+  uint64_t slots = 0;
+  void* buf = nullptr;    // the per-task arrays
+  void* ebuf = nullptr;   // the entry slots
+  wos::DevTape tp{};
+  uint32_t* code = nullptr;
+  float* bdir = nullptr;
+  float* sdir = nullptr;
+  int32_t* pstate = nullptr;
+};
+
+struct wos_tape {
+  int device = 0;
+  std::shared_ptr<Geom> geom;  // kept alive: the tape outlives caches and, harmlessly, its scene
+  uint64_t scene_serial = 0;
+  int dim = 0;
+  int32_t sdims[3] = {0, 0, 0};
+  wos::DevParams dp{};         // what the fold reads, and ignore_source
+  int64_t n = 0, wpp = 0;
+  std::vector<TapeSeg> seg;
+  unsigned long long* d_cnt = nullptr;  // the recorded walks' counters (kNumCounters), copied into every replay's stats
+  uint32_t* d_flag = nullptr;           // DevTape::overflow
+  int64_t n_entries = 0, max_entries = 0, bytes = 0;
+  int32_t bpc_fb = 0, bpc_walk = 0, walk_lds = 0, star_grid = 0, geom_global = 0, dir_grid = 0;
+  ~wos_tape() {
+    hipSetDevice(device);
+    for (TapeSeg& g : seg) { hipFree(g.buf); hipFree(g.ebuf); }
+    hipFree(d_cnt);
+    hipFree(d_flag);
+  }
+};
+
+namespace {
+
+size_t tape_task_bytes(int dim, int64_t T, int64_t nb) {
+  return ((size_t)(2 * dim + 4) * T + (size_t)3 * T + (size_t)(T + 1) + (size_t)nb) * 4;
+}
+
+// the views into a segment's per-task allocation
+void tape_seg_views(TapeSeg& g, int dim, uint32_t* flag) {
+  const int64_t T = g.T;
+  float* f = (float*)g.buf;
+  g.bdir = f; f += dim * T;
+  g.sdir = f; f += dim * T;
+  g.tp.gnorm = f; f += T;
+  g.tp.thr_end = f; f += T;
+  g.tp.term = f; f += T;
+  g.tp.tneu = f; f += T;
+  uint32_t* u = (uint32_t*)f;
+  g.code = u; u += T;
+  g.tp.cell0 = u; u += T;
+  g.tp.cnt = u; u += T;
+  g.tp.slot = u; u += T + 1;
+  g.pstate = (int32_t*)u;
+  g.tp.overflow = flag;
+}
+
+}  // namespace
+
+extern "C" {
+
+int wos_tape_record(wos_scene* s, const wos_solver_params* prm, const float* pts, int64_t n, int64_t index_base,
+                    int64_t index_stride, int64_t max_bytes, wos_tape** out, wos_stats* stats, void* stream,
+                    uint32_t flags) {
+  if (!s || !prm || !out) return fail(WOS_E_INVALID, "wos_tape_record: null scene/params/out");
+  *out = nullptr;
+  if (n < 0) return fail(WOS_E_INVALID, "wos_tape_record: negative point count");
+  if (n > 0 && !pts) return fail(WOS_E_INVALID, "wos_tape_record: null point buffer");
+  if (n >= (int64_t)0xFFFFFFF0LL) return fail(WOS_E_INVALID, "wos_tape_record: too many points for one call");
+  if (prm->n_walks < 1) return fail(WOS_E_INVALID, "wos_tape_record: nWalks must be >= 1");
+  if (prm->max_walk_length < 0) return fail(WOS_E_INVALID, "wos_tape_record: maxWalkLength must be >= 0");
+  if (!(prm->epsilon_shell >= 0.0f) || !(prm->min_star_radius >= 0.0f) || !(prm->silhouette_precision >= 0.0f))
+    return fail(WOS_E_INVALID, "wos_tape_record: negative tolerance");
+  if (prm->robust_float)
+    return fail(WOS_E_INVALID, "wos_tape_record: robust_float walks are not recorded (reference float semantics only)");
+  std::lock_guard<std::mutex> lock(s->mu);
+  HIP_TRY(hipSetDevice(s->device));
+  DevCtx& c = g_ctx[s->device];
+  std::lock_guard<std::mutex> lk(c.mu);
+  {
+    int rc = ctx_ready(c, s->device);
+    if (rc != WOS_OK) return rc;
+  }
+  const int dim = s->geom->host.dim;
+  hipStream_t st = (hipStream_t)stream;
+  SolvePlan plan;
+  {
+    int rc = solve_plan(c, s, prm, SolveExtra{}, true, plan);
+    if (rc != WOS_OK) return rc;
+  }
+  wos::DevParams& dp = plan.dp;
+  HIP_TRY(ctx_order(c, st));
+  const float* d_pts = pts;
+  if (!(flags & WOS_PTRS_DEVICE) && n > 0) {
+    int rc = ensure_workspace(c, dim, (size_t)n);
+    if (rc != WOS_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(c.d_pts, pts, (size_t)n * dim * sizeof(float), hipMemcpyHostToDevice, st));
+    d_pts = c.d_pts;
+  }
+  const int64_t wpp = plan.wpp;
+  const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(n, g_max_batch_tasks.load() / wpp));
+  const int64_t n_chunks = n > 0 ? (n + chunk - 1) / chunk : 0;
+  DevBufs tmp;  // the recording pass's own counters and queues; the scan's block sums
+  unsigned long long* d_cnt2 = nullptr;
+  unsigned long long* d_bsum = nullptr;
+  if (n > 0) {
+    int rc = ensure_tasks(c, dim, chunk * wpp, chunk, 1);
+    if (rc != WOS_OK) return rc;
+    rc = solve_grids(c, dim, chunk, true, plan);
+    if (rc != WOS_OK) return rc;
+    HIP_TRY(tmp.get(&d_cnt2, (size_t)wos::kNumCounterSlots));
+    HIP_TRY(tmp.get(&d_bsum, (size_t)wos::tape_slot_blocks(chunk * wpp) + 1));
+  }
+
+  std::unique_ptr<wos_tape> tape(new wos_tape());
+  tape->device = s->device;
+  tape->geom = s->geom;
+  tape->scene_serial = s->serial;
+  tape->dim = dim;
+  for (int k = 0; k < 3; k++) tape->sdims[k] = s->dev.source ? s->dev.sdims[k] : 0;
+  tape->dp = dp;
+  tape->dp.jump = nullptr;
+  tape->dp.rej_tab = nullptr;
+  tape->n = n;
+  tape->wpp = wpp;
+  tape->bpc_fb = plan.bpc_fb;
+  tape->bpc_walk = plan.bpc_walk;
+  tape->walk_lds = (int32_t)plan.shmem_walk;
+  tape->star_grid = plan.dsc.sgrid != nullptr;
+  tape->geom_global = plan.dsc.geom_global;
+  tape->dir_grid = plan.dsc.dgrid != nullptr;
+  HIP_TRY(hipMalloc((void**)&tape->d_cnt, (wos::kNumCounters + 2) * sizeof(unsigned long long)));
+  HIP_TRY(hipMalloc((void**)&tape->d_flag, sizeof(uint32_t)));
+  HIP_TRY(hipMemsetAsync(tape->d_cnt, 0, (wos::kNumCounters + 2) * sizeof(unsigned long long), st));
+  HIP_TRY(hipMemsetAsync(tape->d_flag, 0, sizeof(uint32_t), st));
+  tape->bytes = (int64_t)((wos::kNumCounters + 2) * sizeof(unsigned long long) + sizeof(uint32_t));
+  unsigned long long* d_stat = tape->d_cnt + wos::kNumCounters;  // entries written: sum, longest walk
+  const auto over_cap = [&](int64_t bytes) {
+    return fail(WOS_E_CAPACITY, "wos_tape_record: the tape needs more than " + std::to_string(bytes) +
+                                    " bytes, max_bytes is " + std::to_string(max_bytes));
+  };
+
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  HIP_TRY(hipEventCreate(&ev0));
+  struct EvGuard { hipEvent_t& a; hipEvent_t& b; ~EvGuard() { if (a) hipEventDestroy(a); if (b) hipEventDestroy(b); } } evg{ev0, ev1};
+  HIP_TRY(hipEventCreate(&ev1));
+  HIP_TRY(hipEventRecord(ev0, st));
+  if (n_chunks == 0) HIP_TRY(wos::launch_zero(c.d_counters, wos::kMainCounterSlots, nullptr, 0, st));
+  tape->seg.reserve((size_t)n_chunks);
+  for (int64_t k = 0; k < n_chunks; k++) {
+    const int64_t b0 = k * chunk;
+    const int64_t nb = std::min(chunk, n - b0);
+    tape->seg.emplace_back();
+    TapeSeg& g = tape->seg.back();
+    g.nb = nb;
+    g.T = nb * wpp;
+    const size_t tb = tape_task_bytes(dim, g.T, nb);
+    if (max_bytes > 0 && tape->bytes + (int64_t)tb > max_bytes) return over_cap(tape->bytes + (int64_t)tb);
+    HIP_TRY(hipMalloc(&g.buf, tb));
+    tape->bytes += (int64_t)tb;
+    tape_seg_views(g, dim, tape->d_flag);
+    // the batch as a solve lays it out; the first balls' records go to the tape at once
+    wos::DevTasks tk = task_view(c, dim, g.T, (int32_t)wpp, 1);
+    wos::DevTasks tkr = tk;
+    tkr.bdir = g.bdir;
+    tkr.sdir = g.sdir;
+    const int64_t bbase = index_base + b0 * index_stride;
+    unsigned long long* qslot = c.d_counters + wos::kNumCounters;
+    const int walk_grid = (int)std::min<int64_t>(plan.grid_walk, (g.T + 63) / 64);
+    HIP_TRY(wos::launch_zero(k == 0 ? c.d_counters : qslot,
+                             k == 0 ? wos::kNumCounterSlots : wos::kNumCounterSlots - wos::kNumCounters,
+                             tk.hist, 2 * wos::kCostBuckets, st));
+    HIP_TRY(wos::launch_point_setup(dim, plan.dfb, dp, d_pts + b0 * dim, nb, tk, st));
+    HIP_TRY(wos::launch_lpt_order(tk, nb, st));
+    HIP_TRY(wos::launch_first_balls_rec(dim, plan.dfb, dp, d_pts + b0 * dim, nb, bbase, index_stride, tkr, g.tp,
+                                        c.d_counters, (unsigned int*)qslot, plan.grid_fb, plan.shmem_fb_run,
+                                        plan.lhs_floats, st));
+    // pass 1, the plain walk kernel: its codes bound every walk's entries (its totals, from a
+    // zero first-ball source, are not used); its counters are the recording's
+    HIP_TRY(hipMemsetAsync(tk.tsrc, 0, (size_t)g.T * sizeof(float), st));
+    HIP_TRY(wos::launch_walks(plan.kv, plan.dsc, dp, tk, bbase, index_stride, c.d_counters,
+                              (unsigned int*)(c.d_counters + wos::kTaskQueueSlot0), walk_grid, plan.shmem_walk,
+                              plan.geom_floats_walk, st));
+    HIP_TRY(wos::launch_tape_slots(tk.code, g.T, (uint32_t*)g.tp.slot, d_bsum, st));
+    unsigned long long slots = 0;
+    HIP_TRY(hipMemcpyAsync(&slots, d_bsum + wos::tape_slot_blocks(g.T), sizeof(slots), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (slots >= (1ull << 31))
+      return fail(WOS_E_CAPACITY, "wos_tape_record: a batch's walks need " + std::to_string(slots) +
+                                      " entry slots (32-bit slot indices); lower wos_set_max_batch_tasks");
+    g.slots = slots;
+    const size_t eb = (size_t)std::max<unsigned long long>(slots, 1) * 12;
+    if (max_bytes > 0 && tape->bytes + (int64_t)eb > max_bytes) return over_cap(tape->bytes + (int64_t)eb);
+    HIP_TRY(hipMalloc(&g.ebuf, eb));
+    tape->bytes += (int64_t)eb;
+    g.tp.e_cell = (uint32_t*)g.ebuf;
+    g.tp.e_thr = (float*)g.ebuf + std::max<unsigned long long>(slots, 1);
+    g.tp.e_nrm = g.tp.e_thr + std::max<unsigned long long>(slots, 1);
+    HIP_TRY(hipMemsetAsync(g.ebuf, 0, eb, st));  // slots a walk leaves unused read as cell 0
+    // pass 2, the same walks again (deterministic), recording into their slots
+    tkr.code = g.code;
+    HIP_TRY(wos::launch_zero(d_cnt2, wos::kNumCounterSlots, nullptr, 0, st));
+    HIP_TRY(wos::launch_walks_rec(dim, plan.dsc.geom_global != 0, plan.dsc, dp, tkr, g.tp, bbase, index_stride, d_cnt2,
+                                  (unsigned int*)(d_cnt2 + wos::kTaskQueueSlot0), walk_grid, plan.shmem_walk,
+                                  plan.geom_floats_walk, st));
+    HIP_TRY(hipMemcpyAsync(g.pstate, tk.pstate, (size_t)nb * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+    HIP_TRY(wos::launch_tape_stats(g.code, g.tp.cnt, g.T, d_stat, st));
+  }
+  HIP_TRY(hipMemcpyAsync(tape->d_cnt, c.d_counters, wos::kNumCounters * sizeof(unsigned long long),
+                         hipMemcpyDeviceToDevice, st));
+  HIP_TRY(hipEventRecord(ev1, st));
+  unsigned long long h_cnt[wos::kNumCounters + 2] = {};
+  uint32_t h_flag = 0;
+  HIP_TRY(hipMemcpyAsync(h_cnt, tape->d_cnt, sizeof(h_cnt), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(&h_flag, tape->d_flag, sizeof(h_flag), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipEventRecord(c.done, st));
+  c.last_stream = st;
+  HIP_TRY(hipStreamSynchronize(st));
+  c.inflight = false;
+  if (h_flag)
+    return fail(WOS_E_DEVICE, "wos_tape_record: a walk outgrew the slots sized for it; the tape is discarded");
+  tape->n_entries = (int64_t)h_cnt[wos::kNumCounters];
+  tape->max_entries = (int64_t)h_cnt[wos::kNumCounters + 1];
+  if (stats) {
+    *stats = wos_stats{};
+    stats->walk_steps = h_cnt[0];
+    stats->wasted_steps = h_cnt[1];
+    stats->walks_recorded = h_cnt[2];
+    stats->walks_escaped = h_cnt[3];
+    stats->walks_max_length = h_cnt[4];
+    stats->walks_rr = h_cnt[5];
+    stats->walks_dirichlet = h_cnt[6];
+    stats->points_estimated = h_cnt[7];
+    stats->rejection_iters = h_cnt[8];
+    float ms = 0.0f;
+    HIP_TRY(hipEventElapsedTime(&ms, ev0, ev1));
+    stats->kernel_ms = ms;
+    stats->walk_launches = (uint64_t)(2 * n_chunks);
+    stats->first_ball_blocks_per_cu = tape->bpc_fb;
+    stats->walk_blocks_per_cu = tape->bpc_walk;
+    stats->walk_lds_bytes = tape->walk_lds;
+    stats->star_grid = tape->star_grid;
+    stats->geom_global = tape->geom_global;
+    stats->dir_grid = tape->dir_grid;
+  }
+  *out = tape.release();
+  return WOS_OK;
+}
+
+int wos_tape_solve(wos_tape* tape, wos_scene* s, int32_t n_channels, float* p, float* grad, float* p_var,
+                   float* grad_var, int32_t* n_est, int32_t* steps, wos_stats* stats, void* stream, uint32_t flags) {
+  if (!tape || !s) return fail(WOS_E_INVALID, "wos_tape_solve: null tape/scene");
+  const int64_t n = tape->n;
+  const int dim = tape->dim;
+  if (n > 0 && (!p || !grad)) return fail(WOS_E_INVALID, "wos_tape_solve: null output buffer");
+  std::lock_guard<std::mutex> lock(s->mu);
+  if (s->serial != tape->scene_serial)
+    return fail(WOS_E_INVALID, "wos_tape_solve: the tape was recorded on another scene");
+  if (n_channels != s->dev.n_channels)
+    return fail(WOS_E_INVALID, "wos_tape_solve: n_channels " + std::to_string(n_channels) +
+                                   " differs from the scene's " + std::to_string(s->dev.n_channels));
+  for (int k = 0; k < 3; k++)
+    if ((s->dev.source ? s->dev.sdims[k] : 0) != tape->sdims[k])
+      return fail(WOS_E_INVALID, "wos_tape_solve: the scene's source dims differ from the recorded ones "
+                                 "(the tape stores grid cells)");
+  HIP_TRY(hipSetDevice(s->device));
+  DevCtx& c = g_ctx[s->device];
+  std::lock_guard<std::mutex> lk(c.mu);
+  {
+    int rc = ctx_ready(c, s->device);
+    if (rc != WOS_OK) return rc;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  // the shared workspace, and the source a wos_scene_set_source* on another stream may still write
+  HIP_TRY(ctx_order(c, st));
+  const int C = n_channels;
+  float* d_p = p;
+  float* d_g = grad;
+  int32_t* d_nest = n_est;
+  int32_t* d_steps = steps;
+  float* d_pvar = p_var;
+  float* d_gvar = grad_var;
+  const bool dev_ptrs = (flags & WOS_PTRS_DEVICE) != 0;
+  if (!dev_ptrs && n > 0) {
+    int rc = ensure_workspace(c, dim, (size_t)n * C);
+    if (rc != WOS_OK) return rc;
+    d_p = c.d_p; d_g = c.d_g;
+    d_nest = n_est ? c.d_nest : nullptr;
+    d_steps = steps ? c.d_steps : nullptr;
+    if (p_var || grad_var) {
+      rc = ensure_var_workspace(c, (size_t)n * C);
+      if (rc != WOS_OK) return rc;
+      d_pvar = p_var ? c.d_pvar : nullptr;
+      d_gvar = grad_var ? c.d_gvar : nullptr;
+    }
+  }
+  // the replay's transient total / first [C][T]: the head of the task workspace
+  int64_t maxT = 0;
+  for (const TapeSeg& g : tape->seg) maxT = std::max(maxT, g.T);
+  if (maxT > 0) {
+    int rc = ensure_tasks(c, dim, maxT, 0, C);
+    if (rc != WOS_OK) return rc;
+  }
+  const int64_t n_chunks = (int64_t)tape->seg.size();
+  const uint64_t ticket = c.next_ticket++;
+  StatSlot& q = c.slot[ticket % kStatSlots];
+  while ((int64_t)q.bev.size() < 4 * n_chunks) {
+    hipEvent_t e = nullptr;
+    HIP_TRY(hipEventCreate(&e));
+    q.bev.push_back(e);
+  }
+  q.ticket = ticket;
+  q.n_batches = n_chunks;
+  q.bpc_fb = tape->bpc_fb;
+  q.bpc_walk = tape->bpc_walk;
+  q.walk_lds = tape->walk_lds;
+  q.star_grid = tape->star_grid;
+  q.geom_global = tape->geom_global;
+  q.dir_grid = tape->dir_grid;
+  HIP_TRY(hipEventRecord(q.ev0, st));
+  int64_t b0 = 0;
+  for (int64_t k = 0; k < n_chunks; k++) {
+    const TapeSeg& g = tape->seg[(size_t)k];
+    hipEvent_t* ev = &q.bev[4 * k];
+    float* total = c.d_tasks;
+    float* first = c.d_tasks + (int64_t)C * g.T;
+    HIP_TRY(hipEventRecord(ev[0], st));
+    HIP_TRY(hipEventRecord(ev[1], st));  // no first balls: walk_ms is the replay kernel
+    HIP_TRY(wos::launch_tape_replay(g.tp, g.code, s->dev, tape->dp.ignore_source, g.T, total, first, st));
+    HIP_TRY(hipEventRecord(ev[2], st));
+    wos::DevTasks tk{};
+    tk.code = g.code;
+    tk.bdir = g.bdir;
+    tk.sdir = g.sdir;
+    tk.pstate = g.pstate;
+    tk.T = g.T;
+    tk.wpp = (int32_t)tape->wpp;
+    for (int ch = 0; ch < C; ch++) {  // the solve's fold, unchanged, on the replayed totals
+      wos::DevTasks tkc = tk;
+      tkc.total = total + (int64_t)ch * g.T;
+      tkc.first = first + (int64_t)ch * g.T;
+      const int64_t o1 = (int64_t)ch * n + b0, od = ((int64_t)ch * n + b0) * dim;
+      HIP_TRY(wos::launch_fold(dim, tape->dp, tkc, g.nb, d_p + o1, d_g + od, (d_nest && ch == 0) ? d_nest + b0 : nullptr,
+                               (d_steps && ch == 0) ? d_steps + b0 : nullptr, d_pvar ? d_pvar + o1 : nullptr,
+                               d_gvar ? d_gvar + od : nullptr, st));
+    }
+    HIP_TRY(hipEventRecord(ev[3], st));
+    b0 += g.nb;
+  }
+  HIP_TRY(hipEventRecord(q.ev1, st));
+  HIP_TRY(hipMemcpyAsync(q.h_cnt, tape->d_cnt, wos::kNumCounters * sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                         st));
+  if (!dev_ptrs && n > 0) {
+    HIP_TRY(hipMemcpyAsync(p, d_p, (size_t)n * C * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(grad, d_g, (size_t)n * C * dim * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (n_est) HIP_TRY(hipMemcpyAsync(n_est, d_nest, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    if (steps) HIP_TRY(hipMemcpyAsync(steps, d_steps, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    if (p_var) HIP_TRY(hipMemcpyAsync(p_var, d_pvar, (size_t)n * C * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (grad_var)
+      HIP_TRY(hipMemcpyAsync(grad_var, d_gvar, (size_t)n * C * dim * sizeof(float), hipMemcpyDeviceToHost, st));
+  }
+  HIP_TRY(hipEventRecord(q.done, st));
+  HIP_TRY(hipEventRecord(c.done, st));
+  c.last_stream = st;
+  c.inflight = true;
+  if ((flags & WOS_ASYNC) && dev_ptrs) {
+    if (stats) {
+      *stats = wos_stats{};
+      stats->ticket = ticket;
+    }
+    return WOS_OK;
+  }
+  HIP_TRY(hipStreamSynchronize(st));
+  c.inflight = false;
+  if (stats) {
+    int rc = fill_stats(q, stats);
+    if (rc != WOS_OK) return rc;
+  }
+  return WOS_OK;
+}
+
+int wos_tape_get_info(const wos_tape* tape, wos_tape_info* info) {
+  if (!tape || !info) return fail(WOS_E_INVALID, "wos_tape_get_info: null argument");
+  *info = wos_tape_info{};
+  info->dim = tape->dim;
+  info->n_walks = tape->dp.n_walks;
+  for (int k = 0; k < 3; k++) info->source_dims[k] = tape->sdims[k];
+  info->device = tape->device;
+  info->n_points = tape->n;
+  info->n_tasks = tape->n * tape->wpp;
+  info->n_entries = tape->n_entries;
+  info->max_entries_per_walk = tape->max_entries;
+  info->bytes = tape->bytes;
+  info->replay_chunk_entries = wos::kTapeChunk;
+  return WOS_OK;
+}
+
+int wos_tape_destroy(wos_tape* tape) {
+  if (!tape) return WOS_OK;
+  {
+    // a replay enqueued with WOS_ASYNC may still read the tape
+    DevCtx& c = g_ctx[tape->device];
+    std::lock_guard<std::mutex> lk(c.mu);
+    hipSetDevice(tape->device);
+    if (c.ready && c.inflight && c.done) hipEventSynchronize(c.done);
+  }
+  delete tape;
+  return WOS_OK;
 }
 
 void wos_default_bvc_params(wos_bvc_params* p) {

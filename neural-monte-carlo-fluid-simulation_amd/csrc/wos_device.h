@@ -2163,8 +2163,17 @@ __device__ __forceinline__ void sample_volume_wave(const DevParams& prm, bool ac
 // ---------------------------------------------------------------------------
 // NC source channels (source_values): only totalSource and the deferred texel are per channel,
 // everything a walk decides on is shared
-template <int DIM, int NC = 1>
-struct WalkState {
+// REC (recording instantiations, wos_tape.hip): the walk writes what its source contributions
+// are made of to its slots of a DevTape instead of looking the source up; nothing otherwise
+template <bool REC>
+struct WalkRec {};
+template <>
+struct WalkRec<true> {
+  const DevTape* tape;
+  uint32_t rbase, rcap, rn;  // first slot, slots, entries so far
+};
+template <int DIM, int NC = 1, bool REC = false>
+struct WalkState : WalkRec<REC> {
   float pt[DIM], n[DIM], prevDir[DIM];
   float prevDist, throughput;
   bool onNeumann;
@@ -2177,8 +2186,8 @@ struct WalkState {
 };
 
 // Fold a deferred source contribution into totalSource (a no-op without one)
-template <int DIM, int NC>
-__device__ __forceinline__ void flush_source(WalkState<DIM, NC>& st) {
+template <int DIM, int NC, bool REC>
+__device__ __forceinline__ void flush_source(WalkState<DIM, NC, REC>& st) {
   if (st.pend) {
     for (int c = 0; c < NC; c++) st.totalSource[c] += st.pThr * (st.pNrm * st.pTex[c]);
     st.pend = false;
@@ -2282,9 +2291,9 @@ __device__ __forceinline__ int fcpw_stochastic_pick(const DevScene& sc, const fl
 // non-finite; only then the stochastic sample is evaluated -- at every step with
 // image-valued h (DevScene::nimg).  flip: this step flipped the walk's normal
 // (flipNormalOrientation, double-sided scenes); prec: silhouettePrecision.
-template <int DIM, bool RB, int NC>
+template <int DIM, bool RB, int NC, bool REC>
 __device__ __forceinline__ void neumann_term(const DevScene& sc, const float* prims, const Gfn<DIM, RB>& g,
-                                             WalkState<DIM, NC>& st, float R, const float* rn, bool flip, float prec) {
+                                             WalkState<DIM, NC, REC>& st, float R, const float* rn, bool flip, float prec) {
   constexpr int PS = Layout<DIM>::prim;
   const int np = sc.n_prims;
   const float* x = st.pt;
@@ -2355,9 +2364,9 @@ __device__ __forceinline__ void neumann_term(const DevScene& sc, const float* pr
 //   star_radius_wave -- (convergent, all lanes) computeStarRadius;
 //   walk_step_end    -- ball update, direction, ray, source sample, move, roulette.
 // Returns -1 while the walk continues, else its termination code.
-template <int DIM, int NC>
+template <int DIM, int NC, bool REC>
 __device__ __forceinline__ int walk_step_begin(const DevScene& sc, const DevParams& prm, float dirichletDist,
-                                               WalkState<DIM, NC>& st, bool* flip, bool* query, float firstR = 0.0f) {
+                                               WalkState<DIM, NC, REC>& st, bool* flip, bool* query, float firstR = 0.0f) {
   if (!(dirichletDist > prm.epsilon_shell)) return WC_DIRICHLET;
   *flip = false;
   // first step of a boundary-start walk: the precomputed first sphere radius
@@ -2374,9 +2383,9 @@ __device__ __forceinline__ int walk_step_begin(const DevScene& sc, const DevPara
 }
 
 // ball + direction + ray origin; the ray query follows (walk_on_stars.h:169-210)
-template <int DIM, bool RB, int NC>
+template <int DIM, bool RB, int NC, bool REC>
 __device__ __forceinline__ float walk_step_mid(const DevParams& prm, float dirichletDist, Pcg32& smp, Gfn<DIM, RB>& g,
-                                               WalkState<DIM, NC>& st, uint32_t* steps, bool query, float starQ,
+                                               WalkState<DIM, NC, REC>& st, uint32_t* steps, bool query, float starQ,
                                                float* dir, float* org, float firstR = 0.0f) {
   float starRadius = dirichletDist;
   if (firstR > 0.0f) {
@@ -2407,9 +2416,9 @@ __device__ __forceinline__ float walk_step_mid(const DevParams& prm, float diric
 // the source sample (convergent, sample_volume_wave) and walk_step_tail follow
 // NEU = false: the instantiation for scenes whose Neumann term is provably +0 at every
 // step (DevParams::neumann_inert) -- the term's code is compiled out, the draws stay
-template <int DIM, bool RB, bool NEU = true, int NC>
+template <int DIM, bool RB, bool NEU = true, int NC, bool REC>
 __device__ __forceinline__ void walk_step_end(const DevScene& sc, const DevParams& prm, const LGeom& G,
-                                              Pcg32& smp, Gfn<DIM, RB>& g, WalkState<DIM, NC>& st, float starRadius,
+                                              Pcg32& smp, Gfn<DIM, RB>& g, WalkState<DIM, NC, REC>& st, float starRadius,
                                               const float* dir, const float* org, bool hit, Hit& ip, bool flip) {
   const int np = sc.n_prims;
   const float* prims = G.prim;
@@ -2431,18 +2440,30 @@ __device__ __forceinline__ void walk_step_end(const DevScene& sc, const DevParam
 }
 
 // after the source sample (walk_on_stars.h:270-327)
-template <int DIM, bool RB, int NC>
+template <int DIM, bool RB, int NC, bool REC>
 __device__ __forceinline__ int walk_step_tail(const DevScene& sc, const LGeom& G, const DevParams& prm,
                                               float& dirichletDist,
-                                              Pcg32& smp, Gfn<DIM, RB>& g, WalkState<DIM, NC>& st, const float* dir,
+                                              Pcg32& smp, Gfn<DIM, RB>& g, WalkState<DIM, NC, REC>& st, const float* dir,
                                               bool hit, const Hit& ip, const float* sp) {
   if (!prm.ignore_source) {
     flush_source<DIM>(st);
     if (g.r <= ip.d) {
-      st.pNrm = g.norm();
-      st.pThr = st.throughput;
-      source_values<DIM, NC>(sc, sp, st.pTex);
-      st.pend = true;
+      if constexpr (REC) {
+        // the entry (cell, pThr, pNrm) in place of the texel; never past the walk's slots
+        if (st.rn < st.rcap) {
+          const DevTape& tp = *st.tape;
+          const uint32_t e = st.rbase + st.rn;
+          tp.e_cell[e] = (uint32_t)source_cell<DIM>(sc, sp);
+          tp.e_thr[e] = st.throughput;
+          tp.e_nrm[e] = g.norm();
+        }
+        st.rn++;
+      } else {
+        st.pNrm = g.norm();
+        st.pThr = st.throughput;
+        source_values<DIM, NC>(sc, sp, st.pTex);
+        st.pend = true;
+      }
     }
   }
   if (!hit && outside_bbox<DIM>(sc, ip.p)) return WC_ESCAPED;
@@ -3357,11 +3378,14 @@ __device__ __forceinline__ void build_lhs(const DevParams& prm, const unsigned l
 // 2D first balls: K0, I0, K1, I1 at the sampled radius from one fused Bessel evaluation
 // (pdf and gradient norm), and the second member reuses the first's gradient norm when its
 // radius is the same float -- identical values, fewer double-precision exp / sqrt / divisions
-template <int DIM, bool RB, int NC = 1>
+// REC (wos_tape.hip): the source sample's norm and grid cell go to `tape` instead of the texel's
+// products to tk.first / tk.tsrc
+template <int DIM, bool RB, int NC = 1, bool REC = false>
 __device__ __forceinline__ void first_balls(const DevScene& sc, const DevParams& prm, const DevTasks& tk,
                                             const float* x, float firstR, const float* strat, int64_t gidx,
                                             bool active, int w, int64_t t0, bool yuk0, uint32_t* iters,
-                                            RejLDS* rejL, int lane, const float* pb, const float* dn) {
+                                            RejLDS* rejL, int lane, const float* pb, const float* dn,
+                                            const DevTape* tape = nullptr) {
   constexpr int sd = DIM - 1;
   if (DIM == 2 && !active) return;
   if (!active) w = 0;
@@ -3395,6 +3419,8 @@ __device__ __forceinline__ void first_balls(const DevScene& sc, const DevParams&
     for (int c = 0; c < NC; c++) { totalSource[c] = 0.0f; firstSource[c] = 0.0f; }
     float sdir[DIM], bdir[DIM];
     for (int k = 0; k < DIM; k++) sdir[k] = 0.0f;
+    float rec_gnorm = 0.0f;
+    uint32_t rec_cell = 0u;
     if (!prm.ignore_source) {
       if (a == 0) {
         DIAG_T0(t_smp);
@@ -3446,12 +3472,17 @@ __device__ __forceinline__ void first_balls(const DevScene& sc, const DevParams&
         g.r = normv<DIM>(sdv);
       }
       float gnorm = g.norm();
-      float tex[NC];
-      source_values<DIM, NC>(sc, g.yVol, tex);
-      for (int c = 0; c < NC; c++) {
-        float contrib = gnorm * tex[c];
-        totalSource[c] += throughput * contrib;
-        firstSource[c] = contrib;
+      if constexpr (REC) {
+        rec_gnorm = gnorm;
+        rec_cell = (uint32_t)source_cell<DIM>(sc, g.yVol);
+      } else {
+        float tex[NC];
+        source_values<DIM, NC>(sc, g.yVol, tex);
+        for (int c = 0; c < NC; c++) {
+          float contrib = gnorm * tex[c];
+          totalSource[c] += throughput * contrib;
+          firstSource[c] = contrib;
+        }
       }
       float gr[DIM];
       if (DIM == 2 && g.yukawa == 1 && g.r == r_a) {
@@ -3524,7 +3555,10 @@ __device__ __forceinline__ void first_balls(const DevScene& sc, const DevParams&
     DIAG_ADD(a == 0 ? D_FB_MA : D_FB_MB, t_mem);
     if (!active) continue;
     DIAG_T0(t_st);
-    if constexpr (NC == 1) {
+    if constexpr (REC) {
+      tape->gnorm[t] = rec_gnorm;
+      tape->cell0[t] = rec_cell;
+    } else if constexpr (NC == 1) {
       tk.first[t] = firstSource[0];
     } else {
       for (int c = 0; c < NC; c++)
@@ -3536,7 +3570,8 @@ __device__ __forceinline__ void first_balls(const DevScene& sc, const DevParams&
       tk.pt[k * T + t] = g.ySurf[k];
     }
     tk.thr[t] = throughput;
-    if constexpr (NC == 1) {
+    if constexpr (REC) {
+    } else if constexpr (NC == 1) {
       tk.tsrc[t] = totalSource[0];
     } else {
       for (int c = 0; c < NC; c++)
@@ -3762,154 +3797,15 @@ __global__ __launch_bounds__(256) void wos_point_setup_kernel(const DevScene sc,
 // wos_point_setup_kernel ran first: point i's state and first-ball radius are read
 // from pstate / prad (no geometry is staged: the first balls query none).
 // NC: source channels (1, or kMaxChannels: source_values).
+// The body is wos_first_ball_body.inc, shared word for word with the recording kernel of
+// wos_tape.hip (REC = true writes `tape`).
 template <int DIM, bool RB = false, int NC = 1>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(DIM == 2 ? WOS_FB_WAVES_PER_EU2 : WOS_FB_WAVES_PER_EU))) void wos_first_ball_kernel(
     const DevScene sc, const DevParams prm, const float* __restrict__ pts, int64_t n, int64_t base, int64_t stride,
     const DevTasks tk, unsigned long long* __restrict__ counters, unsigned int* __restrict__ work, int lhs_floats) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  const int lane = threadIdx.x & (kWave - 1);
-  const int wave = threadIdx.x / kWave;
-  const int npairs = prm.n_pairs;
-  // P points per wave (fb_points_per_wave): slot s holds its stratified samples and
-  // shuffle partners at wbase + 2 s lhs_floats; the rejection sampler's / shuffle's
-  // scratch follows the P slots; the block's staged jump constants follow the waves
-  const int P = fb_points_per_wave(npairs);
-  const int wave_floats = 2 * P * lhs_floats + (int)(fb_union_bytes(P * lhs_floats, 2 * npairs) / sizeof(float));
-  float* wbase = smem + wave * wave_floats;
-  unsigned long long* ljump = reinterpret_cast<unsigned long long*>(smem + (int)(blockDim.x / kWave) * wave_floats);
-  stage_rej_jump(prm);
-  for (int i = threadIdx.x; i < 2 * prm.lhs_jump_n; i += blockDim.x) ljump[i] = prm.jump[i];
-#if WOS_DIAG
-  if (threadIdx.x < D_NUM) s_diag[threadIdx.x] = 0u;
-#endif
-  __syncthreads();
-  RejLDS* rejL = reinterpret_cast<RejLDS*>(wbase + 2 * P * lhs_floats);
-  // this lane's point slot and pair (P == 1: all lanes serve the one point, pairs w0 + lane);
-  // span = lanes per slot, so lane s * span is slot s's first lane (wave-uniform)
-  const int span = P > 1 ? npairs : kWave;
-  const int slot = P > 1 ? lane / npairs : 0;
-  const int wl = lane - slot * span;
-  const bool used = slot < P;
-  const int myslot = used ? slot : 0;
-
-  uint32_t c_iters = 0, c_pts = 0;
-  const bool yuk0 = sc.absorption > 0.0f && prm.steps_before_tikhonov == 0;
-
-  // point queue, one chunk of P points ahead: the next index is taken (and each lane's
-  // point coordinates, radius and state loaded) while the current chunk is processed, so
-  // neither the queue atomic nor the point loads sit on a point's critical path.  Points
-  // are taken kPtGrab chunks at a time (one queue atomic per grab: a single-address
-  // atomic per point serialises at ~13 ns, which had bounded the whole kernel).
-  const unsigned int take = kPtGrab * (unsigned int)P;
-  unsigned int idx = 0;
-  if (lane == 0) idx = atomicAdd(work, take);
-  idx = __shfl(idx, 0);
-  unsigned int cend = idx + take;
-  float xn[DIM], rn = 0.0f;
-  bool en = false;
-  // 2D Yukawa, reference semantics: the first ball's Bessel members come from the setup kernel
-  const bool pre = !RB && DIM == 2 && yuk0;
-  float bn[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-  {
-    const unsigned int li = idx + (unsigned int)myslot;
-    for (int k = 0; k < DIM; k++) xn[k] = (int64_t)li < n ? pts[(int64_t)li * DIM + k] : 0.0f;
-    if ((int64_t)li < n) {
-      rn = tk.prad[li];
-      en = (tk.pstate[li] & kPtEstimate) != 0;
-      if (pre)
-        for (int k = 0; k < 4; k++) bn[k] = tk.pball[k * tk.pball_stride + li];
-    }
-  }
-  for (;;) {
-    if ((int64_t)idx >= n) break;
-    float x[DIM];
-    for (int k = 0; k < DIM; k++) x[k] = xn[k];
-    float firstR = rn;
-    const bool estimate = en && used;
-    float pb[4];
-    for (int k = 0; k < 4; k++) pb[k] = bn[k];
-    const bool grab = idx + (unsigned int)P >= cend;  // wave-uniform
-    unsigned int nidx_l0 = 0;
-    if (grab && lane == 0) nidx_l0 = atomicAdd(work, take);
-    DIAG_T0(t_fb0);
-    // the next chunk: its index (the atomic has returned by now), coordinates, radius, state
-    unsigned int nidx, ncend = cend;
-    if (grab) {
-      nidx = (unsigned int)__shfl((int)nidx_l0, 0);
-      ncend = nidx + take;
-    } else {
-      nidx = idx + (unsigned int)P;
-    }
-    {
-      const unsigned int li = nidx + (unsigned int)myslot;
-      for (int k = 0; k < DIM; k++) xn[k] = (int64_t)li < n ? pts[(int64_t)li * DIM + k] : 0.0f;
-      en = false;
-      if ((int64_t)li < n) {
-        rn = tk.prad[li];
-        en = (tk.pstate[li] & kPtEstimate) != 0;
-        if (pre)
-          for (int k = 0; k < 4; k++) bn[k] = tk.pball[k * tk.pball_stride + li];
-      }
-    }
-    // estimated slots: bit s * span set when point idx + s is estimated
-    const uint64_t em = __ballot(estimate && wl == 0);
-    if (em == 0) { idx = nidx; cend = ncend; continue; }
-    c_pts += lane == 0 ? (uint32_t)__popcll(em) : 0u;
-    DIAG_ADD(D_FB_SETUP, t_fb0);
-    DIAG_COUNT(D_FB_PTS, __popcll(em));
-    DIAG_T0(t_fb1);
-    const bool all = lhs_all_fits(npairs, DIM, P);
-    for (int s = 0; s < P; s++) {
-      if (!all && !((em >> (s * span)) & 1ull)) continue;
-      float* strat_s = wbase + 2 * s * lhs_floats;
-      build_lhs<DIM>(prm, ljump, base + (int64_t)(idx + (unsigned int)s) * stride, strat_s,
-                     reinterpret_cast<int*>(strat_s + lhs_floats), reinterpret_cast<char*>(rejL), lane, !all);
-    }
-    if constexpr (DIM == 3)
-      if (all) {
-        const int ns = 2 * npairs;
-        const int* part0 = reinterpret_cast<const int*>(wbase + lhs_floats);
-        if (ns <= kWave) lhs_permute_reg<DIM - 1, 1, 4>(wbase, part0, 2 * lhs_floats, 0, P * (DIM - 1), ns, lane);
-        else lhs_permute_reg<DIM - 1, 2, 2>(wbase, part0, 2 * lhs_floats, 0, P * (DIM - 1), ns, lane);
-      }
-    DIAG_ADD(D_FB_LHS, t_fb1);
-    DIAG_T0(t_fb2);
-    // lanes without a point of their own (an unestimated slot, or beyond P slots) run the
-    // first estimated slot's pair-0 arithmetic and write nothing (3D: they still serve the
-    // cooperative sampler)
-    const int fs = (int)(__builtin_ctzll(em) / (unsigned)span);
-    const int es = estimate ? myslot : fs;
-    if (!estimate) {
-      for (int k = 0; k < DIM; k++) x[k] = lane_bcast(x[k], fs * span);
-      firstR = lane_bcast(firstR, fs * span);
-      for (int k = 0; k < 4; k++) pb[k] = lane_bcast(pb[k], fs * span);
-    }
-    const unsigned int pidx = idx + (unsigned int)es;
-    const int64_t gidx = base + (int64_t)pidx * stride;
-    const float* strat = wbase + 2 * es * lhs_floats;
-    const int wend = P > 1 ? 1 : npairs;
-    for (int w0 = 0; w0 < wend; w0 += kWave) {
-      const int w = w0 + wl;
-      first_balls<DIM, RB, NC>(sc, prm, tk, x, firstR, strat, gidx, estimate && w < npairs, w,
-                           (int64_t)pidx * tk.wpp + (int64_t)w * prm.n_anti, yuk0, &c_iters, rejL, lane,
-                           pb, tk.ddir ? tk.ddir + (int64_t)pidx * DIM : nullptr);
-    }
-    DIAG_ADD(D_FB_BALLS, t_fb2);
-    DIAG_ADD(D_FB_TOTAL, t_fb0);
-    DIAG_MAX(D_FB_MAX, __builtin_amdgcn_s_memtime() - t_fb0);
-    wave_sync();
-    idx = nidx;
-    cend = ncend;
-  }
-  flush_counter(counters, C_ITERS, c_iters, lane);
-  flush_counter(counters, C_PTS, c_pts, lane);
-#if WOS_DIAG
-  __syncthreads();
-  if (threadIdx.x < D_NUM) {
-    if (diag_is_max(threadIdx.x)) atomicMax(&g_diag[threadIdx.x], s_diag[threadIdx.x]);
-    else atomicAdd(&g_diag[threadIdx.x], s_diag[threadIdx.x]);
-  }
-#endif
+  constexpr bool REC = false;
+  const DevTape* const tape = nullptr;
+#include "wos_first_ball_body.inc"
 }
 
 // issue priority of the calling wave (s_setprio takes an immediate), uniform level 0..3
@@ -3922,10 +3818,10 @@ __device__ __forceinline__ void wave_priority(int level) {
 // ---- kernel 2: walks ---------------------------------------------------------
 // The state a walk task starts from (the hand-out of walk_on_stars.h:494-579 after
 // the first ball; BSTART: estimateSolution's boundary start, :437-439) ...
-template <int DIM, bool BSTART, bool RB, int NC>
+template <int DIM, bool BSTART, bool RB, int NC, bool REC>
 __device__ __forceinline__ void walk_start(const DevScene& sc, const DevParams& prm, const DevTasks& tk, int64_t t,
                                            uint32_t pidx, uint32_t w, const float* v_pt, float v_thr, const float* v_tsrc,
-                                           float v_dd, int64_t base, int64_t stride, bool yuk0, WalkState<DIM, NC>& st,
+                                           float v_dd, int64_t base, int64_t stride, bool yuk0, WalkState<DIM, NC, REC>& st,
                                            Gfn<DIM, RB>& g, Pcg32& ws, float& ddist, uint32_t& wsteps, float& firstR) {
   for (int kk = 0; kk < DIM; kk++) { st.pt[kk] = v_pt[kk]; st.n[kk] = 0.0f; st.prevDir[kk] = 0.0f; }
   // prevDir/prevDist only matter once the walk stands on a Neumann boundary,
@@ -3937,6 +3833,11 @@ __device__ __forceinline__ void walk_start(const DevScene& sc, const DevParams& 
   st.totalNeumann = 0.0f;
   for (int c = 0; c < NC; c++) st.totalSource[c] = v_tsrc[c];
   st.pend = false;
+  if constexpr (REC) {
+    st.rbase = st.tape->slot[t];
+    st.rcap = st.tape->slot[t + 1] - st.rbase;
+    st.rn = 0u;
+  }
   ddist = v_dd;
   g.init(yuk0, sc.absorption);
   if constexpr (BSTART) {
@@ -3958,9 +3859,9 @@ __device__ __forceinline__ void walk_start(const DevScene& sc, const DevParams& 
 // One iteration of the walk loop for every lane of the wave (convergent): the lanes
 // with active == false take part in the cooperative queries only.  Returns the
 // termination code (>= 0) or -1 while the walk continues.
-template <int DIM, bool GG, bool BSTART, bool RB, bool NEU = true, int NC>
+template <int DIM, bool GG, bool BSTART, bool RB, bool NEU = true, int NC, bool REC>
 __device__ __forceinline__ int walk_iteration(const DevScene& sc, const DevParams& prm, const LGeom& G, bool active,
-                                              WalkState<DIM, NC>& st, Gfn<DIM, RB>& gc, Pcg32& ws, float& ddist,
+                                              WalkState<DIM, NC, REC>& st, Gfn<DIM, RB>& gc, Pcg32& ws, float& ddist,
                                               uint32_t& wsteps, float& firstR, StarLDS<DIM>* starL,
                                               RayLDS<DIM>* rayL, RejLDS* rejL, uint32_t* c_iters, int lane) {
   DIAG_T0(t_step);
@@ -4027,14 +3928,23 @@ __device__ __forceinline__ int walk_iteration(const DevScene& sc, const DevParam
 }
 
 // the record of a finished walk (walk_on_stars.h:583-585: escaped and over-length walks are dropped)
-template <int DIM, int NC>
+template <int DIM, int NC, bool REC>
 __device__ __forceinline__ void walk_finish(const DevScene& sc, const DevParams& prm, const DevTasks& tk, int64_t t,
-                                            int code, WalkState<DIM, NC>& st, uint32_t wsteps, unsigned int* s_ctr) {
+                                            int code, WalkState<DIM, NC, REC>& st, uint32_t wsteps, unsigned int* s_ctr) {
   flush_source<DIM>(st);
   const bool recorded = code == WC_DIRICHLET || code == WC_RR;
   if (recorded) {
     const float term = (code == WC_DIRICHLET && !prm.ignore_dirichlet) ? dirichlet_value<DIM>(sc, st.pt) : 0.0f;
-    if constexpr (NC == 1) {
+    if constexpr (REC) {
+      // the total's source-free parts; a walk that outgrew its slots voids the tape
+      const DevTape& tp = *st.tape;
+      const bool own_g = code == WC_DIRICHLET && !prm.ignore_dirichlet && sc.dimg == nullptr;
+      if (st.rn > st.rcap) *tp.overflow = 1u;
+      tp.cnt[t] = (st.rn < st.rcap ? st.rn : st.rcap) | (own_g ? kTapeOwnG : 0u);
+      tp.thr_end[t] = st.throughput;
+      tp.term[t] = term;
+      tp.tneu[t] = st.totalNeumann;
+    } else if constexpr (NC == 1) {
       const float tot = st.throughput * term + st.totalNeumann + st.totalSource[0];
       if (!WOS_ACCT_NOREC) tk.total[t] = tot;
     } else {
@@ -4115,8 +4025,8 @@ static_assert(sizeof(WalkState<2, kMaxChannels>) == 4 * (3 * 2 + 6 + 4 + 2 * (kM
 static_assert(sizeof(Gfn<2, false>) == 4 * (1 + 3 * 2 + 9) && sizeof(Gfn<3, true>) == 4 * (1 + 3 * 3 + 9), "Gfn members");
 static_assert(sizeof(Pcg32) == 8, "Pcg32 state");
 // one walk's state into / out of mailbox slot `slot` (word-major, kSpreadMax slots per word)
-template <int DIM, bool RB, int NC>
-__device__ __forceinline__ void spread_put(uint32_t* mb, int slot, const WalkState<DIM, NC>& st, const Gfn<DIM, RB>& g,
+template <int DIM, bool RB, int NC, bool REC>
+__device__ __forceinline__ void spread_put(uint32_t* mb, int slot, const WalkState<DIM, NC, REC>& st, const Gfn<DIM, RB>& g,
                                            const Pcg32& ws, float ddist, float firstR, uint32_t wsteps, uint32_t t) {
   int q = 0;
   auto put = [&](uint32_t v) {
@@ -4135,8 +4045,8 @@ __device__ __forceinline__ void spread_put(uint32_t* mb, int slot, const WalkSta
   (void)firstR;  // 0 after every step (a boundary-start walk's first-sphere radius is used once)
   putf(ddist); put(wsteps); put(t);
 }
-template <int DIM, bool RB, int NC>
-__device__ __forceinline__ void spread_get(const uint32_t* mb, int slot, WalkState<DIM, NC>& st, Gfn<DIM, RB>& g,
+template <int DIM, bool RB, int NC, bool REC>
+__device__ __forceinline__ void spread_get(const uint32_t* mb, int slot, WalkState<DIM, NC, REC>& st, Gfn<DIM, RB>& g,
                                            Pcg32& ws, float& ddist, float& firstR, uint32_t& wsteps, int64_t& t) {
   int q = 0;
   auto get = [&]() { return mb[(q++) * kSpreadMax + slot]; };
@@ -4168,313 +4078,15 @@ struct SpreadLDS {
 // start normal, first sphere radius, on-Neumann flag from DevTasks::n0/r0/sflags, no
 // first ball, walk stream tag 6) -- boundary value caching (wos_bvc.hip).
 // NC: source channels carried by every walk (1, or kMaxChannels: source_values).
+// The body is wos_walk_body.inc, shared word for word with the recording kernel of wos_tape.hip
+// (REC = true; `tape` its DevTape, the kernel's last argument).
 template <int DIM, bool GG, bool BSTART = false, bool RB = false, bool NEU = true, bool SPR = false, int NC = 1>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(DIM == 2 ? WOS_WALK_WAVES_PER_EU : WOS_WALK_WAVES_PER_EU3))) void wos_walk_kernel(
     const DevScene sc_arg, const DevParams prm_arg, const DevTasks tk_arg, int64_t base, int64_t stride,
     unsigned long long* __restrict__ counters, unsigned int* __restrict__ tqueue, int geom_floats) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  __shared__ unsigned int s_ctr[C_NUM];
-  __shared__ SpreadLDS s_spread;
-  const DevScene& sc = sc_arg;
-  const DevParams& prm = prm_arg;
-  const DevTasks& tk = tk_arg;
-  static_assert(walk_pack_words<DIM, NC>() * kSpreadMax * 4 <= (int)walk_scratch_bytes<DIM>(), "mailbox fits the scratch");
-  static_assert(!(BSTART && NC != 1), "boundary-start walks carry one channel");
-  constexpr bool kSpread = SPR;
-  const int lane = threadIdx.x & (kWave - 1);
-  stage_geometry<DIM, GG>(sc, smem, true);
-  stage_rej_jump(prm);
-  // per-wave scratch shared by the star and ray queries (used one after the other)
-  const int wave_u = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / kWave));  // wave-uniform: SGPR address
-  char* wscratch = reinterpret_cast<char*>(smem + geom_floats) + wave_u * walk_scratch_bytes<DIM>();
-  StarLDS<DIM>* starL = reinterpret_cast<StarLDS<DIM>*>(wscratch);
-  RayLDS<DIM>* rayL = reinterpret_cast<RayLDS<DIM>*>(wscratch);
-  RejLDS* rejL = reinterpret_cast<RejLDS*>(wscratch);
-  if (threadIdx.x < C_NUM) s_ctr[threadIdx.x] = 0u;
-  if (threadIdx.x == 0) { s_spread.busy = blockDim.x / kWave; s_spread.idle = 0u; }
-  if (threadIdx.x < kBlock / kWave) s_spread.mbox[threadIdx.x] = 0u;
-#if WOS_DIAG
-  if (threadIdx.x < D_NUM) s_diag[threadIdx.x] = 0u;
-#endif
-  __syncthreads();
-
-  const uint32_t T = (uint32_t)tk.T;
-  const uint32_t wpp = (uint32_t)tk.wpp;
-  // x / wpp as a shift when walks-per-point is a power of two (every shipped config)
-  const int wsh = (wpp & (wpp - 1u)) == 0u ? __builtin_ctz(wpp) : -1;
-  auto divw = [&](uint32_t x) -> uint32_t { return wsh >= 0 ? x >> wsh : x / wpp; };
-  const bool yuk0 = sc.absorption > 0.0f && prm.steps_before_tikhonov == 0;
-  uint32_t c_iters = 0;
-  wave_priority(prm.wave_prio);
-#if WOS_TIMELINE
-  uint64_t tl_t0 = 0;
-  if (lane == 0) {
-    const unsigned long long now = __builtin_amdgcn_s_memrealtime();
-    const unsigned long long old = atomicCAS(&g_tl[0], 0ull, now);
-    tl_t0 = old == 0ull ? now : old;
-  }
-  tl_t0 = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(tl_t0 >> 32)) << 32) |
-          (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)tl_t0);
-  auto tl_bin = [&](uint64_t ts) -> int {
-    const uint64_t b = ts > tl_t0 ? (ts - tl_t0) >> kTlShift : 0;
-    return b < (uint64_t)kTlBins ? (int)b : kTlBins - 1;
-  };
-#endif
-
-  DIAG_T0(t_wave);
-  // ---- task supply: a window [wq, we) of the global queue (wave-uniform; lane i
-  // holds perm[wp0 + i]) feeds a 64-slot ring of staged tasks, one per lane: ring
-  // position (lane - head) & 63, positions [0, S) valid.  The ring is refilled at
-  // the end of every iteration, so the loads of a staged task's point state are in
-  // flight during a whole step and a lane that finishes a walk starts the next one
-  // from registers (cross-lane shuffles) instead of a chain of dependent global loads.
-  // <= 64 points per window
-  // 3D: windows of 128 tasks (walk kernel -2 % on D and E, bit-exact: profiles/r5zo_ab_grab3.log; in 2D they
-  // slowed the karman stride-8 shard, r5zl_ab_star_help2_queue.log)
-  constexpr uint32_t kGrabD = DIM == 3 ? WOS_TASK_GRAB3 : kTaskGrab;
-  const uint32_t G_win = kGrabD < 63u * wpp ? kGrabD : 63u * wpp;
-  // the head of the cost order (the hardest points) is dealt in smaller windows, so the
-  // long walks of one point spread over more waves: kTaskHead windows of kTaskGrabHead
-  // tasks per wave of the grid, then windows of G_win
-  const uint32_t G_head = kTaskGrabHead < G_win ? kTaskGrabHead : G_win;
-  const uint32_t n_head = (uint32_t)__builtin_amdgcn_readfirstlane((int)(kTaskHead * gridDim.x * (blockDim.x / kWave)));
-  const uint32_t NH = G_head > 0u ? ((T + G_head - 1u) / G_head < n_head ? (T + G_head - 1u) / G_head : n_head) : 0u;
-  const uint64_t H = (uint64_t)NH * G_head < (uint64_t)T ? (uint64_t)NH * G_head : (uint64_t)T;
-  uint32_t wq = 0, we = 0, wp0 = 0, wperm = 0;
-  bool exhausted = false;
-  const uint32_t qhome = blockIdx.x & (kTaskQueues - 1u);
-  uint32_t qdone = 0u;  // queues found exhausted (wave-uniform)
-  int head = 0, S = 0;
-  uint32_t s_t = 0, s_ok = 0;  // staged task index, its point is estimated
-  auto refill = [&](const DevTasks& tk) {
-    while (S < kWave && !exhausted) {
-      if (wq >= we) {
-        unsigned int c = 0xFFFFFFFFu, len = 0u;
-        if (lane == 0) {
-          for (uint32_t k = 0; k < kTaskQueues; k++) {
-            const uint32_t x = (qhome + k) & (kTaskQueues - 1u);
-            if ((qdone >> x) & 1u) continue;
-            // queue x's draws: its head windows x, x + Q, ... (< NH), then its tail windows
-            const uint32_t d = atomicAdd(tqueue + x * kTaskQueueStride, 1u);
-            const uint32_t nhx = NH > x ? (NH - x + kTaskQueues - 1u) / kTaskQueues : 0u;
-            const uint64_t st = d < nhx ? (uint64_t)(d * kTaskQueues + x) * G_head
-                                        : H + (uint64_t)((uint64_t)(d - nhx) * kTaskQueues + x) * G_win;
-            if (st < (uint64_t)T) {
-              c = (unsigned int)st;
-              len = d < nhx ? G_head : G_win;
-              break;
-            }
-            qdone |= 1u << x;  // exhausted: never drawn from again by this wave
-          }
-        }
-        c = (unsigned int)__builtin_amdgcn_readlane((int)c, 0);
-        len = (unsigned int)__builtin_amdgcn_readlane((int)len, 0);
-        qdone = (uint32_t)__builtin_amdgcn_readlane((int)qdone, 0);
-        if (c == 0xFFFFFFFFu) { exhausted = true; break; }
-        wq = c;
-        we = (T - c) < len ? T : c + len;
-        wp0 = divw(c);
-        const uint32_t np = divw(we - 1) - wp0 + 1;
-        wperm = (uint32_t)lane < np ? tk.perm[wp0 + lane] : 0u;
-      }
-      const int avail = (int)(we - wq);
-      const int take = (kWave - S) < avail ? (kWave - S) : avail;
-      const int pos = ((lane - head) & (kWave - 1)) - S;
-      const bool mine = pos >= 0 && pos < take;
-      const uint32_t q = wq + (mine ? (uint32_t)pos : 0u), qp = divw(q);
-      const uint32_t pidx = (uint32_t)__shfl((int)wperm, (int)(qp - wp0));  // queue position -> permuted point
-      if (mine) {
-        s_t = pidx * wpp + (q - qp * wpp);
-        s_ok = tk.pstate[pidx] & kPtEstimate;
-      }
-      S += take;
-      wq += (uint32_t)take;
-    }
-  };
-  refill(tk);
-  int64_t t = -1;           // this lane's task
-  WalkState<DIM, NC> st;
-  Gfn<DIM, RB> g;
-  Pcg32 ws;
-  float ddist = 0.0f;
-  uint32_t wsteps = 0;
-  float firstR = 0.0f;  // BSTART: first sphere radius of the lane's walk, 0 after its first step
-
-  for (;;) {
-    DIAG_T0(t_loop);
-#if WOS_TIMELINE
-    const uint64_t tl_a = __builtin_amdgcn_s_memrealtime();
-#endif
-    // per-iteration views of the kernel parameters and of the staged geometry (see kview)
-    KernArgsPtr ka = kernargs_opaque();
-    const DevScene& sc = (const DevScene&)ka->sc;
-    const DevParams& prm = (const DevParams&)ka->prm;
-    const DevTasks& tk = (const DevTasks&)ka->tk;
-    const LGeom G = geometry_view<DIM, GG>(sc, smem, true, false);
-    // ---- hand staged tasks to idle lanes (uniform control flow)
-    {
-      const uint64_t need = __ballot(t < 0);
-      if (need != 0 && S > 0) {
-        const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(need >> 32),
-                                                         __builtin_amdgcn_mbcnt_lo((uint32_t)need, 0u));
-        const int k = __popcll(need);
-        const int take = k < S ? k : S;
-        const int src = (head + (rank < take ? rank : 0)) & (kWave - 1);
-        // the staged task index with its point's estimate bit on top (tasks < 2^31): one shuffle
-        const uint32_t v_pk = (uint32_t)__shfl((int)(s_t | (s_ok ? 0x80000000u : 0u)), src);
-        const uint32_t v_t = v_pk & 0x7FFFFFFFu;
-        const uint32_t v_ok = v_pk >> 31;
-        float v_pt[DIM], v_thr = 0.0f, v_tsrc[NC], v_dd = 0.0f;
-        for (int c = 0; c < NC; c++) v_tsrc[c] = 0.0f;
-        if (t < 0 && rank < take && v_ok) {  // the task record from memory, at hand-out
-          for (int kk = 0; kk < DIM; kk++) v_pt[kk] = tk.pt[kk * tk.T + v_t];
-          v_thr = tk.thr[v_t];
-          if constexpr (NC == 1) {
-            v_tsrc[0] = tk.tsrc[v_t];
-          } else {
-            for (int c = 0; c < NC; c++)
-              if (c < sc.n_channels) v_tsrc[c] = tk.tsrc[(int64_t)c * tk.T + v_t];
-          }
-          // boundary-start walks (BVC) always carry a stored distance
-          v_dd = (BSTART || sc.n_dprims > 0) ? tk.dd[v_t] : bbox_far_dist<DIM>(sc, v_pt);
-        }
-        if (t < 0 && rank < take) {
-          t = (int64_t)v_t;
-          // BSTART: estimateSolution runs one walk only from inside the epsilon shell
-          // (walk_on_stars.h:383-386): the start kernel marks the others (sflags bit 1)
-          if (!v_ok || (BSTART && (tk.sflags[t] & 2u))) {  // point outside the domain: no walks
-            tk.code[t] = 0u;
-            t = -1;
-          } else {
-            const uint32_t pidx = divw(v_t);
-            const uint32_t w = (v_t - pidx * wpp) >> (prm.n_anti - 1);  // n_anti is 1 or 2
-            walk_start<DIM, BSTART, RB>(sc, prm, tk, t, pidx, w, v_pt, v_thr, v_tsrc, v_dd, base, stride, yuk0, st,
-                                        g, ws, ddist, wsteps, firstR);
-          }
-        }
-        head = (head + take) & (kWave - 1);
-        S -= take;
-#if WOS_TIMELINE
-        if (lane == 0) atomicAdd(&g_tl[1 + TL_START * kTlBins + tl_bin(tl_a)], (unsigned long long)take);
-#endif
-      }
-    }
-    if (__ballot(t >= 0) == 0) {
-      if (S == 0 && exhausted) {  // queue drained and every lane idle
-        if (!kSpread) break;
-        // idle: announce, then take a sibling's hand-over or leave once no wave holds walks
-        if (lane == 0) {
-          __hip_atomic_fetch_or(&s_spread.idle, 1u << wave_u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-          __hip_atomic_fetch_sub(&s_spread.busy, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-        }
-        uint32_t n = 0;
-        for (;;) {
-          n = __hip_atomic_load(&s_spread.mbox[wave_u], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP);
-          n = (uint32_t)__builtin_amdgcn_readfirstlane((int)n);
-          if (n != 0u) break;
-          const uint32_t busy = (uint32_t)__builtin_amdgcn_readfirstlane(
-              (int)__hip_atomic_load(&s_spread.busy, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP));
-          if (busy == 0u) break;
-          __builtin_amdgcn_s_sleep(4);
-        }
-        if (n == 0u) break;
-        // the hand-over: slot i of the mailbox (word-major, kSpreadMax slots) -> lane i
-        const uint32_t* mb = reinterpret_cast<const uint32_t*>(wscratch);
-        if ((uint32_t)lane < n) spread_get<DIM, RB>(mb, lane, st, g, ws, ddist, firstR, wsteps, t);
-        wave_sync();
-        if (lane == 0) __hip_atomic_store(&s_spread.mbox[wave_u], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        continue;
-      }
-      refill(tk);
-      continue;
-    }
-    DIAG_COUNT(D_ITERS, 1);
-    DIAG_COUNT(D_LANES, __popcll(__ballot(t >= 0)));
-#if WOS_DIAG
-    const bool lone_it = __popcll(__ballot(t >= 0)) <= 2;
-    if (lone_it) DIAG_COUNT(D_L_ITERS, 1);
-#endif
-    const int code = walk_iteration<DIM, GG, BSTART, RB, NEU>(sc, prm, G, t >= 0, st, g, ws, ddist, wsteps, firstR, starL,
-                                                         rayL, rejL, &c_iters, lane);
-#if WOS_TIMELINE
-    {
-      const unsigned long long nlive = (unsigned long long)__popcll(__ballot(t >= 0));
-      const unsigned long long nfin = (unsigned long long)__popcll(__ballot(t >= 0 && code >= 0));
-      const unsigned long long dt = __builtin_amdgcn_s_memrealtime() - tl_a;
-      if (lane == 0) {
-        const int b = tl_bin(tl_a);
-        atomicAdd(&g_tl[1 + TL_WAVE * kTlBins + b], dt);
-        atomicAdd(&g_tl[1 + TL_LANE * kTlBins + b], dt * nlive);
-        if (nfin) atomicAdd(&g_tl[1 + TL_FIN * kTlBins + b], nfin);
-      }
-    }
-#endif
-    if (t >= 0 && code >= 0) {
-      walk_finish<DIM>(sc, prm, tk, t, code, st, wsteps, s_ctr);
-      t = -1;
-    }
-    if (kSpread && exhausted && S == 0) {
-      const uint64_t live = __ballot(t >= 0);
-      const int k = __popcll(live);
-      if (k >= 2 && __builtin_amdgcn_readfirstlane(
-                        (int)__hip_atomic_load(&s_spread.idle, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) != 0) {
-        int to = -1;
-        if (lane == 0) {
-          uint32_t m = __hip_atomic_load(&s_spread.idle, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-          while (m != 0u) {
-            const uint32_t b = 1u << __builtin_ctz(m);
-            const uint32_t old =
-                __hip_atomic_fetch_and(&s_spread.idle, ~b, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_WORKGROUP);
-            if (old & b) {
-              // the recipient holds walks from here on: counted before it can see them
-              __hip_atomic_fetch_add(&s_spread.busy, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-              to = __builtin_ctz(b);
-              break;
-            }
-            m = old & ~b;
-          }
-        }
-        to = __builtin_amdgcn_readlane(to, 0);
-        if (to >= 0) {
-          // the upper half of the live walks (by lane rank), at most kSpreadMax
-          const int kd = (k / 2) < kSpreadMax ? (k / 2) : kSpreadMax;
-          const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(live >> 32),
-                                                         __builtin_amdgcn_mbcnt_lo((uint32_t)live, 0u));
-          const bool give = t >= 0 && rank >= k - kd;
-          uint32_t* mb = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(smem + geom_floats) +
-                                                     to * walk_scratch_bytes<DIM>());
-          if (give) {
-            spread_put<DIM, RB>(mb, rank - (k - kd), st, g, ws, ddist, firstR, wsteps, (uint32_t)t);
-            t = -1;
-          }
-          wave_sync();
-          if (lane == 0)
-            __hip_atomic_store(&s_spread.mbox[to], (uint32_t)kd, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-        }
-      }
-    }
-    refill(tk);
-#if WOS_DIAG
-    DIAG_ADD_LONE(D_LOOP, D_L_LOOP, t_loop, lone_it);
-#endif
-#if WOS_DIAG
-    if (exhausted) {
-      DIAG_COUNT(D_XITERS, 1);
-      DIAG_COUNT(D_XLANES, __popcll(__ballot(t >= 0)));
-      DIAG_ADD(D_XLOOP, t_loop);
-    }
-#endif
-  }
-  DIAG_MAX(D_WAVEMAX, __builtin_amdgcn_s_memtime() - t_wave);
-  flush_counter(counters, C_ITERS, c_iters, lane);
-  __syncthreads();
-#if WOS_DIAG
-  if (threadIdx.x < D_NUM) {
-    if (diag_is_max(threadIdx.x)) atomicMax(&g_diag[threadIdx.x], s_diag[threadIdx.x]);
-    else atomicAdd(&g_diag[threadIdx.x], s_diag[threadIdx.x]);
-  }
-#endif
-  flush_walk_counters(counters, s_ctr);
+  constexpr bool REC = false;
+  const DevTape* const tape = nullptr;
+#include "wos_walk_body.inc"
 }
 
 // One thread per point, kFoldPoints points per block.  The records of the

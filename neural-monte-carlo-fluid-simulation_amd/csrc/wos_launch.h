@@ -74,6 +74,28 @@ hipError_t launch_bvc_splat(const float* recs, int r0, int r1, int first, int la
                             float absorption, float radius_clamp, float reg, float* sol, float* grad, hipStream_t s);
 hipError_t launch_bvc_fill(float* recs, int64_t b0, int64_t b1, const float* bsol, const float* bdn,
                            const DevScene& sc, int ignore_neumann, hipStream_t s);
+// the walk tape (wos_tape.hip): the recording instantiations of the first-ball and walk kernels
+// (reference semantics, one channel, full Neumann term, no tail spreading; LDS or global
+// geometry), launched like the kernels they record with the tape's pointers beside the tasks
+hipError_t launch_first_balls_rec(int dim, const DevScene& sc, const DevParams& prm, const float* pts, int64_t n,
+                                  int64_t base, int64_t stride, const DevTasks& tk, const DevTape& tape,
+                                  unsigned long long* counters, unsigned int* work, int grid, size_t shmem,
+                                  int lhs_floats, hipStream_t s);
+hipError_t launch_walks_rec(int dim, bool geom_global, const DevScene& sc, const DevParams& prm, const DevTasks& tk,
+                            const DevTape& tape, int64_t base, int64_t stride, unsigned long long* counters,
+                            unsigned int* tqueue, int grid, size_t shmem, int geom_floats, hipStream_t s);
+// resident blocks per CU of the recording first-ball (which 0) / walk (which 1) kernel
+hipError_t occupancy_rec_blocks_per_cu(int dim, bool geom_global, int which, size_t shmem, int* blocks);
+// slot[0..T] from the codes of a plain walk pass; bsum: tape_slot_blocks(T) + 1 u64 of scratch,
+// bsum[tape_slot_blocks(T)] = slot[T] without the 32-bit truncation
+constexpr int64_t tape_slot_blocks(int64_t T) { return (T + 1 + 2047) / 2048; }
+hipError_t launch_tape_slots(const uint32_t* code, int64_t T, uint32_t* slot, unsigned long long* bsum, hipStream_t s);
+// out[0] += entries of the recorded walks, out[1] = max(out[1], entries of the longest)
+hipError_t launch_tape_stats(const uint32_t* code, const uint32_t* cnt, int64_t T, unsigned long long* out,
+                             hipStream_t s);
+// total / first [C][T] of the tape's walks for sc's current source (C = sc.n_channels)
+hipError_t launch_tape_replay(const DevTape& tape, const uint32_t* code, const DevScene& sc, int ignore_source,
+                              int64_t T, float* total, float* first, hipStream_t s);
 // planar [channels][cells] -> texels [cells][kMaxChannels] (channels beyond `channels`: +0)
 hipError_t launch_source_pack(const float* planar, float* texels, int64_t cells, int channels, hipStream_t s);
 }  // namespace wos

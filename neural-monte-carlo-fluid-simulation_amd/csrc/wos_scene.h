@@ -199,6 +199,27 @@ struct DevTasks {
   float* deriv;
 };
 
+// What a recording pass (wos_tape.hip) keeps of a batch's walks instead of their source-dependent
+// values, so that wos_tape_replay_kernel can redo totalSource and the walk total for any source
+// grid.  Per task [T]; entries SoA over the batch's entry slots.  Task t owns the slots
+// [slot[t], slot[t + 1]) (an exclusive scan of an upper bound of its entries, slot[T] = all).
+struct DevTape {
+  float* gnorm;          // [T] first ball: the Green's function norm of its source sample
+  uint32_t* cell0;       // [T] first ball: the source grid cell of its source sample
+  const uint32_t* slot;  // [T + 1] first entry slot of task t
+  uint32_t* cnt;         // [T] entries written | bit 31: Dirichlet end with the constant g (walk_finish own_g)
+  float* thr_end;        // [T] final throughput
+  float* term;           // [T] terminal contribution g (0 without one)
+  float* tneu;           // [T] totalNeumann
+  uint32_t* e_cell;      // [slots] source grid cell of a step's source sample, in step order
+  float* e_thr;          // [slots] throughput before the step (pThr)
+  float* e_nrm;          // [slots] Green's function norm of the step's ball (pNrm)
+  uint32_t* overflow;    // [1] set when a recorded walk had more entries than slots (the tape is discarded)
+};
+constexpr uint32_t kTapeOwnG = 0x80000000u;
+// entries the replay kernel stages per wave and pass (one per lane)
+constexpr int kTapeChunk = 64;
+
 // floats per task: start state pt[DIM] thr tsrc dd, record first bdir[DIM] sdir[DIM] total code;
 // every source channel beyond the first adds its own tsrc, first and total
 constexpr int task_floats(int dim, int channels = 1) { return 3 * dim + 6 + 3 * (channels - 1); }

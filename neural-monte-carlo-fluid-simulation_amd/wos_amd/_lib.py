@@ -97,6 +97,12 @@ class Stats(C.Structure):
         return {n: (float(getattr(self, n)) if t is C.c_double else int(getattr(self, n))) for n, t in self._fields_}
 
 
+class TapeInfo(C.Structure):
+    _fields_ = [("dim", C.c_int32), ("n_walks", C.c_int32), ("source_dims", C.c_int32 * 3), ("device", C.c_int32),
+                ("n_points", C.c_int64), ("n_tasks", C.c_int64), ("n_entries", C.c_int64),
+                ("max_entries_per_walk", C.c_int64), ("bytes", C.c_int64), ("replay_chunk_entries", C.c_int32)]
+
+
 # exported symbols, exactly those declared in include/wos.h
 EXPORTS = (
     "wos_load_obj", "wos_mesh_free", "wos_scene_create", "wos_scene_destroy",
@@ -104,6 +110,7 @@ EXPORTS = (
     "wos_solve_stats", "wos_default_bvc_params", "wos_bvc",
     "wos_selftest_math", "wos_selftest_lhs", "wos_selftest_lhs_permute", "wos_selftest_lhs_plan", "wos_last_error", "wos_abi_version", "wos_device_count", "wos_set_max_batch_tasks",
     "wos_scene_set_source_channels", "wos_scene_channels", "wos_solve_channels",
+    "wos_tape_record", "wos_tape_solve", "wos_tape_get_info", "wos_tape_destroy",
 )
 
 _lib = None
@@ -154,6 +161,16 @@ def load():
                                      C.c_void_p, C.c_void_p, C.POINTER(Stats), C.c_void_p, C.c_uint32]
     L.wos_solve_stats.restype = C.c_int
     L.wos_solve_stats.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(Stats)]
+    L.wos_tape_record.restype = C.c_int
+    L.wos_tape_record.argtypes = [C.c_void_p, C.POINTER(SolverParams), C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
+                                  C.c_int64, C.POINTER(C.c_void_p), C.POINTER(Stats), C.c_void_p, C.c_uint32]
+    L.wos_tape_solve.restype = C.c_int
+    L.wos_tape_solve.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.c_void_p, C.POINTER(Stats), C.c_void_p, C.c_uint32]
+    L.wos_tape_get_info.restype = C.c_int
+    L.wos_tape_get_info.argtypes = [C.c_void_p, C.POINTER(TapeInfo)]
+    L.wos_tape_destroy.restype = C.c_int
+    L.wos_tape_destroy.argtypes = [C.c_void_p]
     L.wos_default_bvc_params.restype = None
     L.wos_default_bvc_params.argtypes = [C.POINTER(BvcParams)]
     L.wos_bvc.restype = C.c_int

@@ -386,6 +386,33 @@ class WosScene:
             out = out + (ne, sp)
         return out
 
+    def record(self, pts, params=None, *, index_base=0, index_stride=1, max_bytes=None):
+        """Record the walks of solve(pts, params, index_base=..., index_stride=...) once
+        (wos_tape_record; blocking, about two solves).  The returned WalkTape replays them for
+        whatever source this scene holds later, bit for bit the full solve, at the cost of
+        streaming the tape.  max_bytes: refuse (WOS_E_CAPACITY) a tape larger than that."""
+        L = _lib.load()
+        params = params if params is not None else solver_params()
+        st = Stats()
+        on_dev = _is_torch(pts) and pts.is_cuda
+        if on_dev:
+            import torch
+            x = pts.detach().to(torch.float32).contiguous()
+            ptr, flags = x.data_ptr(), _lib.WOS_PTRS_DEVICE
+            stream = torch.cuda.current_stream(x.device).cuda_stream
+        else:
+            if _is_torch(pts):
+                pts = pts.detach().cpu().numpy()
+            x = np.ascontiguousarray(pts, dtype=np.float32)
+            ptr, flags, stream = x.ctypes.data, 0, None
+        if x.ndim != 2 or x.shape[1] != self.dim:
+            raise WosError(f"points must be [N,{self.dim}]")
+        h = C.c_void_p()
+        check(L.wos_tape_record(self._h, C.byref(params), ptr, x.shape[0], index_base, index_stride,
+                                int(max_bytes) if max_bytes is not None else 0, C.byref(h), C.byref(st), stream,
+                                flags), "wos_tape_record")
+        return WalkTape(self, h, x.shape[0], x.device if on_dev else None, st.as_dict())
+
     def bvc(self, params=None, bvc=None, samples=True):
         """Boundary value caching (wos_bvc; the reference's bvc, demo.cpp:265-363) on this
         2D scene (Neumann and Dirichlet boundaries).  Returns (solution [g, g], grad [g, g, 2],
@@ -432,6 +459,83 @@ class WosScene:
     def close(self):
         if getattr(self, "_h", None):
             _lib.load().wos_scene_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class WalkTape:
+    """The recorded walks of one (scene, params, points, indices): WosScene.record.  solve()
+    replays them for the scene's current source."""
+
+    def __init__(self, scene, handle, n, torch_device, record_stats):
+        self.scene = scene
+        self._h = handle
+        self._n = int(n)
+        self._torch_device = torch_device  # outputs follow the recorded points: torch-CUDA in, torch-CUDA out
+        self.record_stats = record_stats
+
+    @property
+    def info(self):
+        """wos_tape_info as a dict (bytes, n_entries, max_entries_per_walk, replay_chunk_entries, ...)."""
+        i = _lib.TapeInfo()
+        check(_lib.load().wos_tape_get_info(self._h, C.byref(i)), "wos_tape_get_info")
+        out = {n: getattr(i, n) for n, _ in i._fields_ if n != "source_dims"}
+        out["source_dims"] = list(i.source_dims)
+        return out
+
+    def solve(self, *, variance=False, counts=False, stream=None):
+        """The solve of the recorded points for the scene's current source (wos_tape_solve):
+        the tuple WosScene.solve(pts, params, variance=..., counts=...) would return now, bit
+        for bit, with the recorded walks' counters and this call's times in the stats dict."""
+        L = _lib.load()
+        sc = self.scene
+        st = Stats()
+        n, dim = self._n, sc.dim
+        nch = sc.channels
+        lead = (nch,) if sc._channel_axis else ()
+        if self._torch_device is not None:
+            import torch
+            dev = self._torch_device
+            p = torch.empty(lead + (n,), dtype=torch.float32, device=dev)
+            g = torch.empty(lead + (n, dim), dtype=torch.float32, device=dev)
+            ne = torch.empty(n, dtype=torch.int32, device=dev) if counts else None
+            sp = torch.empty(n, dtype=torch.int32, device=dev) if counts else None
+            pv = torch.empty(lead + (n,), dtype=torch.float32, device=dev) if variance else None
+            gv = torch.empty(lead + (n, dim), dtype=torch.float32, device=dev) if variance else None
+            cur = torch.cuda.current_stream(dev)
+            if stream is None:
+                s = cur.cuda_stream
+            else:
+                ts = stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.ExternalStream(int(stream),
+                                                                                                    device=dev)
+                s = ts.cuda_stream
+                ts.wait_stream(cur)  # the fresh output buffers belong to torch's current stream
+            ptr = lambda t: t.data_ptr() if t is not None else None
+            flags = _lib.WOS_PTRS_DEVICE
+        else:
+            p = np.empty(lead + (n,), np.float32)
+            g = np.empty(lead + (n, dim), np.float32)
+            ne = np.empty(n, np.int32) if counts else None
+            sp = np.empty(n, np.int32) if counts else None
+            pv = np.empty(lead + (n,), np.float32) if variance else None
+            gv = np.empty(lead + (n, dim), np.float32) if variance else None
+            ptr = lambda a: a.ctypes.data if a is not None else None
+            s, flags = stream, 0
+        check(L.wos_tape_solve(self._h, sc._h, nch, ptr(p), ptr(g), ptr(pv), ptr(gv), ptr(ne), ptr(sp), C.byref(st),
+                               s, flags), "wos_tape_solve")
+        out = (p, g, pv, gv, st.as_dict()) if variance else (p, g, st.as_dict())
+        if counts:
+            out = out + (ne, sp)
+        return out
+
+    def close(self):
+        if getattr(self, "_h", None):
+            _lib.load().wos_tape_destroy(self._h)
             self._h = None
 
     def __del__(self):

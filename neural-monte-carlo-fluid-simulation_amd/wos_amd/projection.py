@@ -127,10 +127,20 @@ class PressureProjector:
     over xGMI) hands every rank the full field -- bit-identical to a one-GPU solve, so
     projection_loss draws from it unchanged.  `force_gather` runs the collective even in
     a world of one.
+
+    reuse_walks=True: the walks do not depend on the source, so the first solve(div) records
+    this rank's walks (WosScene.record, at global indices with a group) and every later one
+    replays them for the new div (WalkTape.solve) -- outputs bit-identical to
+    reuse_walks=False at a fraction of the time.  The noise is frozen as the fixed seed already
+    freezes it; a div of another grid shape records anew.
     """
 
+    # class-level defaults: a subclass that builds its own scene keeps the plain path
+    reuse_walks = False
+    _tape, _tape_grid = None, None
+
     def __init__(self, scene_config, solver_config, output_config, pressure_samples, device=None,
-                 group=None, force_gather=False):
+                 group=None, force_gather=False, reuse_walks=False):
         import zombie_bindings  # the drop-in shim parses the reference's scene keys
         self.dim = int(pressure_samples.shape[-1])
         self.device = pressure_samples.device if device is None else torch.device(device)
@@ -140,6 +150,8 @@ class PressureProjector:
         self.samples = pressure_samples.detach().to(self.device, torch.float32).contiguous()
         self.group, self.force_gather = group, force_gather
         self.last_stats = None
+        self.reuse_walks = bool(reuse_walks)
+        self._tape, self._tape_grid = None, None
 
     def source_from_velocity(self, velocity_fn, resolution, size):
         """-div u on the reference's grid (get_divergence, model_split.py:230-236),
@@ -159,6 +171,17 @@ class PressureProjector:
         return self.scene._scene.solve(x, self.params, index_base=index_base, index_stride=index_stride,
                                        variance=True)
 
+    def _replay_points(self, x, index_base, index_stride, variance=False):
+        """_solve_points through the walk tape of (x, index_base, index_stride): recorded on first use."""
+        grid = tuple(self.scene._scene.source_shape[-self.dim:])
+        if self._tape is not None and self._tape_grid != grid:
+            self._tape.close()
+            self._tape = None
+        if self._tape is None:
+            self._tape = self.scene._scene.record(x, self.params, index_base=index_base, index_stride=index_stride)
+            self._tape_grid = grid
+        return self._tape.solve(variance=variance)
+
     def solve(self, div, variance=False):
         """wost_pressure (model_split.py:185-202) with device tensors in and out; with a
         process group, this rank's stride shard + one all-gather (wos_amd.dist).
@@ -169,8 +192,9 @@ class PressureProjector:
         (the variances alike) -- with a process group still through one all-gather."""
         self._set_source(div)
         kw = {"variance": True} if variance else {}
+        solve_points = self._replay_points if self.reuse_walks else self._solve_points
         if self.group is None and not self.force_gather:
-            *out, st = self._solve_points(self.samples, 0, 1, **kw)
+            *out, st = solve_points(self.samples, 0, 1, **kw)
             self.last_stats = st
             return tuple(out)
         import torch.distributed as tdist
@@ -179,7 +203,7 @@ class PressureProjector:
         rank, world = tdist.get_rank(group), tdist.get_world_size(group)
 
         def solve_local(local, base, stride):
-            *out, st = self._solve_points(local.contiguous(), base, stride, **kw)
+            *out, st = solve_points(local.contiguous(), base, stride, **kw)
             self.last_stats = st  # this rank's shard
             return tuple(out)
 
