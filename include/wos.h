@@ -352,6 +352,45 @@ int wos_tape_solve(wos_tape *tape, wos_scene *scene, int32_t n_channels,
 int wos_tape_get_info(const wos_tape *tape, wos_tape_info *info);
 int wos_tape_destroy(wos_tape *tape);
 
+/* ---- Walk tape adjoint: the gradient of a loss with respect to the source grid ------------
+ * wos_tape_solve is an affine map from the source grid to (p, grad p).  wos_tape_vjp applies
+ * its transpose: grad_source[c][cell] = sum_i grad_p[c][i] dp_i/df[cell]
+ * + sum_ik grad_grad[c][i][k] dg_ik/df[cell], on the recorded walks, for every channel on its own
+ * plane.  The map is affine, so the result depends neither on the scene's current source values
+ * nor on the channels' Dirichlet constants.  Upstream values of outputs the forward masks, and of
+ * points it does not estimate, are read as 0.  The sums are float atomics: two calls may differ in
+ * the last bits.  With ignoreSource recorded the result is exactly 0.
+ *
+ * wos_tape_vjp   grad_p [C][n] and grad_grad [C][n][dim] as wos_tape_solve lays out p and grad;
+ *                one of them may be NULL (zeros), both NULL is WOS_E_INVALID.  grad_source
+ *                [C][cells], planar in the layout wos_scene_set_source_channels takes, is
+ *                overwritten.  Scene, n_channels and source dims are checked as wos_tape_solve
+ *                checks them; a tape recorded with a null source is WOS_E_INVALID.  Pointers,
+ *                flags (WOS_PTRS_DEVICE, WOS_ASYNC), ticket and stream ordering as wos_tape_solve.
+ *                stats: the recorded walks' counters; kernel_ms this call's, fold_ms the adjoint
+ *                fold, walk_ms the scatter, walk_launches two per segment.
+ * wos_tape_read  blocking diagnostic copy-out of `count` elements from `offset` of one array of
+ *                one segment (one segment per recorded batch), so that the operator can be
+ *                restated on the host.  Elements are 4 bytes: float, or uint32 (code, cnt, slot,
+ *                cell0, cell) / int32 (pstate).  Per task [n_tasks of the segment]: code, cnt
+ *                (entries | bit 31), cell0, gnorm, thr_end, term, tneu; slot [n_tasks + 1]; bdir,
+ *                sdir [dim][n_tasks]; per entry slot [slot[n_tasks]]: cell, thr, nrm; per point:
+ *                pstate (bit 0 estimated, bit 1 p masked, bit 2 grad masked).
+ *                WOS_TAPE_SEGMENT_POINTS reads nothing from the device: dst receives one int64,
+ *                the segment's point count (offset 0, count 1).  A segment, field, offset or
+ *                count out of range is WOS_E_INVALID. */
+typedef enum wos_tape_field {
+    WOS_TAPE_CODE = 0, WOS_TAPE_CNT = 1, WOS_TAPE_SLOT = 2, WOS_TAPE_CELL0 = 3, WOS_TAPE_GNORM = 4,
+    WOS_TAPE_THR_END = 5, WOS_TAPE_TERM = 6, WOS_TAPE_TNEU = 7, WOS_TAPE_BDIR = 8, WOS_TAPE_SDIR = 9,
+    WOS_TAPE_E_CELL = 10, WOS_TAPE_E_THR = 11, WOS_TAPE_E_NRM = 12, WOS_TAPE_PSTATE = 13,
+    WOS_TAPE_SEGMENT_POINTS = 14
+} wos_tape_field;
+int wos_tape_vjp(wos_tape *tape, wos_scene *scene, int32_t n_channels,
+                 const float *grad_p, const float *grad_grad, float *grad_source,
+                 wos_stats *stats, void *stream, uint32_t flags);
+int wos_tape_read(const wos_tape *tape, int32_t segment, int32_t field, int64_t offset, int64_t count,
+                  void *dst);
+
 /* Device self-test of the deterministic math used by the kernel (for the
  * GPU-vs-oracle parity tests): which = 0 exp, 1 log, 2 sin, 3 cos, 4 atan,
  * 5 sqrt, 6 bessi0, 7 bessi1, 8 bessk0, 9 bessk1 (double); 10 expf, 11 logf,

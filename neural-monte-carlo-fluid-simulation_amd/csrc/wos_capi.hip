@@ -1800,6 +1800,167 @@ int wos_tape_solve(wos_tape* tape, wos_scene* s, int32_t n_channels, float* p, f
   return WOS_OK;
 }
 
+int wos_tape_vjp(wos_tape* tape, wos_scene* s, int32_t n_channels, const float* grad_p, const float* grad_grad,
+                 float* grad_source, wos_stats* stats, void* stream, uint32_t flags) {
+  if (!tape || !s) return fail(WOS_E_INVALID, "wos_tape_vjp: null tape/scene");
+  if (!grad_p && !grad_grad) return fail(WOS_E_INVALID, "wos_tape_vjp: both upstream gradients are null");
+  if (!grad_source) return fail(WOS_E_INVALID, "wos_tape_vjp: null output buffer");
+  const int64_t n = tape->n;
+  const int dim = tape->dim;
+  std::lock_guard<std::mutex> lock(s->mu);
+  if (s->serial != tape->scene_serial)
+    return fail(WOS_E_INVALID, "wos_tape_vjp: the tape was recorded on another scene");
+  if (n_channels != s->dev.n_channels)
+    return fail(WOS_E_INVALID, "wos_tape_vjp: n_channels " + std::to_string(n_channels) +
+                                   " differs from the scene's " + std::to_string(s->dev.n_channels));
+  if (tape->sdims[0] == 0)
+    return fail(WOS_E_INVALID, "wos_tape_vjp: the tape was recorded with a null source (no grid to differentiate)");
+  for (int k = 0; k < 3; k++)
+    if ((s->dev.source ? s->dev.sdims[k] : 0) != tape->sdims[k])
+      return fail(WOS_E_INVALID, "wos_tape_vjp: the scene's source dims differ from the recorded ones "
+                                 "(the tape stores grid cells)");
+  int64_t cells = 1;
+  for (int k = 0; k < dim; k++) cells *= tape->sdims[k];
+  if (cells < 1 || cells > 0xFFFFFFFFLL) return fail(WOS_E_INVALID, "wos_tape_vjp: source grid too large");
+  HIP_TRY(hipSetDevice(s->device));
+  DevCtx& c = g_ctx[s->device];
+  std::lock_guard<std::mutex> lk(c.mu);
+  {
+    int rc = ctx_ready(c, s->device);
+    if (rc != WOS_OK) return rc;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(ctx_order(c, st));  // the shared workspace
+  const int C = n_channels;
+  const bool dev_ptrs = (flags & WOS_PTRS_DEVICE) != 0;
+  const float* d_up = grad_p;
+  const float* d_ug = grad_grad;
+  float* d_out = grad_source;
+  DevBufs tmp;  // host pointers: the device copy of the result
+  if (!dev_ptrs) {
+    if (n > 0) {
+      int rc = ensure_workspace(c, dim, (size_t)n * C);
+      if (rc != WOS_OK) return rc;
+      if (grad_p) {
+        HIP_TRY(hipMemcpyAsync(c.d_p, grad_p, (size_t)n * C * sizeof(float), hipMemcpyHostToDevice, st));
+        d_up = c.d_p;
+      }
+      if (grad_grad) {
+        HIP_TRY(hipMemcpyAsync(c.d_g, grad_grad, (size_t)n * C * dim * sizeof(float), hipMemcpyHostToDevice, st));
+        d_ug = c.d_g;
+      }
+    }
+    HIP_TRY(tmp.get(&d_out, (size_t)cells * C));
+  }
+  // a / c [C][T]: the head of the task workspace, where the replay keeps total / first
+  int64_t maxT = 0;
+  for (const TapeSeg& g : tape->seg) maxT = std::max(maxT, g.T);
+  if (maxT > 0) {
+    int rc = ensure_tasks(c, dim, maxT, 0, C);
+    if (rc != WOS_OK) return rc;
+  }
+  const bool run = !tape->dp.ignore_source;  // ignoreSource: the map does not depend on the grid
+  const int64_t n_chunks = run ? (int64_t)tape->seg.size() : 0;
+  const uint64_t ticket = c.next_ticket++;
+  StatSlot& q = c.slot[ticket % kStatSlots];
+  while ((int64_t)q.bev.size() < 8 * n_chunks) {
+    hipEvent_t e = nullptr;
+    HIP_TRY(hipEventCreate(&e));
+    q.bev.push_back(e);
+  }
+  q.ticket = ticket;
+  q.n_batches = 2 * n_chunks;  // per segment: the adjoint fold (fold_ms), then the scatter (walk_ms)
+  q.bpc_fb = tape->bpc_fb;
+  q.bpc_walk = tape->bpc_walk;
+  q.walk_lds = tape->walk_lds;
+  q.star_grid = tape->star_grid;
+  q.geom_global = tape->geom_global;
+  q.dir_grid = tape->dir_grid;
+  HIP_TRY(hipEventRecord(q.ev0, st));
+  HIP_TRY(hipMemsetAsync(d_out, 0, (size_t)cells * C * sizeof(float), st));
+  int64_t b0 = 0;
+  for (int64_t k = 0; k < n_chunks; k++) {
+    const TapeSeg& g = tape->seg[(size_t)k];
+    hipEvent_t* ev = &q.bev[8 * k];
+    float* a = c.d_tasks;
+    float* cc = c.d_tasks + (int64_t)C * g.T;
+    for (int e = 0; e < 3; e++) HIP_TRY(hipEventRecord(ev[e], st));
+    HIP_TRY(wos::launch_tape_adjoint_fold(dim, tape->dp, g.code, g.bdir, g.sdir, g.pstate, g.nb, g.T, (int)tape->wpp, C,
+                                          d_up ? d_up + b0 : nullptr, d_ug ? d_ug + b0 * dim : nullptr, n, a, cc, st));
+    HIP_TRY(hipEventRecord(ev[3], st));
+    HIP_TRY(hipEventRecord(ev[4], st));
+    HIP_TRY(hipEventRecord(ev[5], st));
+    HIP_TRY(wos::launch_tape_scatter(g.tp, g.code, cells, C, g.T, a, cc, d_out, st));
+    HIP_TRY(hipEventRecord(ev[6], st));
+    HIP_TRY(hipEventRecord(ev[7], st));
+    b0 += g.nb;
+  }
+  HIP_TRY(hipEventRecord(q.ev1, st));
+  HIP_TRY(hipMemcpyAsync(q.h_cnt, tape->d_cnt, wos::kNumCounters * sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                         st));
+  if (!dev_ptrs)
+    HIP_TRY(hipMemcpyAsync(grad_source, d_out, (size_t)cells * C * sizeof(float), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipEventRecord(q.done, st));
+  HIP_TRY(hipEventRecord(c.done, st));
+  c.last_stream = st;
+  c.inflight = true;
+  if ((flags & WOS_ASYNC) && dev_ptrs) {
+    if (stats) {
+      *stats = wos_stats{};
+      stats->ticket = ticket;
+    }
+    return WOS_OK;
+  }
+  HIP_TRY(hipStreamSynchronize(st));
+  c.inflight = false;
+  if (stats) {
+    int rc = fill_stats(q, stats);
+    if (rc != WOS_OK) return rc;
+  }
+  return WOS_OK;
+}
+
+int wos_tape_read(const wos_tape* tape, int32_t segment, int32_t field, int64_t offset, int64_t count, void* dst) {
+  if (!tape || !dst) return fail(WOS_E_INVALID, "wos_tape_read: null argument");
+  if (segment < 0 || segment >= (int32_t)tape->seg.size())
+    return fail(WOS_E_INVALID, "wos_tape_read: segment " + std::to_string(segment) + " of " +
+                                   std::to_string(tape->seg.size()));
+  const TapeSeg& g = tape->seg[(size_t)segment];
+  const int64_t T = g.T, dim = tape->dim;
+  const void* src = nullptr;
+  int64_t len = 0;
+  switch (field) {
+    case WOS_TAPE_CODE: src = g.code; len = T; break;
+    case WOS_TAPE_CNT: src = g.tp.cnt; len = T; break;
+    case WOS_TAPE_SLOT: src = g.tp.slot; len = T + 1; break;
+    case WOS_TAPE_CELL0: src = g.tp.cell0; len = T; break;
+    case WOS_TAPE_GNORM: src = g.tp.gnorm; len = T; break;
+    case WOS_TAPE_THR_END: src = g.tp.thr_end; len = T; break;
+    case WOS_TAPE_TERM: src = g.tp.term; len = T; break;
+    case WOS_TAPE_TNEU: src = g.tp.tneu; len = T; break;
+    case WOS_TAPE_BDIR: src = g.bdir; len = dim * T; break;
+    case WOS_TAPE_SDIR: src = g.sdir; len = dim * T; break;
+    case WOS_TAPE_E_CELL: src = g.tp.e_cell; len = (int64_t)g.slots; break;
+    case WOS_TAPE_E_THR: src = g.tp.e_thr; len = (int64_t)g.slots; break;
+    case WOS_TAPE_E_NRM: src = g.tp.e_nrm; len = (int64_t)g.slots; break;
+    case WOS_TAPE_PSTATE: src = g.pstate; len = g.nb; break;
+    case WOS_TAPE_SEGMENT_POINTS: len = 1; break;
+    default: return fail(WOS_E_INVALID, "wos_tape_read: unknown field " + std::to_string(field));
+  }
+  if (offset < 0 || count < 0 || offset > len || count > len - offset)
+    return fail(WOS_E_INVALID, "wos_tape_read: [" + std::to_string(offset) + ", +" + std::to_string(count) +
+                                   ") is outside the field's " + std::to_string(len) + " elements");
+  if (field == WOS_TAPE_SEGMENT_POINTS) {
+    if (count == 1) *(int64_t*)dst = g.nb;
+    return WOS_OK;
+  }
+  if (count == 0) return WOS_OK;
+  HIP_TRY(hipSetDevice(tape->device));
+  // the tape is written once, by the blocking wos_tape_record
+  HIP_TRY(hipMemcpy(dst, (const char*)src + offset * 4, (size_t)count * 4, hipMemcpyDeviceToHost));
+  return WOS_OK;
+}
+
 int wos_tape_get_info(const wos_tape* tape, wos_tape_info* info) {
   if (!tape || !info) return fail(WOS_E_INVALID, "wos_tape_get_info: null argument");
   *info = wos_tape_info{};

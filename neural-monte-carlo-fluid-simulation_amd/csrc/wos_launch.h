@@ -96,6 +96,17 @@ hipError_t launch_tape_stats(const uint32_t* code, const uint32_t* cnt, int64_t 
 // total / first [C][T] of the tape's walks for sc's current source (C = sc.n_channels)
 hipError_t launch_tape_replay(const DevTape& tape, const uint32_t* code, const DevScene& sc, int ignore_source,
                               int64_t T, float* total, float* first, hipStream_t s);
+// the transpose of replay + fold (wos_tape_vjp).  launch_tape_adjoint_fold: a / c [C][T], the
+// derivatives of the loss by every walk's total and (first + total), from the upstream up_p
+// [C][up_stride] and up_g [C][up_stride][dim] (either may be null: zeros) of the segment's n
+// points; prm: the tape's recorded n_anti and use_cv.  launch_tape_scatter: out[C][cells] +=
+// the walks' a / c times the tape's factors (float atomics; the caller zeroes out).
+hipError_t launch_tape_adjoint_fold(int dim, const DevParams& prm, const uint32_t* code, const float* bdir,
+                                    const float* sdir, const int32_t* pstate, int64_t n, int64_t T, int wpp,
+                                    int n_channels, const float* up_p, const float* up_g, int64_t up_stride,
+                                    float* a, float* c, hipStream_t s);
+hipError_t launch_tape_scatter(const DevTape& tape, const uint32_t* code, int64_t cells, int n_channels, int64_t T,
+                               const float* a, const float* c, float* out, hipStream_t s);
 // planar [channels][cells] -> texels [cells][kMaxChannels] (channels beyond `channels`: +0)
 hipError_t launch_source_pack(const float* planar, float* texels, int64_t cells, int channels, hipStream_t s);
 }  // namespace wos

@@ -330,4 +330,254 @@ hipError_t launch_tape_replay(const DevTape& tape, const uint32_t* code, const D
   return hipGetLastError();
 }
 
+// ---- adjoint (wos_tape_vjp) ---------------------------------------------------------------
+// Replay + fold are an affine map from the source grid to (p, grad p); these two kernels apply its
+// transpose to an upstream (P, G).  With R the recorded records of a point, N = |R|, nb(j) the
+// recorded walks before j's pair and cvb_j / cvs_j the averages of total / first over them
+// (0 without control variates or with nb(j) = 0), the fold computes
+//   p   = (1/N) sum_R total_j
+//   g_k = (1/N) sum_R [(total_j - first_j - cvb_j) b_jk + (first_j - cvs_j) s_jk]
+// so with B_j = sum_k G_k b_jk, S_j = sum_k G_k s_jk:
+//   a_j = dL/dtotal_j          = (1/N) [P + B_j - cv sum_{r in R, pair(r) > pair(j)} B_r / nb(r)]
+//   c_j = dL/dfirst_j + a_j    = (1/N) [S_j - cv sum_{r in R, pair(r) > pair(j)} S_r / nb(r)] + (a_j - B_j / N)
+// (first enters total with weight 1), and the replay's transpose scatters
+//   out[cell0_j] += c_j gnorm_j,   out[cell_e] += a_j (thr_e nrm_e)  for every entry e of walk j.
+//
+// wos_tape_adjoint_fold_kernel: quad lane ch of point pp runs channel ch's sweep -- forward over
+// the codes for N, then backward over the records, pair by pair, carrying the two suffix sums.
+// code, bdir and sdir come through LDS in chunks of kAdjChunk records as in the fold, a and c
+// leave through LDS the same way.  The sums are kept in double and rounded once into a / c.
+constexpr int kAdjPoints = 32;  // points per 128-thread block
+constexpr int kAdjChunk = 16;
+
+template <int DIM>
+__global__ __launch_bounds__(4 * kAdjPoints) void wos_tape_adjoint_fold_kernel(
+    const uint32_t* __restrict__ code, const float* __restrict__ bdir, const float* __restrict__ sdir,
+    const int32_t* __restrict__ pstate, int64_t n, int64_t T, int wpp, int n_anti, int use_cv, int n_channels,
+    const float* __restrict__ up_p, const float* __restrict__ up_g, int64_t up_stride, float* __restrict__ a_out,
+    float* __restrict__ c_out) {
+  constexpr int NF = 1 + 2 * DIM;  // code | bdir[DIM] | sdir[DIM]
+  constexpr int CH = kAdjChunk, LD = CH + 1, NT = 4 * kAdjPoints;
+  __shared__ float lds[NF][kAdjPoints][LD];
+  __shared__ float s_out[2 * kMaxChannels][kAdjPoints][LD];
+  __shared__ int s_n[kAdjPoints];
+  const int tid = threadIdx.x;
+  const int ch = tid & 3, pp = tid >> 2;
+  const int64_t p0 = (int64_t)blockIdx.x * kAdjPoints;
+  const int nb = (int)((n - p0) < kAdjPoints ? (n - p0) : kAdjPoints);
+  const int64_t i = p0 + pp;
+  const int ps = pp < nb ? pstate[i] : 0;
+  const bool live = pp < nb && ch < n_channels && (ps & kPtEstimate) != 0;
+  // N: the block's tasks are contiguous, [p0 * wpp, (p0 + nb) * wpp)
+  if (tid < kAdjPoints) s_n[tid] = 0;
+  __syncthreads();
+  for (int e = tid; e < nb * wpp; e += NT)
+    if (code[p0 * wpp + e] & 1u) atomicAdd(&s_n[e / wpp], 1);
+  __syncthreads();
+  const int N = s_n[pp];
+  // upstream, read as 0 where the forward masks the output
+  double P = 0.0, G[DIM];
+  for (int k = 0; k < DIM; k++) G[k] = 0.0;
+  if (live && N > 0) {
+    if (up_p && !(ps & kPtMaskP)) P = (double)up_p[(int64_t)ch * up_stride + i];
+    if (up_g && !(ps & kPtMaskG))
+      for (int k = 0; k < DIM; k++) G[k] = (double)up_g[((int64_t)ch * up_stride + i) * DIM + k];
+  }
+  const double inv_n = N > 0 ? 1.0 / (double)N : 0.0;
+  double suf_b = 0.0, suf_s = 0.0;    // sum over the recorded walks of later pairs of B_r / nb(r), S_r / nb(r)
+  double pend_b = 0.0, pend_s = 0.0;  // the current pair's B_r, S_r
+  int pend_n = 0, after = 0;          // recorded walks of the current pair, of later pairs
+  const int last = ((wpp - 1) / CH) * CH;
+  for (int c0 = last; c0 >= 0; c0 -= CH) {
+    const int cnt = (wpp - c0) < CH ? (wpp - c0) : CH;
+    for (int e = tid; e < nb * CH; e += NT) {
+      const int q = e / CH, j = e - q * CH;
+      if (j >= cnt) continue;
+      const int64_t t = (p0 + q) * wpp + c0 + j;
+      lds[0][q][j] = __uint_as_float(code[t]);
+      for (int k = 0; k < DIM; k++) {
+        lds[1 + k][q][j] = bdir[k * T + t];
+        lds[1 + DIM + k][q][j] = sdir[k * T + t];
+      }
+    }
+    __syncthreads();
+    if (pp < nb && ch < n_channels) {
+      for (int j = cnt - 1; j >= 0; j--) {
+        float a = 0.0f, c = 0.0f;
+        if (live && N > 0 && (__float_as_uint(lds[0][pp][j]) & 1u)) {
+          double B = 0.0, S = 0.0;
+          for (int k = 0; k < DIM; k++) {
+            B += G[k] * (double)lds[1 + k][pp][j];
+            S += G[k] * (double)lds[1 + DIM + k][pp][j];
+          }
+          const double ad = inv_n * (P + B - suf_b);
+          a = (float)ad;
+          c = (float)(inv_n * (S - suf_s) + (ad - B * inv_n));
+          pend_b += B;
+          pend_s += S;
+          pend_n += 1;
+        }
+        s_out[ch][pp][j] = a;
+        s_out[kMaxChannels + ch][pp][j] = c;
+        if ((c0 + j) % n_anti == 0) {  // the pair is complete: it joins the suffix of the pairs before it
+          const int nbef = N - after - pend_n;
+          if (use_cv && nbef > 0) {
+            suf_b += pend_b / (double)nbef;
+            suf_s += pend_s / (double)nbef;
+          }
+          after += pend_n;
+          pend_b = 0.0; pend_s = 0.0; pend_n = 0;
+        }
+      }
+    }
+    __syncthreads();
+    for (int e = tid; e < nb * CH; e += NT) {
+      const int q = e / CH, j = e - q * CH;
+      if (j >= cnt) continue;
+      const int64_t t = (p0 + q) * wpp + c0 + j;
+      for (int cc = 0; cc < n_channels; cc++) {
+        a_out[(int64_t)cc * T + t] = s_out[cc][q][j];
+        c_out[(int64_t)cc * T + t] = s_out[kMaxChannels + cc][q][j];
+      }
+    }
+    // the next chunk's staging writes lds / s_out only after every thread has passed the barrier
+    // above and finished this copy-out of its own elements; its readers wait at the next barrier
+    __syncthreads();
+  }
+}
+
+template __global__ void wos_tape_adjoint_fold_kernel<2>(const uint32_t*, const float*, const float*, const int32_t*,
+                                                         int64_t, int64_t, int, int, int, int, const float*,
+                                                         const float*, int64_t, float*, float*);
+template __global__ void wos_tape_adjoint_fold_kernel<3>(const uint32_t*, const float*, const float*, const int32_t*,
+                                                         int64_t, int64_t, int, int, int, int, const float*,
+                                                         const float*, int64_t, float*, float*);
+
+hipError_t launch_tape_adjoint_fold(int dim, const DevParams& prm, const uint32_t* code, const float* bdir,
+                                    const float* sdir, const int32_t* pstate, int64_t n, int64_t T, int wpp,
+                                    int n_channels, const float* up_p, const float* up_g, int64_t up_stride,
+                                    float* a, float* c, hipStream_t s) {
+  if (n < 1) return hipSuccess;
+  if (n_channels < 1 || n_channels > kMaxChannels || (int64_t)kAdjPoints * wpp > 0x7FFFFFFFLL)
+    return hipErrorInvalidValue;
+  const int64_t grid = (n + kAdjPoints - 1) / kAdjPoints;
+  if (grid > 0x7FFFFFFFLL) return hipErrorInvalidValue;
+  const int use_cv = prm.use_cv ? 1 : 0;
+  if (dim == 2)
+    hipLaunchKernelGGL(wos_tape_adjoint_fold_kernel<2>, dim3((unsigned)grid), dim3(4 * kAdjPoints), 0, s, code, bdir,
+                       sdir, pstate, n, T, wpp, (int)prm.n_anti, use_cv, n_channels, up_p, up_g, up_stride, a, c);
+  else if (dim == 3)
+    hipLaunchKernelGGL(wos_tape_adjoint_fold_kernel<3>, dim3((unsigned)grid), dim3(4 * kAdjPoints), 0, s, code, bdir,
+                       sdir, pstate, n, T, wpp, (int)prm.n_anti, use_cv, n_channels, up_p, up_g, up_stride, a, c);
+  else
+    return hipErrorInvalidValue;
+  return hipGetLastError();
+}
+
+// wos_tape_scatter_kernel: the replay with the read turned into a write.  One lane per task, a
+// wave per 64 consecutive tasks, the wave's contiguous slot range in chunks of kTapeChunk.  Per
+// chunk every lane writes its walk's a into the LDS slots of its own entries (slots no walk
+// filled keep 0); then the lane that owns entry e loads cell, pThr and pNrm coalesced and adds
+// a * (pThr * pNrm) to out[channel][cell] with the hardware float atomic (global_atomic_add_f32,
+// no return value), runs of equal cells in adjacent lanes first summed in registers.  The
+// task's lane adds the first-ball term c * gnorm at cell0.  out is planar [C][cells], the
+// caller's layout.  The kernel is bound by the atomics' rate (19 - 20 G terms/s on B, C and D alike,
+// hot cells or not: profiles/tape_vjp_timing.jsonl); the run pre-combine bought 1 - 7 %.
+template <int NC>
+__global__ __launch_bounds__(kBlock) void wos_tape_scatter_kernel(const DevTape tp, const uint32_t* __restrict__ code,
+                                                                  uint32_t cells, int n_channels, int64_t T,
+                                                                  const float* __restrict__ a_in,
+                                                                  const float* __restrict__ c_in,
+                                                                  float* __restrict__ out) {
+  __shared__ float s_a[kBlock / kWave][kTapeChunk * NC];
+  const int lane = threadIdx.x & (kWave - 1);
+  const int wave = threadIdx.x / kWave;
+  const int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (t - lane >= T) return;  // the whole wave is beyond the tasks
+  const bool valid = t < T;
+  const uint32_t cd = valid ? code[t] : 0u;
+  const bool rec = (cd & 1u) != 0u;
+  const uint32_t s0 = valid ? tp.slot[t] : 0u;
+  const uint32_t cap = valid ? tp.slot[t + 1] - s0 : 0u;
+  uint32_t n = rec ? tp.cnt[t] & ~kTapeOwnG : 0u;
+  n = n < cap ? n : cap;
+  float a[NC];
+  for (int c = 0; c < NC; c++) a[c] = 0.0f;
+  if (rec) {
+    const float gnorm = tp.gnorm[t];
+    const uint32_t cell = tp.cell0[t];
+    for (int c = 0; c < NC; c++) {
+      if (c >= n_channels) break;
+      a[c] = a_in[(int64_t)c * T + t];
+      const float v = c_in[(int64_t)c * T + t] * gnorm;
+      if (cell < cells && v != 0.0f) unsafeAtomicAdd(&out[(size_t)c * cells + cell], v);
+    }
+  }
+  const uint32_t e0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)s0);
+  uint32_t e1 = rec ? s0 + n : e0;
+  for (int off = kWave / 2; off > 0; off >>= 1) {
+    const uint32_t o = (uint32_t)__shfl_xor((int)e1, off);
+    e1 = o > e1 ? o : e1;
+  }
+  for (uint32_t w0 = e0; w0 < e1; w0 += kTapeChunk) {
+    for (int c = 0; c < NC; c++) s_a[wave][lane * NC + c] = 0.0f;
+    wave_sync();
+    const uint32_t lo = s0 > w0 ? s0 : w0;
+    const uint32_t hi = s0 + n < w0 + kTapeChunk ? s0 + n : w0 + kTapeChunk;
+    for (uint32_t j = lo; j < hi; j++) {
+      const uint32_t k = j - w0;
+      for (int c = 0; c < NC; c++) s_a[wave][k * NC + c] = a[c];
+    }
+    wave_sync();
+    const uint32_t e = w0 + (uint32_t)lane;
+    // consecutive steps of a walk often sample the same cell: a run of equal cells in adjacent
+    // lanes is summed into its first lane (segmented suffix scan), one atomic per run
+    uint32_t cell = 0xFFFFFFFFu;
+    float v[NC];
+    for (int c = 0; c < NC; c++) v[c] = 0.0f;
+    if (e < e1) {
+      cell = tp.e_cell[e];
+      const float w = tp.e_thr[e] * tp.e_nrm[e];
+      for (int c = 0; c < NC; c++) v[c] = s_a[wave][lane * NC + c] * w;
+    }
+    const uint32_t prev = (uint32_t)__shfl_up((int)cell, 1);
+    const bool head = lane == 0 || prev != cell;
+    const unsigned long long heads = __ballot(head);
+    const int run = 63 - __builtin_clzll(heads & (~0ull >> (63 - lane)));  // the run's first lane
+    for (int off = 1; off < kWave; off <<= 1) {
+      const int orun = __shfl_down(run, off);
+      for (int c = 0; c < NC; c++) {
+        const float o = __shfl_down(v[c], off);
+        if (lane + off < kWave && orun == run) v[c] += o;
+      }
+    }
+    if (head && cell < cells)
+      for (int c = 0; c < NC; c++) {
+        if (c >= n_channels) break;
+        if (v[c] != 0.0f) unsafeAtomicAdd(&out[(size_t)c * cells + cell], v[c]);
+      }
+    wave_sync();
+  }
+}
+
+template __global__ void wos_tape_scatter_kernel<1>(const DevTape, const uint32_t*, uint32_t, int, int64_t, const float*,
+                                                    const float*, float*);
+template __global__ void wos_tape_scatter_kernel<kMaxChannels>(const DevTape, const uint32_t*, uint32_t, int, int64_t,
+                                                               const float*, const float*, float*);
+
+hipError_t launch_tape_scatter(const DevTape& tape, const uint32_t* code, int64_t cells, int n_channels, int64_t T,
+                               const float* a, const float* c, float* out, hipStream_t s) {
+  if (T < 1) return hipSuccess;
+  const int64_t grid = (T + kBlock - 1) / kBlock;
+  if (grid > 0x7FFFFFFFLL || cells < 1 || cells > 0xFFFFFFFFLL || n_channels < 1 || n_channels > kMaxChannels)
+    return hipErrorInvalidValue;
+  if (n_channels > 1)
+    hipLaunchKernelGGL(wos_tape_scatter_kernel<kMaxChannels>, dim3((unsigned)grid), dim3(kBlock), 0, s, tape, code,
+                       (uint32_t)cells, n_channels, T, a, c, out);
+  else
+    hipLaunchKernelGGL(wos_tape_scatter_kernel<1>, dim3((unsigned)grid), dim3(kBlock), 0, s, tape, code, (uint32_t)cells,
+                       1, T, a, c, out);
+  return hipGetLastError();
+}
+
 }  // namespace wos

@@ -111,7 +111,14 @@ EXPORTS = (
     "wos_selftest_math", "wos_selftest_lhs", "wos_selftest_lhs_permute", "wos_selftest_lhs_plan", "wos_last_error", "wos_abi_version", "wos_device_count", "wos_set_max_batch_tasks",
     "wos_scene_set_source_channels", "wos_scene_channels", "wos_solve_channels",
     "wos_tape_record", "wos_tape_solve", "wos_tape_get_info", "wos_tape_destroy",
+    "wos_tape_vjp", "wos_tape_read",
 )
+
+# wos_tape_field (include/wos.h): the arrays wos_tape_read copies out, with their element types
+TAPE_FIELDS = {"code": (0, "u4"), "cnt": (1, "u4"), "slot": (2, "u4"), "cell0": (3, "u4"), "gnorm": (4, "f4"),
+               "thr_end": (5, "f4"), "term": (6, "f4"), "tneu": (7, "f4"), "bdir": (8, "f4"), "sdir": (9, "f4"),
+               "cell": (10, "u4"), "thr": (11, "f4"), "nrm": (12, "f4"), "pstate": (13, "i4")}
+TAPE_SEGMENT_POINTS = 14
 
 _lib = None
 
@@ -171,6 +178,11 @@ def load():
     L.wos_tape_get_info.argtypes = [C.c_void_p, C.POINTER(TapeInfo)]
     L.wos_tape_destroy.restype = C.c_int
     L.wos_tape_destroy.argtypes = [C.c_void_p]
+    L.wos_tape_vjp.restype = C.c_int
+    L.wos_tape_vjp.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                               C.POINTER(Stats), C.c_void_p, C.c_uint32]
+    L.wos_tape_read.restype = C.c_int
+    L.wos_tape_read.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_void_p]
     L.wos_default_bvc_params.restype = None
     L.wos_default_bvc_params.argtypes = [C.POINTER(BvcParams)]
     L.wos_bvc.restype = C.c_int

@@ -533,6 +533,91 @@ class WalkTape:
             out = out + (ne, sp)
         return out
 
+    def vjp(self, grad_p=None, grad_grad=None, *, stream=None):
+        """The transpose of solve() applied to an upstream (wos_tape_vjp): the gradient with
+        respect to the scene's source grid of a loss whose derivatives by solve()'s p and grad
+        are grad_p and grad_grad (shaped like them; one may be None: zeros).  Returns an array
+        of the scene's source_shape -- numpy for numpy input, a torch-CUDA tensor for torch-CUDA
+        input.  It depends neither on the current source values nor on dirichlet_values;
+        upstream values of masked outputs and of points without an estimate are ignored.  The
+        sums are float atomics: two calls may differ in the last bits.  last_vjp_stats holds the
+        call's statistics (fold_ms: the adjoint fold, walk_ms: the scatter)."""
+        L = _lib.load()
+        sc = self.scene
+        if grad_p is None and grad_grad is None:
+            raise WosError("WalkTape.vjp: grad_p and grad_grad are both None")
+        n, dim = self._n, sc.dim
+        nch = sc.channels
+        lead = (nch,) if sc._channel_axis else ()
+        shapes = (lead + (n,), lead + (n, dim))
+        for u, shp, name in ((grad_p, shapes[0], "grad_p"), (grad_grad, shapes[1], "grad_grad")):
+            if u is not None and tuple(u.shape) != shp:
+                raise WosError(f"WalkTape.vjp: {name} must have shape {shp}, got {tuple(u.shape)}")
+        if sc.source_shape is None:
+            raise WosError("WalkTape.vjp: the scene has no source grid")
+        on_dev = any(_is_torch(u) and u.is_cuda for u in (grad_p, grad_grad))
+        st = Stats()
+        if on_dev:
+            import torch
+            dev = next(u.device for u in (grad_p, grad_grad) if _is_torch(u) and u.is_cuda)
+            up = [None if u is None else torch.as_tensor(u).detach().to(dev, torch.float32).contiguous()
+                  for u in (grad_p, grad_grad)]
+            out = torch.empty(sc.source_shape, dtype=torch.float32, device=dev)
+            cur = torch.cuda.current_stream(dev)
+            if stream is None:
+                s = cur.cuda_stream
+            else:
+                ts = stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.ExternalStream(int(stream),
+                                                                                                    device=dev)
+                s = ts.cuda_stream
+                ts.wait_stream(cur)  # the upstream and the fresh output belong to torch's current stream
+            ptr = lambda t: t.data_ptr() if t is not None else None
+            flags = _lib.WOS_PTRS_DEVICE
+        else:
+            up = [None if u is None else np.ascontiguousarray(u.detach().cpu().numpy() if _is_torch(u) else u,
+                                                              dtype=np.float32) for u in (grad_p, grad_grad)]
+            out = np.empty(sc.source_shape, np.float32)
+            ptr = lambda a: a.ctypes.data if a is not None else None
+            s, flags = stream, 0
+        check(L.wos_tape_vjp(self._h, sc._h, nch, ptr(up[0]), ptr(up[1]), ptr(out), C.byref(st), s, flags),
+              "wos_tape_vjp")
+        self.last_vjp_stats = st.as_dict()
+        return out
+
+    def read(self, field, segment=0):
+        """One array of one segment of the tape as numpy (wos_tape_read; one segment per recorded
+        batch): per task code, cnt, cell0, gnorm, thr_end, term, tneu [T], slot [T + 1], bdir,
+        sdir [dim, T]; per entry slot cell, thr, nrm [slot[T]]; per point pstate.  A diagnostic:
+        with it the replay, the fold and their transpose can be restated on the host."""
+        L = _lib.load()
+        if field not in _lib.TAPE_FIELDS:
+            raise WosError(f"WalkTape.read: unknown field {field!r} (one of {', '.join(_lib.TAPE_FIELDS)})")
+        fid, dtype = _lib.TAPE_FIELDS[field]
+        npts = np.zeros(1, np.int64)
+        check(L.wos_tape_read(self._h, segment, _lib.TAPE_SEGMENT_POINTS, 0, 1, npts.ctypes.data), "wos_tape_read")
+        info = self.info
+        T = int(npts[0]) * (info["n_tasks"] // max(1, info["n_points"]))
+        dim = info["dim"]
+        if field in ("cell", "thr", "nrm"):
+            last = np.zeros(1, np.uint32)
+            check(L.wos_tape_read(self._h, segment, _lib.TAPE_FIELDS["slot"][0], T, 1, last.ctypes.data), "wos_tape_read")
+            shape = (int(last[0]),)
+        else:
+            shape = {"slot": (T + 1,), "bdir": (dim, T), "sdir": (dim, T), "pstate": (int(npts[0]),)}.get(field, (T,))
+        out = np.empty(shape, dtype)
+        check(L.wos_tape_read(self._h, segment, fid, 0, out.size, out.ctypes.data), "wos_tape_read")
+        return out
+
+    @property
+    def segments(self):
+        """Point counts of the tape's segments (one per recorded batch), in order."""
+        L = _lib.load()
+        out, npts = [], np.zeros(1, np.int64)
+        while sum(out) < self._n:
+            check(L.wos_tape_read(self._h, len(out), _lib.TAPE_SEGMENT_POINTS, 0, 1, npts.ctypes.data), "wos_tape_read")
+            out.append(int(npts[0]))
+        return out
+
     def close(self):
         if getattr(self, "_h", None):
             _lib.load().wos_tape_destroy(self._h)

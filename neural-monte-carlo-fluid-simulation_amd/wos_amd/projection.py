@@ -110,6 +110,30 @@ def divergence(y, x, create_graph=False):
     return div
 
 
+class _TapeProjection(torch.autograd.Function):
+    """solve(div) of a PressureProjector with reuse_walks as a differentiable function of div:
+    forward is the source replacement plus the replay, backward the tape's transpose
+    (WalkTape.vjp).  The variance outputs are not differentiable."""
+
+    @staticmethod
+    def forward(ctx, div, proj, variance):
+        proj._set_source(div.detach())
+        *out, st = proj._replay_points(proj.samples, 0, 1, **({"variance": True} if variance else {}))
+        proj.last_stats = st
+        ctx.tape, ctx.shape, ctx.dtype = proj._tape, tuple(div.shape), div.dtype
+        if variance:
+            ctx.mark_non_differentiable(out[2], out[3])
+        return tuple(out)
+
+    @staticmethod
+    def backward(ctx, grad_p, grad_g, *unused):
+        if ctx.tape._h is None:
+            raise RuntimeError("the projector recorded a new tape (another source grid) before backward()")
+        if tuple(ctx.tape.scene.source_shape) != ctx.shape:
+            raise RuntimeError("the projector's source grid changed shape before backward()")
+        return ctx.tape.vjp(grad_p, grad_g).to(ctx.dtype), None, None
+
+
 class PressureProjector:
     """One scene for the whole simulation; each projection replaces its source in
     place and solves at the (device-resident) pressure samples.
@@ -133,6 +157,11 @@ class PressureProjector:
     replays them for the new div (WalkTape.solve) -- outputs bit-identical to
     reuse_walks=False at a fraction of the time.  The noise is frozen as the fixed seed already
     freezes it; a div of another grid shape records anew.
+
+    solve(div, differentiable=True) (reuse_walks=True, no group) returns p and grad_p attached to
+    div's autograd graph: backward applies the transpose of the recorded walks' affine map
+    (WalkTape.vjp), so a loss on p / grad_p reaches whatever produced div --
+    source_from_velocity(..., create_graph=True) keeps that graph down to the network's weights.
     """
 
     # class-level defaults: a subclass that builds its own scene keeps the plain path
@@ -153,12 +182,15 @@ class PressureProjector:
         self.reuse_walks = bool(reuse_walks)
         self._tape, self._tape_grid = None, None
 
-    def source_from_velocity(self, velocity_fn, resolution, size):
+    def source_from_velocity(self, velocity_fn, resolution, size, create_graph=False):
         """-div u on the reference's grid (get_divergence, model_split.py:230-236),
-        computed and kept on the device."""
+        computed and kept on the device.  create_graph=True keeps the autograd graph instead of
+        detaching, so a loss behind solve(div, differentiable=True) reaches velocity_fn's weights."""
         sampler = sample_uniform_2d if self.dim == 2 else sample_uniform_3d
         grid = sampler(resolution, size, with_boundary=True, device=self.device).requires_grad_(True)
         u = velocity_fn(grid)
+        if create_graph:
+            return (-divergence(u, grid, create_graph=True)[..., 0]).contiguous()
         div = divergence(u, grid)
         return (-div[..., 0]).detach().contiguous()
 
@@ -182,14 +214,24 @@ class PressureProjector:
             self._tape_grid = grid
         return self._tape.solve(variance=variance)
 
-    def solve(self, div, variance=False):
+    def solve(self, div, variance=False, differentiable=False):
         """wost_pressure (model_split.py:185-202) with device tensors in and out; with a
         process group, this rank's stride shard + one all-gather (wos_amd.dist).
         variance=True: (p, grad_p, p_var, grad_var) -- the per-walk sample variances of
         WosScene.solve(..., variance=True), gathered by the same collective.
         A `div` with a leading channel axis, (C, ...) with C <= 4, solves the C source fields
         on one set of walks and returns channel-major outputs, p [C, N] and grad_p [C, N, dim]
-        (the variances alike) -- with a process group still through one all-gather."""
+        (the variances alike) -- with a process group still through one all-gather.
+        differentiable=True: p and grad_p carry div's autograd graph (the variances do not);
+        needs reuse_walks=True and no process group."""
+        if differentiable:
+            if not self.reuse_walks:
+                raise ValueError("solve(differentiable=True) needs reuse_walks=True: the backward pass is the "
+                                 "walk tape's transpose")
+            if self.group is not None or self.force_gather:
+                raise ValueError("solve(differentiable=True) does not support a process group: the sharded "
+                                 "backward is not implemented")
+            return _TapeProjection.apply(div, self, bool(variance))
         self._set_source(div)
         kw = {"variance": True} if variance else {}
         solve_points = self._replay_points if self.reuse_walks else self._solve_points
