@@ -359,7 +359,8 @@ int wos_tape_destroy(wos_tape *tape);
  * plane.  The map is affine, so the result depends neither on the scene's current source values
  * nor on the channels' Dirichlet constants.  Upstream values of outputs the forward masks, and of
  * points it does not estimate, are read as 0.  The sums are float atomics: two calls may differ in
- * the last bits.  With ignoreSource recorded the result is exactly 0.
+ * the last bits (wos_tape_vjp_indexed below sums in a fixed order instead).  With ignoreSource
+ * recorded the result is exactly 0.
  *
  * wos_tape_vjp   grad_p [C][n] and grad_grad [C][n][dim] as wos_tape_solve lays out p and grad;
  *                one of them may be NULL (zeros), both NULL is WOS_E_INVALID.  grad_source
@@ -390,6 +391,53 @@ int wos_tape_vjp(wos_tape *tape, wos_scene *scene, int32_t n_channels,
                  wos_stats *stats, void *stream, uint32_t flags);
 int wos_tape_read(const wos_tape *tape, int32_t segment, int32_t field, int64_t offset, int64_t count,
                   void *dst);
+
+/* ---- Walk tape adjoint, indexed: the same gradient, bit for bit reproducible ---------------
+ * The terms wos_tape_vjp adds per segment, in their canonical order: first the first-ball terms
+ * (cell0[t], id = t | 0x80000000, w = gnorm[t]) of every recorded task t = 0 .. T - 1 with
+ * cell0[t] < cells, then the entry terms (cell[e], id = t, w = fl(thr[e] nrm[e])) of every filled
+ * slot e = 0 .. slot[T] - 1 with cell[e] < cells (filled: e in [slot[t], slot[t] + min(cnt[t]
+ * without bit 31, slot[t + 1] - slot[t])) of a recorded task t).  The index of a segment is this
+ * list stably sorted by cell: row offsets [cells + 1] and, per term, cell, id and w (12 bytes).
+ * Bit 31 of id selects c_j instead of a_j.  The tape owns one index per segment; it is a pure
+ * function of the tape.  wos_tape_vjp_indexed sums the terms of every cell in an order that
+ * depends on the row offsets and on tile_terms alone -- not on n_channels, the stream or
+ * timing -- without atomics, so two calls agree in every bit (csrc/wos_tape_index.hip states the
+ * order).  Segments are added in segment order: a tape recorded in other batches has another
+ * (equally fixed) order.
+ *
+ * wos_tape_index_build     blocking, idempotent (a second call returns WOS_OK and does nothing).
+ *                          max_bytes <= 0: no cap; else the cap of the call's peak device
+ *                          allocation, the index plus the sort's scratch: over it the call
+ *                          returns WOS_E_CAPACITY, keeps nothing and leaves the tape as it was.
+ *                          A tape recorded with a null source is WOS_E_INVALID, a grid of
+ *                          0xFFFFFFFF cells or more too.  With ignoreSource recorded the index is
+ *                          empty.  The index survives wos_release_caches; wos_tape_destroy frees
+ *                          it.  wos_tape_get_info's bytes do not count it.
+ * wos_tape_index_get_info  built 0 / 1; n_terms over all segments; max_terms_per_cell the longest
+ *                          row of any segment; bytes the index's device memory; tile_terms the
+ *                          tile constant of the sum (set whether built or not).
+ * wos_tape_index_read      blocking diagnostic copy-out as wos_tape_read's: row [n_cells + 1]
+ *                          uint32, cell and id [row[n_cells]] uint32, w float.  WOS_E_INVALID
+ *                          before the build.
+ * wos_tape_vjp_indexed     parameters, checks, pointers, flags, ticket and stats as wos_tape_vjp;
+ *                          fold_ms the adjoint fold, walk_ms the sum kernels.  WOS_E_INVALID if the
+ *                          index is not built. */
+typedef enum wos_tape_index_field {
+    WOS_TAPE_INDEX_ROW = 0, WOS_TAPE_INDEX_ID = 1, WOS_TAPE_INDEX_W = 2, WOS_TAPE_INDEX_CELL = 3
+} wos_tape_index_field;
+typedef struct wos_tape_index_info {
+    int32_t built, n_segments;
+    int64_t n_terms, n_cells, max_terms_per_cell, bytes;
+    int32_t tile_terms;
+} wos_tape_index_info;
+int wos_tape_index_build(wos_tape *tape, int64_t max_bytes);
+int wos_tape_index_get_info(const wos_tape *tape, wos_tape_index_info *info);
+int wos_tape_index_read(const wos_tape *tape, int32_t segment, int32_t field, int64_t offset, int64_t count,
+                        void *dst);
+int wos_tape_vjp_indexed(wos_tape *tape, wos_scene *scene, int32_t n_channels,
+                         const float *grad_p, const float *grad_grad, float *grad_source,
+                         wos_stats *stats, void *stream, uint32_t flags);
 
 /* Device self-test of the deterministic math used by the kernel (for the
  * GPU-vs-oracle parity tests): which = 0 exp, 1 log, 2 sin, 3 cos, 4 atan,
@@ -432,6 +480,15 @@ int wos_selftest_lhs(uint64_t key, const int64_t *gidx, int64_t n, int32_t n_pai
 int wos_selftest_lhs_permute(int32_t impl, const int32_t *partner, const float *values, int32_t nstrat,
                              int32_t sd, int32_t slots, int32_t count, float *out, int32_t device);
 int wos_selftest_lhs_plan(int32_t n_pairs, int32_t dim, int32_t *out);
+
+/* Device self-test of the indexed adjoint's sum kernels (csrc/wos_tape_index.hip) on a
+ * caller-supplied index, without a scene: row [n_rows + 1] (row[0] = 0, non-decreasing), id and
+ * w [row[n_rows]] (id & 0x7FFFFFFF < n_tasks; bit 31: take c), a and c [n_channels][n_tasks],
+ * n_channels 1 .. 4.  out [n_channels][n_rows] = the per-row sums, from zero;
+ * *tile_terms (may be NULL) = the tile constant.  Anything else is WOS_E_INVALID. */
+int wos_selftest_tape_rowsum(const uint32_t *row, int64_t n_rows, const uint32_t *id, const float *w,
+                             const float *a, const float *c, int64_t n_tasks, int32_t n_channels,
+                             float *out, int32_t *tile_terms, int32_t device);
 
 const char *wos_last_error(void);
 int32_t wos_abi_version(void);

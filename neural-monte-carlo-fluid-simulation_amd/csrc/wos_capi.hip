@@ -1430,6 +1430,20 @@ struct TapeSeg {
   int32_t* pstate = nullptr;
 };
 
+// a segment's cell-sorted index (wos_tape_index_build), one allocation:
+//   u32 row[cells + 1] cell[n_terms] id[n_terms]   float w[n_terms]   float part[tiles][2][kMaxChannels]
+struct TapeIndexSeg {
+  void* buf = nullptr;
+  wos::DevTapeIndex ix{};
+  int64_t bytes = 0, max_row = 0;
+};
+
+struct TapeIndex {
+  std::vector<TapeIndexSeg> seg;
+  int64_t bytes = 0, n_terms = 0, max_row = 0;
+  ~TapeIndex() { for (TapeIndexSeg& g : seg) hipFree(g.buf); }
+};
+
 struct wos_tape {
   int device = 0;
   std::shared_ptr<Geom> geom;  // kept alive: the tape outlives caches and, harmlessly, its scene
@@ -1443,8 +1457,10 @@ struct wos_tape {
   uint32_t* d_flag = nullptr;           // DevTape::overflow
   int64_t n_entries = 0, max_entries = 0, bytes = 0;
   int32_t bpc_fb = 0, bpc_walk = 0, walk_lds = 0, star_grid = 0, geom_global = 0, dir_grid = 0;
+  std::unique_ptr<TapeIndex> index;  // null until wos_tape_index_build
   ~wos_tape() {
     hipSetDevice(device);
+    index.reset();
     for (TapeSeg& g : seg) { hipFree(g.buf); hipFree(g.ebuf); }
     hipFree(d_cnt);
     hipFree(d_flag);
@@ -1800,31 +1816,36 @@ int wos_tape_solve(wos_tape* tape, wos_scene* s, int32_t n_channels, float* p, f
   return WOS_OK;
 }
 
-int wos_tape_vjp(wos_tape* tape, wos_scene* s, int32_t n_channels, const float* grad_p, const float* grad_grad,
-                 float* grad_source, wos_stats* stats, void* stream, uint32_t flags) {
-  if (!tape || !s) return fail(WOS_E_INVALID, "wos_tape_vjp: null tape/scene");
-  if (!grad_p && !grad_grad) return fail(WOS_E_INVALID, "wos_tape_vjp: both upstream gradients are null");
-  if (!grad_source) return fail(WOS_E_INVALID, "wos_tape_vjp: null output buffer");
+// wos_tape_vjp (indexed = false: the scatter's float atomics) and wos_tape_vjp_indexed (the index's
+// ordered sums) differ in the kernel that follows the adjoint fold; fn: the name errors carry
+static int tape_vjp(const std::string& fn, bool indexed, wos_tape* tape, wos_scene* s, int32_t n_channels,
+                    const float* grad_p, const float* grad_grad, float* grad_source, wos_stats* stats, void* stream,
+                    uint32_t flags) {
+  if (!tape || !s) return fail(WOS_E_INVALID, fn + ": null tape/scene");
+  if (!grad_p && !grad_grad) return fail(WOS_E_INVALID, fn + ": both upstream gradients are null");
+  if (!grad_source) return fail(WOS_E_INVALID, fn + ": null output buffer");
   const int64_t n = tape->n;
   const int dim = tape->dim;
   std::lock_guard<std::mutex> lock(s->mu);
   if (s->serial != tape->scene_serial)
-    return fail(WOS_E_INVALID, "wos_tape_vjp: the tape was recorded on another scene");
+    return fail(WOS_E_INVALID, fn + ": the tape was recorded on another scene");
   if (n_channels != s->dev.n_channels)
-    return fail(WOS_E_INVALID, "wos_tape_vjp: n_channels " + std::to_string(n_channels) +
+    return fail(WOS_E_INVALID, fn + ": n_channels " + std::to_string(n_channels) +
                                    " differs from the scene's " + std::to_string(s->dev.n_channels));
   if (tape->sdims[0] == 0)
-    return fail(WOS_E_INVALID, "wos_tape_vjp: the tape was recorded with a null source (no grid to differentiate)");
+    return fail(WOS_E_INVALID, fn + ": the tape was recorded with a null source (no grid to differentiate)");
   for (int k = 0; k < 3; k++)
     if ((s->dev.source ? s->dev.sdims[k] : 0) != tape->sdims[k])
-      return fail(WOS_E_INVALID, "wos_tape_vjp: the scene's source dims differ from the recorded ones "
+      return fail(WOS_E_INVALID, fn + ": the scene's source dims differ from the recorded ones "
                                  "(the tape stores grid cells)");
   int64_t cells = 1;
   for (int k = 0; k < dim; k++) cells *= tape->sdims[k];
-  if (cells < 1 || cells > 0xFFFFFFFFLL) return fail(WOS_E_INVALID, "wos_tape_vjp: source grid too large");
+  if (cells < 1 || cells > 0xFFFFFFFFLL) return fail(WOS_E_INVALID, fn + ": source grid too large");
   HIP_TRY(hipSetDevice(s->device));
   DevCtx& c = g_ctx[s->device];
   std::lock_guard<std::mutex> lk(c.mu);
+  if (indexed && !tape->index)
+    return fail(WOS_E_INVALID, fn + ": the tape has no index (wos_tape_index_build)");
   {
     int rc = ctx_ready(c, s->device);
     if (rc != WOS_OK) return rc;
@@ -1869,7 +1890,7 @@ int wos_tape_vjp(wos_tape* tape, wos_scene* s, int32_t n_channels, const float* 
     q.bev.push_back(e);
   }
   q.ticket = ticket;
-  q.n_batches = 2 * n_chunks;  // per segment: the adjoint fold (fold_ms), then the scatter (walk_ms)
+  q.n_batches = 2 * n_chunks;  // per segment: the adjoint fold (fold_ms), then the scatter or the sum (walk_ms)
   q.bpc_fb = tape->bpc_fb;
   q.bpc_walk = tape->bpc_walk;
   q.walk_lds = tape->walk_lds;
@@ -1890,7 +1911,10 @@ int wos_tape_vjp(wos_tape* tape, wos_scene* s, int32_t n_channels, const float* 
     HIP_TRY(hipEventRecord(ev[3], st));
     HIP_TRY(hipEventRecord(ev[4], st));
     HIP_TRY(hipEventRecord(ev[5], st));
-    HIP_TRY(wos::launch_tape_scatter(g.tp, g.code, cells, C, g.T, a, cc, d_out, st));
+    if (indexed)
+      HIP_TRY(wos::launch_tape_rowsum(tape->index->seg[(size_t)k].ix, cells, C, g.T, a, cc, d_out, st));
+    else
+      HIP_TRY(wos::launch_tape_scatter(g.tp, g.code, cells, C, g.T, a, cc, d_out, st));
     HIP_TRY(hipEventRecord(ev[6], st));
     HIP_TRY(hipEventRecord(ev[7], st));
     b0 += g.nb;
@@ -1918,6 +1942,17 @@ int wos_tape_vjp(wos_tape* tape, wos_scene* s, int32_t n_channels, const float* 
     if (rc != WOS_OK) return rc;
   }
   return WOS_OK;
+}
+
+int wos_tape_vjp(wos_tape* tape, wos_scene* s, int32_t n_channels, const float* grad_p, const float* grad_grad,
+                 float* grad_source, wos_stats* stats, void* stream, uint32_t flags) {
+  return tape_vjp("wos_tape_vjp", false, tape, s, n_channels, grad_p, grad_grad, grad_source, stats, stream, flags);
+}
+
+int wos_tape_vjp_indexed(wos_tape* tape, wos_scene* s, int32_t n_channels, const float* grad_p,
+                         const float* grad_grad, float* grad_source, wos_stats* stats, void* stream, uint32_t flags) {
+  return tape_vjp("wos_tape_vjp_indexed", true, tape, s, n_channels, grad_p, grad_grad, grad_source, stats, stream,
+                  flags);
 }
 
 int wos_tape_read(const wos_tape* tape, int32_t segment, int32_t field, int64_t offset, int64_t count, void* dst) {
@@ -1974,6 +2009,132 @@ int wos_tape_get_info(const wos_tape* tape, wos_tape_info* info) {
   info->max_entries_per_walk = tape->max_entries;
   info->bytes = tape->bytes;
   info->replay_chunk_entries = wos::kTapeChunk;
+  return WOS_OK;
+}
+
+static int64_t tape_cells(const wos_tape* tape) {
+  int64_t cells = 1;
+  for (int k = 0; k < tape->dim; k++) cells *= tape->sdims[k];
+  return cells;
+}
+
+int wos_tape_index_build(wos_tape* tape, int64_t max_bytes) {
+  if (!tape) return fail(WOS_E_INVALID, "wos_tape_index_build: null tape");
+  if (tape->sdims[0] == 0)
+    return fail(WOS_E_INVALID, "wos_tape_index_build: the tape was recorded with a null source (no grid to index)");
+  const int64_t cells = tape_cells(tape);
+  if (cells < 1 || cells >= 0xFFFFFFFFLL) return fail(WOS_E_INVALID, "wos_tape_index_build: source grid too large");
+  HIP_TRY(hipSetDevice(tape->device));
+  DevCtx& c = g_ctx[tape->device];
+  std::lock_guard<std::mutex> lk(c.mu);
+  if (tape->index) return WOS_OK;
+  int bits = 1;  // of the keys 0 .. cells - 1; the absent key's low bits, all ones, sort behind them
+  while ((1ull << bits) < (uint64_t)cells + 1) bits++;
+  const hipStream_t st = nullptr;
+  std::unique_ptr<TapeIndex> index(new TapeIndex());
+  auto over_cap = [&](int64_t need) {
+    return fail(WOS_E_CAPACITY, "wos_tape_index_build: the index and its sort need more than " + std::to_string(need) +
+                                    " bytes, max_bytes is " + std::to_string(max_bytes));
+  };
+  for (const TapeSeg& g : tape->seg) {
+    // with ignoreSource recorded no term depends on the grid: an empty index
+    const int64_t N = tape->dp.ignore_source ? 0 : g.T + (int64_t)g.slots;
+    if (N >= 0xFFFFFFFFLL)
+      return fail(WOS_E_CAPACITY, "wos_tape_index_build: a segment of " + std::to_string(N) +
+                                      " terms (at most 2^32 - 2); record in smaller batches (wos_set_max_batch_tasks)");
+    DevBufs tmp;  // the sort's scratch
+    uint32_t *key_in = nullptr, *key_out = nullptr, *d_terms = nullptr;
+    unsigned long long *val_in = nullptr, *val_out = nullptr;
+    char* sort_tmp = nullptr;
+    size_t sort_bytes = 0;
+    uint32_t n_terms = 0;
+    int64_t scratch = 0;
+    if (N > 0) {
+      HIP_TRY(wos::tape_index_sort(nullptr, &sort_bytes, key_in, key_out, val_in, val_out, N, bits, st));
+      scratch = N * 24 + (int64_t)sort_bytes + 4;
+      if (max_bytes > 0 && index->bytes + scratch + (cells + 1) * 4 > max_bytes)
+        return over_cap(index->bytes + scratch + (cells + 1) * 4);
+      HIP_TRY(tmp.get(&key_in, (size_t)N));
+      HIP_TRY(tmp.get(&key_out, (size_t)N));
+      HIP_TRY(tmp.get(&val_in, (size_t)N));
+      HIP_TRY(tmp.get(&val_out, (size_t)N));
+      HIP_TRY(tmp.get(&sort_tmp, sort_bytes));
+      HIP_TRY(tmp.get(&d_terms, 1));
+      HIP_TRY(wos::launch_tape_index_enum(g.tp, g.code, g.T, (int64_t)g.slots, cells, key_in, val_in, st));
+      HIP_TRY(wos::tape_index_sort(sort_tmp, &sort_bytes, key_in, key_out, val_in, val_out, N, bits, st));
+      HIP_TRY(wos::launch_tape_index_count(key_out, N, d_terms, st));
+      HIP_TRY(hipMemcpyAsync(&n_terms, d_terms, sizeof(n_terms), hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));
+    }
+    const int64_t tiles = wos::tape_index_tiles(n_terms);
+    const int64_t bytes = ((cells + 1) + 3 * (int64_t)n_terms + tiles * 2 * wos::kMaxChannels) * 4;
+    if (max_bytes > 0 && index->bytes + scratch + bytes > max_bytes) return over_cap(index->bytes + scratch + bytes);
+    index->seg.emplace_back();
+    TapeIndexSeg& x = index->seg.back();
+    HIP_TRY(hipMalloc(&x.buf, (size_t)bytes));
+    x.bytes = bytes;
+    index->bytes += bytes;
+    uint32_t* u = (uint32_t*)x.buf;
+    uint32_t* row = u; u += cells + 1;
+    uint32_t* cell = u; u += n_terms;
+    uint32_t* id = u; u += n_terms;
+    float* w = (float*)u; u += n_terms;
+    x.ix = wos::DevTapeIndex{row, cell, id, w, (float*)u, n_terms};
+    if (n_terms > 0)
+      HIP_TRY(wos::launch_tape_index_finish(key_out, val_out, n_terms, cells, row, cell, id, w, st));
+    else
+      HIP_TRY(hipMemsetAsync(row, 0, (size_t)(cells + 1) * 4, st));
+    std::vector<uint32_t> h_row((size_t)cells + 1);
+    HIP_TRY(hipMemcpyAsync(h_row.data(), row, h_row.size() * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (int64_t r = 0; r < cells; r++) x.max_row = std::max<int64_t>(x.max_row, (int64_t)h_row[r + 1] - h_row[r]);
+    index->n_terms += n_terms;
+    index->max_row = std::max(index->max_row, x.max_row);
+  }
+  tape->index = std::move(index);
+  return WOS_OK;
+}
+
+int wos_tape_index_get_info(const wos_tape* tape, wos_tape_index_info* info) {
+  if (!tape || !info) return fail(WOS_E_INVALID, "wos_tape_index_get_info: null argument");
+  *info = wos_tape_index_info{};
+  info->n_cells = tape->sdims[0] == 0 ? 0 : tape_cells(tape);
+  info->tile_terms = wos::kTapeIndexTile;
+  std::lock_guard<std::mutex> lk(g_ctx[tape->device].mu);
+  if (!tape->index) return WOS_OK;
+  info->built = 1;
+  info->n_segments = (int32_t)tape->index->seg.size();
+  info->n_terms = tape->index->n_terms;
+  info->max_terms_per_cell = tape->index->max_row;
+  info->bytes = tape->index->bytes;
+  return WOS_OK;
+}
+
+int wos_tape_index_read(const wos_tape* tape, int32_t segment, int32_t field, int64_t offset, int64_t count,
+                        void* dst) {
+  if (!tape || !dst) return fail(WOS_E_INVALID, "wos_tape_index_read: null argument");
+  std::lock_guard<std::mutex> lk(g_ctx[tape->device].mu);
+  if (!tape->index) return fail(WOS_E_INVALID, "wos_tape_index_read: the tape has no index (wos_tape_index_build)");
+  if (segment < 0 || segment >= (int32_t)tape->index->seg.size())
+    return fail(WOS_E_INVALID, "wos_tape_index_read: segment " + std::to_string(segment) + " of " +
+                                   std::to_string(tape->index->seg.size()));
+  const wos::DevTapeIndex& ix = tape->index->seg[(size_t)segment].ix;
+  const void* src = nullptr;
+  int64_t len = ix.n_terms;
+  switch (field) {
+    case WOS_TAPE_INDEX_ROW: src = ix.row; len = tape_cells(tape) + 1; break;
+    case WOS_TAPE_INDEX_ID: src = ix.id; break;
+    case WOS_TAPE_INDEX_W: src = ix.w; break;
+    case WOS_TAPE_INDEX_CELL: src = ix.cell; break;
+    default: return fail(WOS_E_INVALID, "wos_tape_index_read: unknown field " + std::to_string(field));
+  }
+  if (offset < 0 || count < 0 || offset > len || count > len - offset)
+    return fail(WOS_E_INVALID, "wos_tape_index_read: [" + std::to_string(offset) + ", +" + std::to_string(count) +
+                                   ") is outside the field's " + std::to_string(len) + " elements");
+  if (count == 0) return WOS_OK;
+  HIP_TRY(hipSetDevice(tape->device));
+  // the index is written once, by the blocking wos_tape_index_build
+  HIP_TRY(hipMemcpy(dst, (const char*)src + offset * 4, (size_t)count * 4, hipMemcpyDeviceToHost));
   return WOS_OK;
 }
 
@@ -2546,6 +2707,52 @@ int wos_selftest_lhs_plan(int32_t n_pairs, int32_t dim, int32_t* out) {
     return fail(WOS_E_INVALID, "wos_selftest_lhs_plan: bad argument");
   wos::lhs_plan(n_pairs, dim, out);
   out[6] = (int32_t)kLdsDynamicMax;
+  return WOS_OK;
+}
+
+int wos_selftest_tape_rowsum(const uint32_t* row, int64_t n_rows, const uint32_t* id, const float* w, const float* a,
+                             const float* c, int64_t n_tasks, int32_t n_channels, float* out, int32_t* tile_terms,
+                             int32_t device) {
+  if (tile_terms) *tile_terms = wos::kTapeIndexTile;
+  if (!row || !id || !w || !a || !c || !out) return fail(WOS_E_INVALID, "wos_selftest_tape_rowsum: null argument");
+  if (n_rows < 1 || n_rows >= 0xFFFFFFFFLL || n_tasks < 1 || n_tasks > (1LL << 30) || n_channels < 1 ||
+      n_channels > wos::kMaxChannels || row[0] != 0)
+    return fail(WOS_E_INVALID, "wos_selftest_tape_rowsum: bad argument");
+  for (int64_t r = 0; r < n_rows; r++)
+    if (row[r + 1] < row[r]) return fail(WOS_E_INVALID, "wos_selftest_tape_rowsum: row offsets decrease at " + std::to_string(r));
+  const uint32_t n_terms = row[n_rows];
+  std::vector<uint32_t> cell(n_terms);
+  for (int64_t r = 0; r < n_rows; r++)
+    for (uint32_t i = row[r]; i < row[r + 1]; i++) cell[i] = (uint32_t)r;
+  for (uint32_t i = 0; i < n_terms; i++)
+    if ((int64_t)(id[i] & 0x7FFFFFFFu) >= n_tasks)
+      return fail(WOS_E_INVALID, "wos_selftest_tape_rowsum: id out of range at " + std::to_string(i));
+  HIP_TRY(hipSetDevice(device));
+  DevBufs tmp;
+  uint32_t *d_row = nullptr, *d_cell = nullptr, *d_id = nullptr;
+  float *d_w = nullptr, *d_part = nullptr, *d_a = nullptr, *d_c = nullptr, *d_out = nullptr;
+  const size_t ct = (size_t)n_channels * n_tasks, co = (size_t)n_channels * n_rows;
+  HIP_TRY(tmp.get(&d_row, (size_t)n_rows + 1));
+  HIP_TRY(tmp.get(&d_cell, n_terms));
+  HIP_TRY(tmp.get(&d_id, n_terms));
+  HIP_TRY(tmp.get(&d_w, n_terms));
+  HIP_TRY(tmp.get(&d_part, (size_t)wos::tape_index_tiles(n_terms) * 2 * wos::kMaxChannels));
+  HIP_TRY(tmp.get(&d_a, ct));
+  HIP_TRY(tmp.get(&d_c, ct));
+  HIP_TRY(tmp.get(&d_out, co));
+  HIP_TRY(hipMemcpy(d_row, row, ((size_t)n_rows + 1) * 4, hipMemcpyHostToDevice));
+  if (n_terms > 0) {
+    HIP_TRY(hipMemcpy(d_cell, cell.data(), (size_t)n_terms * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_id, id, (size_t)n_terms * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_w, w, (size_t)n_terms * 4, hipMemcpyHostToDevice));
+  }
+  HIP_TRY(hipMemcpy(d_a, a, ct * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_c, c, ct * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemset(d_out, 0, co * 4));
+  const wos::DevTapeIndex ix{d_row, d_cell, d_id, d_w, d_part, n_terms};
+  HIP_TRY(wos::launch_tape_rowsum(ix, n_rows, n_channels, n_tasks, d_a, d_c, d_out, nullptr));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(out, d_out, co * 4, hipMemcpyDeviceToHost));
   return WOS_OK;
 }
 

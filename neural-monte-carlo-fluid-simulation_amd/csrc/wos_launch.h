@@ -107,6 +107,35 @@ hipError_t launch_tape_adjoint_fold(int dim, const DevParams& prm, const uint32_
                                     float* a, float* c, hipStream_t s);
 hipError_t launch_tape_scatter(const DevTape& tape, const uint32_t* code, int64_t cells, int n_channels, int64_t T,
                                const float* a, const float* c, float* out, hipStream_t s);
+// the tape's cell-sorted index and the atomic-free sum over it (wos_tape_index.hip).  A segment's
+// terms sorted stably by cell: row [cells + 1] offsets, per term cell, id (task | bit 31: c, not a)
+// and w -- 12 bytes a term; part [tape_index_tiles][2][kMaxChannels]: the sums of the rows that
+// cross the tiles of kTapeIndexTile terms, rewritten by every launch_tape_rowsum.
+constexpr int kTapeIndexTile = 1024;
+struct DevTapeIndex {
+  const uint32_t* row;
+  const uint32_t* cell;
+  const uint32_t* id;
+  const float* w;
+  float* part;
+  uint32_t n_terms;
+};
+constexpr int64_t tape_index_tiles(int64_t n_terms) { return (n_terms + kTapeIndexTile - 1) / kTapeIndexTile; }
+// key / val [T + slots]: the canonical enumeration (absent terms: key 0xFFFFFFFF)
+hipError_t launch_tape_index_enum(const DevTape& tape, const uint32_t* code, int64_t T, int64_t slots, int64_t cells,
+                                  uint32_t* key, unsigned long long* val, hipStream_t s);
+// stable sort by the keys' low `bits` bits; temp == nullptr: *temp_bytes = the scratch it needs
+hipError_t tape_index_sort(void* temp, size_t* temp_bytes, const uint32_t* key_in, uint32_t* key_out,
+                           const unsigned long long* val_in, unsigned long long* val_out, int64_t N, int bits,
+                           hipStream_t s);
+// *n_terms = the sorted keys before the first absent one
+hipError_t launch_tape_index_count(const uint32_t* key, int64_t N, uint32_t* n_terms, hipStream_t s);
+hipError_t launch_tape_index_finish(const uint32_t* key, const unsigned long long* val, uint32_t n_terms,
+                                    int64_t cells, uint32_t* row, uint32_t* cell, uint32_t* id, float* w,
+                                    hipStream_t s);
+// out[C][cells] = out + the segment's per-cell sums of a / c [C][T] times w, in the index's order
+hipError_t launch_tape_rowsum(const DevTapeIndex& ix, int64_t cells, int n_channels, int64_t T, const float* a,
+                              const float* c, float* out, hipStream_t s);
 // planar [channels][cells] -> texels [cells][kMaxChannels] (channels beyond `channels`: +0)
 hipError_t launch_source_pack(const float* planar, float* texels, int64_t cells, int channels, hipStream_t s);
 }  // namespace wos

@@ -103,6 +103,11 @@ class TapeInfo(C.Structure):
                 ("max_entries_per_walk", C.c_int64), ("bytes", C.c_int64), ("replay_chunk_entries", C.c_int32)]
 
 
+class TapeIndexInfo(C.Structure):
+    _fields_ = [("built", C.c_int32), ("n_segments", C.c_int32), ("n_terms", C.c_int64), ("n_cells", C.c_int64),
+                ("max_terms_per_cell", C.c_int64), ("bytes", C.c_int64), ("tile_terms", C.c_int32)]
+
+
 # exported symbols, exactly those declared in include/wos.h
 EXPORTS = (
     "wos_load_obj", "wos_mesh_free", "wos_scene_create", "wos_scene_destroy",
@@ -112,6 +117,8 @@ EXPORTS = (
     "wos_scene_set_source_channels", "wos_scene_channels", "wos_solve_channels",
     "wos_tape_record", "wos_tape_solve", "wos_tape_get_info", "wos_tape_destroy",
     "wos_tape_vjp", "wos_tape_read",
+    "wos_tape_index_build", "wos_tape_index_get_info", "wos_tape_index_read", "wos_tape_vjp_indexed",
+    "wos_selftest_tape_rowsum",
 )
 
 # wos_tape_field (include/wos.h): the arrays wos_tape_read copies out, with their element types
@@ -119,6 +126,8 @@ TAPE_FIELDS = {"code": (0, "u4"), "cnt": (1, "u4"), "slot": (2, "u4"), "cell0": 
                "thr_end": (5, "f4"), "term": (6, "f4"), "tneu": (7, "f4"), "bdir": (8, "f4"), "sdir": (9, "f4"),
                "cell": (10, "u4"), "thr": (11, "f4"), "nrm": (12, "f4"), "pstate": (13, "i4")}
 TAPE_SEGMENT_POINTS = 14
+# wos_tape_index_field (include/wos.h): the arrays wos_tape_index_read copies out
+TAPE_INDEX_FIELDS = {"row": (0, "u4"), "id": (1, "u4"), "w": (2, "f4"), "cell": (3, "u4")}
 
 _lib = None
 
@@ -183,6 +192,17 @@ def load():
                                C.POINTER(Stats), C.c_void_p, C.c_uint32]
     L.wos_tape_read.restype = C.c_int
     L.wos_tape_read.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_void_p]
+    L.wos_tape_index_build.restype = C.c_int
+    L.wos_tape_index_build.argtypes = [C.c_void_p, C.c_int64]
+    L.wos_tape_index_get_info.restype = C.c_int
+    L.wos_tape_index_get_info.argtypes = [C.c_void_p, C.POINTER(TapeIndexInfo)]
+    L.wos_tape_index_read.restype = C.c_int
+    L.wos_tape_index_read.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_void_p]
+    L.wos_tape_vjp_indexed.restype = C.c_int
+    L.wos_tape_vjp_indexed.argtypes = L.wos_tape_vjp.argtypes
+    L.wos_selftest_tape_rowsum.restype = C.c_int
+    L.wos_selftest_tape_rowsum.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_int64, C.c_int32, C.c_void_p, C.POINTER(C.c_int32), C.c_int32]
     L.wos_default_bvc_params.restype = None
     L.wos_default_bvc_params.argtypes = [C.POINTER(BvcParams)]
     L.wos_bvc.restype = C.c_int

@@ -533,15 +533,51 @@ class WalkTape:
             out = out + (ne, sp)
         return out
 
-    def vjp(self, grad_p=None, grad_grad=None, *, stream=None):
+    def build_index(self, max_bytes=None):
+        """Build the tape's cell-sorted index (wos_tape_index_build; blocking, once per tape: a
+        second call does nothing), which vjp(..., deterministic=True) sums over.  max_bytes:
+        refuse (WOS_E_CAPACITY) a build whose index and sort scratch need more device memory;
+        the tape then stays as it was."""
+        check(_lib.load().wos_tape_index_build(self._h, int(max_bytes) if max_bytes else 0), "wos_tape_index_build")
+
+    @property
+    def index_info(self):
+        """wos_tape_index_info as a dict: built, n_segments, n_terms, n_cells, max_terms_per_cell,
+        bytes, tile_terms."""
+        i = _lib.TapeIndexInfo()
+        check(_lib.load().wos_tape_index_get_info(self._h, C.byref(i)), "wos_tape_index_get_info")
+        return {n: int(getattr(i, n)) for n, _ in i._fields_}
+
+    def read_index(self, field, segment=0):
+        """One array of one segment's index as numpy (wos_tape_index_read): row [cells + 1], and
+        per term, sorted stably by cell, id (task | bit 31: the first-ball term), w and cell."""
+        L = _lib.load()
+        if field not in _lib.TAPE_INDEX_FIELDS:
+            raise WosError(f"WalkTape.read_index: unknown field {field!r} (one of {', '.join(_lib.TAPE_INDEX_FIELDS)})")
+        fid, dtype = _lib.TAPE_INDEX_FIELDS[field]
+        cells = self.index_info["n_cells"]
+        row = np.empty(cells + 1, "u4")
+        check(L.wos_tape_index_read(self._h, segment, _lib.TAPE_INDEX_FIELDS["row"][0], 0, row.size, row.ctypes.data),
+              "wos_tape_index_read")
+        if field == "row":
+            return row
+        out = np.empty(int(row[-1]), dtype)
+        check(L.wos_tape_index_read(self._h, segment, fid, 0, out.size, out.ctypes.data), "wos_tape_index_read")
+        return out
+
+    def vjp(self, grad_p=None, grad_grad=None, *, stream=None, deterministic=False):
         """The transpose of solve() applied to an upstream (wos_tape_vjp): the gradient with
         respect to the scene's source grid of a loss whose derivatives by solve()'s p and grad
         are grad_p and grad_grad (shaped like them; one may be None: zeros).  Returns an array
         of the scene's source_shape -- numpy for numpy input, a torch-CUDA tensor for torch-CUDA
         input.  It depends neither on the current source values nor on dirichlet_values;
-        upstream values of masked outputs and of points without an estimate are ignored.  The
-        sums are float atomics: two calls may differ in the last bits.  last_vjp_stats holds the
-        call's statistics (fold_ms: the adjoint fold, walk_ms: the scatter)."""
+        upstream values of masked outputs and of points without an estimate are ignored.
+        deterministic=False: the sums are float atomics (wos_tape_vjp), two calls may differ in
+        the last bits.  deterministic=True: the sums run over the tape's cell-sorted index in a
+        fixed order, without atomics (wos_tape_vjp_indexed): every call on this tape, and on a
+        tape recorded from the same inputs in the same batches, returns the same bits; the
+        index is built on first use (build_index).  last_vjp_stats holds the call's statistics
+        (fold_ms: the adjoint fold, walk_ms: the scatter or the sum kernels)."""
         L = _lib.load()
         sc = self.scene
         if grad_p is None and grad_grad is None:
@@ -579,8 +615,10 @@ class WalkTape:
             out = np.empty(sc.source_shape, np.float32)
             ptr = lambda a: a.ctypes.data if a is not None else None
             s, flags = stream, 0
-        check(L.wos_tape_vjp(self._h, sc._h, nch, ptr(up[0]), ptr(up[1]), ptr(out), C.byref(st), s, flags),
-              "wos_tape_vjp")
+        if deterministic:
+            self.build_index()
+        fn = "wos_tape_vjp_indexed" if deterministic else "wos_tape_vjp"
+        check(getattr(L, fn)(self._h, sc._h, nch, ptr(up[0]), ptr(up[1]), ptr(out), C.byref(st), s, flags), fn)
         self.last_vjp_stats = st.as_dict()
         return out
 
@@ -693,6 +731,28 @@ def selftest_lhs_plan(n_pairs, dim):
     keys = ("points_per_wave", "one_pass", "shuffle", "pair_passes", "jump_mixed", "wave_lds_bytes", "lds_budget",
             "point_grab", "shuffle_chunks")
     return {k: int(v) for k, v in zip(keys, out)}
+
+
+def selftest_tape_rowsum(row, id, w, a, c, device=0):
+    """The indexed adjoint's sum kernels on a hand-built index (wos_selftest_tape_rowsum): row
+    [n_rows + 1] offsets, id / w per term, a / c [C, T] (or [T]: one channel).  Returns
+    (out float32 [C, n_rows] or [n_rows], the tile constant)."""
+    row = np.ascontiguousarray(row, dtype=np.uint32)
+    id = np.ascontiguousarray(id, dtype=np.uint32)
+    w = np.ascontiguousarray(w, dtype=np.float32)
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    c = np.ascontiguousarray(c, dtype=np.float32)
+    if a.shape != c.shape or a.ndim not in (1, 2) or id.shape != w.shape or row.ndim != 1 or row.size < 2:
+        raise WosError("selftest_tape_rowsum: row [n_rows + 1], id / w [n_terms], a / c [C, T] or [T]")
+    nch = 1 if a.ndim == 1 else a.shape[0]
+    if id.size != int(row[-1]):
+        raise WosError(f"selftest_tape_rowsum: {id.size} terms, row[-1] = {int(row[-1])}")
+    out = np.empty((nch, row.size - 1), np.float32)
+    tile = C.c_int32(0)
+    check(_lib.load().wos_selftest_tape_rowsum(row.ctypes.data, row.size - 1, id.ctypes.data, w.ctypes.data,
+                                               a.ctypes.data, c.ctypes.data, a.shape[-1], nch, out.ctypes.data,
+                                               C.byref(tile), device), "wos_selftest_tape_rowsum")
+    return (out[0] if a.ndim == 1 else out), int(tile.value)
 
 
 def device_count():

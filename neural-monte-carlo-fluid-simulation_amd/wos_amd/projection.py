@@ -113,7 +113,8 @@ def divergence(y, x, create_graph=False):
 class _TapeProjection(torch.autograd.Function):
     """solve(div) of a PressureProjector with reuse_walks as a differentiable function of div:
     forward is the source replacement plus the replay, backward the tape's transpose
-    (WalkTape.vjp).  The variance outputs are not differentiable."""
+    (WalkTape.vjp; over the tape's cell-sorted index, bit for bit reproducible, with the
+    projector's deterministic_backward).  The variance outputs are not differentiable."""
 
     @staticmethod
     def forward(ctx, div, proj, variance):
@@ -121,6 +122,7 @@ class _TapeProjection(torch.autograd.Function):
         *out, st = proj._replay_points(proj.samples, 0, 1, **({"variance": True} if variance else {}))
         proj.last_stats = st
         ctx.tape, ctx.shape, ctx.dtype = proj._tape, tuple(div.shape), div.dtype
+        ctx.deterministic = proj.deterministic_backward
         if variance:
             ctx.mark_non_differentiable(out[2], out[3])
         return tuple(out)
@@ -131,7 +133,7 @@ class _TapeProjection(torch.autograd.Function):
             raise RuntimeError("the projector recorded a new tape (another source grid) before backward()")
         if tuple(ctx.tape.scene.source_shape) != ctx.shape:
             raise RuntimeError("the projector's source grid changed shape before backward()")
-        return ctx.tape.vjp(grad_p, grad_g).to(ctx.dtype), None, None
+        return ctx.tape.vjp(grad_p, grad_g, deterministic=ctx.deterministic).to(ctx.dtype), None, None
 
 
 class PressureProjector:
@@ -162,14 +164,18 @@ class PressureProjector:
     div's autograd graph: backward applies the transpose of the recorded walks' affine map
     (WalkTape.vjp), so a loss on p / grad_p reaches whatever produced div --
     source_from_velocity(..., create_graph=True) keeps that graph down to the network's weights.
+    deterministic_backward=True: that backward sums in a fixed order without atomics
+    (WalkTape.vjp(deterministic=True); the tape's index is built at the first backward), so two
+    backward passes give the same bits and a training run can be replayed.
     """
 
     # class-level defaults: a subclass that builds its own scene keeps the plain path
     reuse_walks = False
+    deterministic_backward = False
     _tape, _tape_grid = None, None
 
     def __init__(self, scene_config, solver_config, output_config, pressure_samples, device=None,
-                 group=None, force_gather=False, reuse_walks=False):
+                 group=None, force_gather=False, reuse_walks=False, deterministic_backward=False):
         import zombie_bindings  # the drop-in shim parses the reference's scene keys
         self.dim = int(pressure_samples.shape[-1])
         self.device = pressure_samples.device if device is None else torch.device(device)
@@ -180,6 +186,7 @@ class PressureProjector:
         self.group, self.force_gather = group, force_gather
         self.last_stats = None
         self.reuse_walks = bool(reuse_walks)
+        self.deterministic_backward = bool(deterministic_backward)
         self._tape, self._tape_grid = None, None
 
     def source_from_velocity(self, velocity_fn, resolution, size, create_graph=False):
