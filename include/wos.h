@@ -150,6 +150,41 @@ typedef struct wos_scene_info {
 } wos_scene_info;
 int wos_scene_get_info(const wos_scene *scene, wos_scene_info *info);
 
+/* ---- Geometry queries: distance, side and solve state of points, on the device ----------
+ * What a solve's point setup computes for every query point before it walks (added within
+ * ABI 10: a new entry point only), for callers that need it outside a solve: the time-stepper's
+ * obstacle SDF (the reference's obs_sdf_func, src/2d/models/base.py:239-241, 352-358, which for
+ * a mesh goes through the host: obstacle_function, src/2d/sources.py:102-119) and an inside /
+ * mask test that agrees with the solver's own.  For n points pts[n*dim], each output optional
+ * (NULL), all four NULL being WOS_E_INVALID:
+ *   dist[n]         distance to boundary `which` (WOS_QUERY_NEUMANN: the scene's boundary mesh;
+ *                   WOS_QUERY_DIRICHLET: its optional Dirichlet mesh)
+ *   signed_dist[n]  the solver's signed distance: +dist on the side the primitive's normal at
+ *                   the closest point faces, -dist on the other -- negative on the domain side
+ *   closest[n*dim]  the closest point on that boundary (the last primitive among exact ties)
+ *   state[n]        bit 0 estimated, bit 1 p masked, bit 2 grad masked -- WOS_TAPE_PSTATE's bits,
+ *                   what a solve with output.boundaryDistanceMask = boundary_distance_mask gives
+ *                   the point -- and bit 3 insideDomain (fcpw_scene_loader.h:642-648).  It always
+ *                   takes both boundaries as the solver does (without Dirichlet geometry the far
+ *                   corner of the bounding box) and does not depend on `which`.
+ * The values are the solve's own device functions': bit for bit what wos_solve decides.
+ * WOS_E_INVALID: `which` out of range; dist, signed_dist or closest asked of a boundary the scene
+ * does not hold (state alone needs none).  n == 0 succeeds without a launch.  Pointers are host
+ * pointers (blocking; staged through temporaries of the call's own) or, with WOS_PTRS_DEVICE,
+ * device pointers on the scene's device; WOS_ASYNC as in wos_solve: with WOS_PTRS_DEVICE it
+ * enqueues on `stream` and returns, without it (host pointers) the flag is ignored and the call
+ * blocks.  The call reads geometry only: it is ordered against nothing but `stream`, may run
+ * beside solves on other streams, and leaves the solve workspace and the source alone.
+ * Lifetime of an enqueued query: it reads the scene's prepared geometry, which outlives
+ * wos_scene_destroy and wos_release_caches until the device has finished with it (it is released
+ * only after a device synchronise), so destroying the scene behind a pending query is safe; pts
+ * and the output buffers are the caller's and must stay valid until `stream` has run the query. */
+enum { WOS_QUERY_NEUMANN = 0, WOS_QUERY_DIRICHLET = 1 };
+int wos_scene_query(wos_scene *scene, int32_t which, float boundary_distance_mask,
+                    const float *pts, int64_t n,
+                    float *dist, float *signed_dist, float *closest /* [n][dim] */, int32_t *state,
+                    void *stream, uint32_t flags);
+
 /* Solver / output settings: the keys runWalkOnStars_sampled reads
  * (demo.cpp:121-137) plus output.boundaryDistanceMask (grid.h:159) and the
  * counter-based RNG key that replaces the clock seeds. */

@@ -232,6 +232,9 @@ struct Geom {
   uint32_t* d_dgrid = nullptr;
   ~Geom() {
     hipSetDevice(device);
+    // a wos_scene_query enqueued with WOS_ASYNC may still read these records: it is ordered against
+    // nothing but its stream, and wos_scene_destroy waits for solves only
+    hipDeviceSynchronize();
     hipFree(d_prim); hipFree(d_paux); hipFree(d_sil); hipFree(d_dprim); hipFree(d_dpaux);
     hipFree(d_pgroup); hipFree(d_sgroup); hipFree(d_dgroup);
     hipFree(d_ptree); hipFree(d_stree); hipFree(d_dtree);
@@ -723,6 +726,74 @@ int wos_scene_get_info(const wos_scene* s, wos_scene_info* info) {
   info->n_dprims = h.n_dprims;
   info->device = s->device;
   for (int k = 0; k < 3; k++) { info->bbox_min[k] = h.pmin[k]; info->bbox_max[k] = h.pmax[k]; }
+  return WOS_OK;
+}
+
+// Geometry queries (wos_query.hip).  Reads the prepared geometry only: no device-context lock,
+// no workspace, no ordering against solves on other streams.  Host pointers are staged through
+// one allocation of the call's own, freed before it returns.
+int wos_scene_query(wos_scene* s, int32_t which, float boundary_distance_mask, const float* pts, int64_t n,
+                    float* dist, float* signed_dist, float* closest, int32_t* state, void* stream, uint32_t flags) {
+  if (!s) return fail(WOS_E_INVALID, "wos_scene_query: null scene");
+  if (which != WOS_QUERY_NEUMANN && which != WOS_QUERY_DIRICHLET)
+    return fail(WOS_E_INVALID, "wos_scene_query: which must be WOS_QUERY_NEUMANN (0) or WOS_QUERY_DIRICHLET (1), got " +
+                                   std::to_string(which));
+  if (!dist && !signed_dist && !closest && !state)
+    return fail(WOS_E_INVALID, "wos_scene_query: no output requested (dist, signed_dist, closest and state are all null)");
+  if (n < 0) return fail(WOS_E_INVALID, "wos_scene_query: negative point count");
+  if (n >= (int64_t)0xFFFFFFF0LL) return fail(WOS_E_INVALID, "wos_scene_query: too many points for one call");
+  const wos::HostScene& host = s->geom->host;
+  const int dim = host.dim;
+  if ((dist || signed_dist || closest) && (which == WOS_QUERY_NEUMANN ? host.n_prims : host.n_dprims) <= 0)
+    return fail(WOS_E_INVALID, std::string("wos_scene_query: the scene holds no ") +
+                                   (which == WOS_QUERY_NEUMANN ? "Neumann" : "Dirichlet") +
+                                   " boundary (dist, signed_dist and closest need one; state alone does not)");
+  if (n == 0) return WOS_OK;
+  if (!pts) return fail(WOS_E_INVALID, "wos_scene_query: null point buffer");
+  wos::DevScene dsc;
+  {
+    std::lock_guard<std::mutex> lock(s->mu);  // set_source rewrites the source fields of s->dev
+    dsc = s->dev;
+  }
+  HIP_TRY(hipSetDevice(s->device));
+  hipStream_t st = (hipStream_t)stream;
+  if (flags & WOS_PTRS_DEVICE) {
+    HIP_TRY(wos::launch_point_query(dim, dsc, which, boundary_distance_mask, pts, n, dist, signed_dist, closest,
+                                    state, st));
+    if (!(flags & WOS_ASYNC)) HIP_TRY(hipStreamSynchronize(st));
+    return WOS_OK;
+  }
+  // one temporary: pts [n][dim] | dist [n] | signed_dist [n] | closest [n][dim] | state [n], 4-byte elements
+  const size_t N = (size_t)n;
+  const size_t o_dist = N * dim, o_sd = o_dist + (dist ? N : 0), o_cl = o_sd + (signed_dist ? N : 0),
+               o_st = o_cl + (closest ? N * dim : 0), total = o_st + (state ? N : 0);
+  float* tmp = nullptr;
+  if (hipMalloc((void**)&tmp, total * sizeof(float)) != hipSuccess)
+    return fail(WOS_E_NOMEM, "wos_scene_query: cannot allocate " + std::to_string(total * sizeof(float)) +
+                                 " bytes of staging");
+  const auto run = [&]() -> hipError_t {
+    hipError_t e = hipMemcpyAsync(tmp, pts, N * dim * sizeof(float), hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) return e;
+    e = wos::launch_point_query(dim, dsc, which, boundary_distance_mask, tmp, n, dist ? tmp + o_dist : nullptr,
+                                signed_dist ? tmp + o_sd : nullptr, closest ? tmp + o_cl : nullptr,
+                                state ? (int32_t*)(tmp + o_st) : nullptr, st);
+    if (e != hipSuccess) return e;
+    if (dist && (e = hipMemcpyAsync(dist, tmp + o_dist, N * sizeof(float), hipMemcpyDeviceToHost, st)) != hipSuccess)
+      return e;
+    if (signed_dist &&
+        (e = hipMemcpyAsync(signed_dist, tmp + o_sd, N * sizeof(float), hipMemcpyDeviceToHost, st)) != hipSuccess)
+      return e;
+    if (closest &&
+        (e = hipMemcpyAsync(closest, tmp + o_cl, N * dim * sizeof(float), hipMemcpyDeviceToHost, st)) != hipSuccess)
+      return e;
+    if (state && (e = hipMemcpyAsync(state, tmp + o_st, N * sizeof(int32_t), hipMemcpyDeviceToHost, st)) != hipSuccess)
+      return e;
+    return hipStreamSynchronize(st);
+  };
+  const hipError_t e = run();
+  if (e != hipSuccess) hipStreamSynchronize(st);  // nothing may still use tmp when it is freed
+  hipFree(tmp);
+  if (e != hipSuccess) return fail(WOS_E_DEVICE, std::string("wos_scene_query: ") + hipGetErrorString(e));
   return WOS_OK;
 }
 

@@ -25,6 +25,11 @@ hipError_t launch_first_balls(const KernelVariant& v, const DevScene& sc, const 
 // per-point setup: pstate + first-ball radius + bucket histogram, before launch_lpt_order
 hipError_t launch_point_setup(int dim, const DevScene& sc, const DevParams& prm, const float* pts, int64_t n,
                               const DevTasks& tk, hipStream_t s);
+// geometry queries (wos_query.hip; include/wos.h wos_scene_query): per point the distance, signed
+// distance and closest point [n][dim] of boundary `which` (0 Neumann, 1 Dirichlet) and the state
+// word for `mask` (pstate's bits 0-2, bit 3 inside); every output may be null
+hipError_t launch_point_query(int dim, const DevScene& sc, int which, float mask, const float* pts, int64_t n,
+                              float* dist, float* sdist, float* closest, int32_t* state, hipStream_t s);
 // zero n64 u64 words at a and n32 u32 words at b (one launch)
 hipError_t launch_zero(unsigned long long* a, int n64, uint32_t* b, int n32, hipStream_t s);
 // bucket offsets + point permutation for the walk queue

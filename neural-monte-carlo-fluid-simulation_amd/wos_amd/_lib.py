@@ -119,7 +119,13 @@ EXPORTS = (
     "wos_tape_vjp", "wos_tape_read",
     "wos_tape_index_build", "wos_tape_index_get_info", "wos_tape_index_read", "wos_tape_vjp_indexed",
     "wos_selftest_tape_rowsum",
+    "wos_scene_query",
 )
+
+# include/wos.h WOS_QUERY_*: the boundary wos_scene_query's dist / signed_dist / closest describe
+QUERY_NEUMANN, QUERY_DIRICHLET = 0, 1
+# wos_scene_query's state word: WOS_TAPE_PSTATE's bits 0-2, bit 3 insideDomain
+STATE_ESTIMATED, STATE_MASK_P, STATE_MASK_GRAD, STATE_INSIDE = 1, 2, 4, 8
 
 # wos_tape_field (include/wos.h): the arrays wos_tape_read copies out, with their element types
 TAPE_FIELDS = {"code": (0, "u4"), "cnt": (1, "u4"), "slot": (2, "u4"), "cell0": (3, "u4"), "gnorm": (4, "f4"),
@@ -152,6 +158,9 @@ def load():
     L.wos_scene_get_info.argtypes = [C.c_void_p, C.POINTER(SceneInfo)]
     L.wos_scene_set_source.restype = C.c_int
     L.wos_scene_set_source.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.c_void_p]
+    L.wos_scene_query.restype = C.c_int
+    L.wos_scene_query.argtypes = [C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
     L.wos_release_caches.restype = C.c_int
     L.wos_release_caches.argtypes = [C.c_int32]
     L.wos_set_max_batch_tasks.restype = C.c_int64

@@ -386,6 +386,72 @@ class WosScene:
             out = out + (ne, sp)
         return out
 
+    def query(self, pts, *, which="neumann", boundary_distance_mask=0.0, closest=False, stream=None):
+        """Distance, side and solve state of points [N, dim] (wos_scene_query), computed by the
+        solve's own device code: (dist [N], signed_dist [N], state [N] int32[, closest [N, dim]]).
+        which: "neumann" (the boundary mesh) or "dirichlet" (the optional Dirichlet mesh) -- the
+        boundary dist, signed_dist and closest describe.  signed_dist is the solver's: negative on
+        the domain side.  state: bit 0 estimated, bit 1 p masked, bit 2 grad masked -- what a solve
+        with output.boundaryDistanceMask = boundary_distance_mask gives the point -- and bit 3
+        inside the domain (_lib.STATE_*); it takes both boundaries into account whatever `which`.
+        numpy in, numpy out (blocking); a torch CUDA tensor in, torch tensors on its device out,
+        enqueued on `stream` (a torch.cuda.Stream or a raw hipStream_t; default: torch's current
+        stream) without a host synchronisation."""
+        w = {"neumann": _lib.QUERY_NEUMANN, "dirichlet": _lib.QUERY_DIRICHLET}.get(which, which)
+        if w not in (_lib.QUERY_NEUMANN, _lib.QUERY_DIRICHLET):
+            raise WosError(f"WosScene.query: which must be 'neumann' or 'dirichlet', got {which!r}")
+        d, sd, cp, state = self._query(pts, w, boundary_distance_mask, (True, True, bool(closest), True), stream)
+        return (d, sd, state, cp) if closest else (d, sd, state)
+
+    def query_state(self, pts, boundary_distance_mask=0.0, *, stream=None):
+        """query()'s state words alone: needs neither boundary to exist and scans nothing else."""
+        return self._query(pts, _lib.QUERY_NEUMANN, boundary_distance_mask, (False, False, False, True), stream)[3]
+
+    def _query(self, pts, which, mask, want, stream):
+        """wos_scene_query for the outputs `want` = (dist, signed_dist, closest, state) asks for:
+        those four, None where not asked."""
+        L = _lib.load()
+        mask = float(mask)
+        dtypes = ("float32", "float32", "float32", "int32")
+        if _is_torch(pts) and pts.is_cuda:
+            import torch
+            x = pts.detach().to(torch.float32).contiguous()
+            if x.ndim != 2 or x.shape[1] != self.dim:
+                raise WosError(f"points must be [N,{self.dim}]")
+            n = x.shape[0]
+            out = [torch.empty((n, self.dim) if k == 2 else (n,), dtype=getattr(torch, dtypes[k]), device=x.device)
+                   if want[k] else None for k in range(4)]
+            if n == 0:  # empty tensors have null data pointers, which the C ABI reads as "not asked for"
+                return tuple(out)
+            cur = torch.cuda.current_stream(x.device)
+            if stream is None:
+                s = cur.cuda_stream
+            else:
+                ts = stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.ExternalStream(int(stream),
+                                                                                                    device=x.device)
+                s = ts.cuda_stream
+                ts.wait_stream(cur)  # the points and the fresh outputs belong to torch's current stream
+                for t in [x] + out:
+                    if t is not None:
+                        t.record_stream(ts)  # ... and are used on `stream`: the allocator must wait for it
+            ptr = [t.data_ptr() if t is not None else None for t in out]
+            check(L.wos_scene_query(self._h, which, mask, x.data_ptr(), n, *ptr, s,
+                                    _lib.WOS_PTRS_DEVICE | _lib.WOS_ASYNC), "wos_scene_query")
+        else:
+            if _is_torch(pts):
+                pts = pts.detach().cpu().numpy()
+            x = np.ascontiguousarray(pts, dtype=np.float32)
+            if x.ndim != 2 or x.shape[1] != self.dim:
+                raise WosError(f"points must be [N,{self.dim}]")
+            n = x.shape[0]
+            out = [np.empty((n, self.dim) if k == 2 else (n,), dtypes[k]) if want[k] else None for k in range(4)]
+            if n == 0:
+                return tuple(out)
+            ptr = [a.ctypes.data if a is not None else None for a in out]
+            s = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
+            check(L.wos_scene_query(self._h, which, mask, x.ctypes.data, n, *ptr, s, 0), "wos_scene_query")
+        return tuple(out)
+
     def record(self, pts, params=None, *, index_base=0, index_stride=1, max_bytes=None):
         """Record the walks of solve(pts, params, index_base=..., index_stride=...) once
         (wos_tape_record; blocking, about two solves).  The returned WalkTape replays them for

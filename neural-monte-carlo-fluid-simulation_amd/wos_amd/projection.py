@@ -110,6 +110,66 @@ def divergence(y, x, create_graph=False):
     return div
 
 
+class _MeshDistance(torch.autograd.Function):
+    """sign * signed_dist of WosScene.query as a once-differentiable function of the points."""
+
+    @staticmethod
+    def forward(ctx, x, scene, sign):
+        xq = x.detach().to(torch.float32).contiguous()
+        dist, sd, _, cp = scene.query(xq, which="neumann", closest=True)
+        # a host scene (CPU tensors in) answers in numpy
+        dist, sd, cp = (torch.as_tensor(a).to(xq.device) for a in (dist, sd, cp))
+        out = sd if sign > 0 else -sd
+        ctx.save_for_backward(xq, cp, dist, out)
+        ctx.dtype = x.dtype
+        return out.to(x.dtype)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        xq, cp, dist, out = ctx.saved_tensors
+        r = xq - cp
+        nrm = torch.sqrt((r * r).sum(-1, keepdim=True))
+        on = (dist == 0)[:, None] | (nrm == 0)
+        direction = torch.where(on, torch.zeros_like(r), r / torch.where(on, torch.ones_like(nrm), nrm))
+        # |value| grows along (x - closest): d value / dx = sgn(value) (x - closest) / |x - closest|
+        g = grad_out.to(torch.float32)[:, None] * torch.sign(out)[:, None] * direction
+        return g.to(ctx.dtype), None, None
+
+
+class MeshSDF:
+    """The signed distance to a scene's boundary mesh as a device function with the signature of
+    the reference's obs_sdf_func (src/2d/models/base.py:239-241, 352-358): samples [..., dim] ->
+    distances [...], on the samples' device, with no host synchronisation.  It replaces
+    obstacle_function(v, l) (src/2d/sources.py:102-119: gpytoolbox on the host per call, no
+    gradient) for any OBJ outline.
+
+        sdf = MeshSDF(scene, positive="outside")      # scene: a WosScene or a zombie_bindings.Scene
+        dist = sdf(samples); samples = samples[dist > 0]
+
+    The value is WosScene.query's signed_dist, the solver's own: negative on the domain side.
+    positive="inside" returns -signed_dist (positive in the domain the solver estimates in),
+    positive="outside" +signed_dist (for an obstacle mesh whose domain side is the obstacle's
+    interior this is the reference's convention: positive in the fluid).
+    Once differentiable: d value / dx = sgn(value) (x - closest) / |x - closest|, and 0 where the
+    distance is 0, so the grad(w) . u term of divergence(query_velocity(grid), grid) behaves as
+    with an analytic SDF.  Second derivatives are not provided: the backward is
+    once_differentiable, and source_from_velocity(create_graph=True) through a MeshSDF raises."""
+
+    def __init__(self, scene, positive="inside"):
+        if positive not in ("inside", "outside"):
+            raise ValueError(f"MeshSDF: positive must be 'inside' or 'outside', got {positive!r}")
+        self.scene = getattr(scene, "_scene", scene)
+        self.positive = positive
+        self.dim = int(self.scene.dim)
+
+    def __call__(self, samples):
+        if samples.shape[-1] != self.dim:
+            raise ValueError(f"MeshSDF: samples must be [..., {self.dim}], got shape {tuple(samples.shape)}")
+        out = _MeshDistance.apply(samples.reshape(-1, self.dim), self.scene, 1 if self.positive == "outside" else -1)
+        return out.reshape(samples.shape[:-1])
+
+
 class _TapeProjection(torch.autograd.Function):
     """solve(div) of a PressureProjector with reuse_walks as a differentiable function of div:
     forward is the source replacement plus the replay, backward the tape's transpose
@@ -200,6 +260,16 @@ class PressureProjector:
             return (-divergence(u, grid, create_graph=True)[..., 0]).contiguous()
         div = divergence(u, grid)
         return (-div[..., 0]).detach().contiguous()
+
+    def sample_state(self, pts=None):
+        """The state words solve() will give the pressure samples, or `pts` [N, dim]
+        (WosScene.query_state with this projector's scene and boundaryDistanceMask): int32 [N],
+        bit 0 estimated, bit 1 p masked, bit 2 grad p masked, bit 3 inside the domain.  A masked
+        sample comes back as grad_p = 0 and projection_loss then trains on target = u_prev there;
+        with this a caller can draw or filter samples the solve estimates and does not mask:
+        keep = (state & 5) == 1."""
+        x = self.samples if pts is None else pts
+        return self.scene._scene.query_state(x, self.params.boundary_distance_mask)
 
     def _set_source(self, div):
         self.scene._scene.set_source(div)

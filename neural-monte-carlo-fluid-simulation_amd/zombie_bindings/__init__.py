@@ -181,6 +181,18 @@ class Scene:
             source = np.asarray(source, dtype=np.float32)
         self._scene.set_source(source)
 
+    def sdf(self, pts, positive="inside"):
+        """Extension: the signed distance of pts [..., dim] to this scene's boundary mesh, on the
+        device (wos_amd.projection.MeshSDF; replaces obstacle_function, src/2d/sources.py:102-119).
+        positive="inside": positive in the solver's domain, "outside": the solver's own sign.
+        A torch tensor gives a tensor on its device, once differentiable in pts."""
+        from wos_amd.projection import MeshSDF
+        if _engine._is_torch(pts):
+            return MeshSDF(self, positive)(pts)
+        import torch
+        x = torch.from_numpy(np.ascontiguousarray(pts, dtype=np.float32))
+        return MeshSDF(self, positive)(x).numpy()
+
 
 def wost(scene, solverConfig, outputConfig, pts, return_numpy=False, return_variance=False):
     """runWalkOnStars_sampled (demo.cpp:119-205) / runWalkOnStars_3d: returns
