@@ -525,6 +525,44 @@ int wos_selftest_tape_rowsum(const uint32_t *row, int64_t n_rows, const uint32_t
                              const float *a, const float *c, int64_t n_tasks, int32_t n_channels,
                              float *out, int32_t *tile_terms, int32_t device);
 
+/* ---- Fused SIREN: value, input Jacobian and divergence of the velocity network ---------------
+ * The reference's MLP with sine (src/2d/models/networks.py:25-68): Linear(d_in, hidden),
+ * sin(omega .), n_hidden_layers x [Linear(hidden, hidden), sin(omega .)], Linear(hidden, d_out),
+ * every layer with bias -- evaluated in forward mode in one kernel (added within ABI 10: new entry
+ * points only; csrc/wos_siren.hip).  It replaces the autograd divergence behind get_divergence
+ * (model_split.py:230-236, diff_ops.py:45-51): no activation leaves the chip.  For n points
+ * pts[n*d_in], each output optional (NULL), all three NULL being WOS_E_INVALID:
+ *   u[n*d_out]         the network's value
+ *   jac[n*d_out*d_in]  jac[(p*d_out + i)*d_in + k] = d u_i / d x_k
+ *   div[n]             (jac[0][0] + jac[1][1]) + jac[2][2], added in f32 in that order; needs
+ *                      d_out == d_in
+ * Envelope: d_in 2 or 3, d_out 1..3, hidden a multiple of 32 in 32..256, n_hidden_layers 0..8,
+ * omega finite; anything else is WOS_E_INVALID with a message naming the field.  weights and biases
+ * are host arrays of n_hidden_layers + 2 pointers, torch's layout: weights[l] [out][in] row-major.
+ * All arithmetic is f32 in a fixed order (DESIGN.md "Fused SIREN source"): a point's outputs are the
+ * same bits whatever n is, wherever the point sits in pts, whichever outputs are requested and from
+ * run to run.  Pointer rules are wos_scene_query's: pts, u, jac, div and every weights[l] / biases[l]
+ * are host pointers (the call stages them and blocks) or, with WOS_PTRS_DEVICE, device pointers on
+ * `device`; with WOS_PTRS_DEVICE | WOS_ASYNC the call enqueues on `stream` and returns, and the
+ * buffers must stay valid until `stream` has run it.  n == 0 succeeds without a launch. */
+typedef struct wos_siren_net {
+    int32_t d_in, d_out, hidden, n_hidden_layers;
+    float omega;
+    const float *const *weights;   /* n_hidden_layers + 2 pointers */
+    const float *const *biases;    /* n_hidden_layers + 2 pointers */
+} wos_siren_net;
+int wos_siren_eval(const wos_siren_net *net, const float *pts, int64_t n,
+                   float *u, float *jac, float *div,
+                   uint32_t flags, int32_t device, void *stream);
+
+/* Device self-test of wos_siren_eval's hidden-layer product (the kernel's own device function on
+ * its own LDS layout), host pointers, blocking: for n_points points carrying 1 + d_in columns of
+ * `hidden` floats, X [n_points][1 + d_in][hidden], the pre-activations Z of the same shape:
+ * Z[p][0] = W X[p][0] + b and Z[p][s] = W X[p][s] for s > 0, W [hidden][hidden] row-major.
+ * hidden and d_in as wos_siren_eval; n_points >= 1. */
+int wos_selftest_siren_layer(int32_t hidden, int32_t d_in, int64_t n_points, const float *W, const float *b,
+                             const float *X, float *Z, int32_t device);
+
 const char *wos_last_error(void);
 int32_t wos_abi_version(void);
 int32_t wos_device_count(void);

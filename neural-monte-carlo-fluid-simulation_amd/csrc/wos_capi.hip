@@ -32,6 +32,7 @@
 #include "wos_detmath.h"
 #include "wos_host_scene.h"
 #include "wos_launch.h"
+#include "wos_siren.h"
 
 namespace {
 
@@ -2824,6 +2825,135 @@ int wos_selftest_tape_rowsum(const uint32_t* row, int64_t n_rows, const uint32_t
   HIP_TRY(wos::launch_tape_rowsum(ix, n_rows, n_channels, n_tasks, d_a, d_c, d_out, nullptr));
   HIP_TRY(hipDeviceSynchronize());
   HIP_TRY(hipMemcpy(out, d_out, co * 4, hipMemcpyDeviceToHost));
+  return WOS_OK;
+}
+
+// ---- fused SIREN (wos_siren.hip) -------------------------------------------------------------
+static int siren_shape_check(const std::string& fn, int32_t d_in, int32_t hidden) {
+  if (d_in != 2 && d_in != 3) return fail(WOS_E_INVALID, fn + ": d_in must be 2 or 3, got " + std::to_string(d_in));
+  if (hidden < 32 || hidden > wos::kSirenMaxHidden || hidden % 32 != 0)
+    return fail(WOS_E_INVALID, fn + ": hidden must be a multiple of 32 in 32.." + std::to_string(wos::kSirenMaxHidden) +
+                                   ", got " + std::to_string(hidden));
+  return WOS_OK;
+}
+
+// No scene, no workspace, no lock: the call owns what it allocates.  Device pointers: the packed
+// weights are a stream-ordered allocation, so WOS_ASYNC needs no host wait to free them.  Host
+// pointers: one staging allocation, freed after the call's own synchronise.
+int wos_siren_eval(const wos_siren_net* net, const float* pts, int64_t n, float* u, float* jac, float* div,
+                   uint32_t flags, int32_t device, void* stream) {
+  const std::string fn = "wos_siren_eval";
+  if (!net) return fail(WOS_E_INVALID, fn + ": null net");
+  if (int rc = siren_shape_check(fn, net->d_in, net->hidden)) return rc;
+  if (net->d_out < 1 || net->d_out > 3)
+    return fail(WOS_E_INVALID, fn + ": d_out must be 1..3, got " + std::to_string(net->d_out));
+  if (net->n_hidden_layers < 0 || net->n_hidden_layers > wos::kSirenMaxHiddenLayers)
+    return fail(WOS_E_INVALID, fn + ": n_hidden_layers must be 0.." + std::to_string(wos::kSirenMaxHiddenLayers) +
+                                   ", got " + std::to_string(net->n_hidden_layers));
+  if (!std::isfinite(net->omega)) return fail(WOS_E_INVALID, fn + ": omega must be finite");
+  const int D = net->d_in, DO = net->d_out, H = net->hidden, L = net->n_hidden_layers, NL = L + 2;
+  if (!net->weights || !net->biases) return fail(WOS_E_INVALID, fn + ": null weights or biases array");
+  for (int l = 0; l < NL; l++)
+    if (!net->weights[l] || !net->biases[l])
+      return fail(WOS_E_INVALID, fn + ": null weights or biases pointer of layer " + std::to_string(l));
+  if (!u && !jac && !div) return fail(WOS_E_INVALID, fn + ": no output requested (u, jac and div are all null)");
+  if (div && DO != D)
+    return fail(WOS_E_INVALID, fn + ": div needs d_out == d_in, got d_out " + std::to_string(DO) + ", d_in " +
+                                   std::to_string(D));
+  if (n < 0) return fail(WOS_E_INVALID, fn + ": negative point count");
+  if (n > (int64_t)0x7FFFFFFF * wos::kSirenTile) return fail(WOS_E_INVALID, fn + ": too many points for one call");
+  if (n == 0) return WOS_OK;
+  if (!pts) return fail(WOS_E_INVALID, fn + ": null point buffer");
+  HIP_TRY(hipSetDevice(device));
+  hipStream_t st = (hipStream_t)stream;
+  wos::SirenNet dn{};
+  dn.d_in = D;
+  dn.d_out = DO;
+  dn.H = H;
+  dn.L = L;
+  dn.omega = net->omega;
+  const size_t pack_n = wos::siren_pack_floats(H, L);
+  if (flags & WOS_PTRS_DEVICE) {
+    for (int l = 0; l < NL; l++) { dn.w[l] = net->weights[l]; dn.b[l] = net->biases[l]; }
+    float* packed = nullptr;
+    if (pack_n > 0) HIP_TRY(hipMallocAsync((void**)&packed, pack_n * sizeof(float), st));
+    hipError_t e = wos::launch_siren_pack(dn, packed, st);
+    if (e == hipSuccess) e = wos::launch_siren_eval(dn, packed, pts, n, u, jac, div, st);
+    if (packed) {
+      const hipError_t e2 = hipFreeAsync(packed, st);
+      if (e == hipSuccess) e = e2;
+    }
+    if (e == hipSuccess && !(flags & WOS_ASYNC)) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return fail(WOS_E_DEVICE, fn + ": " + hipGetErrorString(e));
+    return WOS_OK;
+  }
+  // one temporary: packed | weights and biases layer by layer | pts | u | jac | div (floats)
+  const size_t N = (size_t)n;
+  size_t o_w[wos::kSirenMaxLayers], o_b[wos::kSirenMaxLayers], n_w[wos::kSirenMaxLayers], n_b[wos::kSirenMaxLayers];
+  size_t off = pack_n;
+  for (int l = 0; l < NL; l++) {
+    n_b[l] = l == NL - 1 ? (size_t)DO : (size_t)H;
+    n_w[l] = n_b[l] * (l == 0 ? (size_t)D : (size_t)H);
+    o_w[l] = off;
+    off += n_w[l];
+    o_b[l] = off;
+    off += n_b[l];
+  }
+  const size_t o_pts = off, o_u = o_pts + N * D, o_j = o_u + (u ? N * DO : 0), o_d = o_j + (jac ? N * DO * D : 0),
+               total = o_d + (div ? N : 0);
+  float* tmp = nullptr;
+  if (hipMalloc((void**)&tmp, total * sizeof(float)) != hipSuccess)
+    return fail(WOS_E_NOMEM, fn + ": cannot allocate " + std::to_string(total * sizeof(float)) + " bytes of staging");
+  const auto run = [&]() -> hipError_t {
+    hipError_t e;
+    for (int l = 0; l < NL; l++) {
+      if ((e = hipMemcpyAsync(tmp + o_w[l], net->weights[l], n_w[l] * sizeof(float), hipMemcpyHostToDevice, st)) != hipSuccess)
+        return e;
+      if ((e = hipMemcpyAsync(tmp + o_b[l], net->biases[l], n_b[l] * sizeof(float), hipMemcpyHostToDevice, st)) != hipSuccess)
+        return e;
+      dn.w[l] = tmp + o_w[l];
+      dn.b[l] = tmp + o_b[l];
+    }
+    if ((e = hipMemcpyAsync(tmp + o_pts, pts, N * D * sizeof(float), hipMemcpyHostToDevice, st)) != hipSuccess) return e;
+    if ((e = wos::launch_siren_pack(dn, tmp, st)) != hipSuccess) return e;
+    if ((e = wos::launch_siren_eval(dn, tmp, tmp + o_pts, n, u ? tmp + o_u : nullptr, jac ? tmp + o_j : nullptr,
+                                    div ? tmp + o_d : nullptr, st)) != hipSuccess)
+      return e;
+    if (u && (e = hipMemcpyAsync(u, tmp + o_u, N * DO * sizeof(float), hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
+    if (jac && (e = hipMemcpyAsync(jac, tmp + o_j, N * DO * D * sizeof(float), hipMemcpyDeviceToHost, st)) != hipSuccess)
+      return e;
+    if (div && (e = hipMemcpyAsync(div, tmp + o_d, N * sizeof(float), hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
+    return hipStreamSynchronize(st);
+  };
+  const hipError_t e = run();
+  if (e != hipSuccess) hipStreamSynchronize(st);  // nothing may still use tmp when it is freed
+  hipFree(tmp);
+  if (e != hipSuccess) return fail(WOS_E_DEVICE, fn + ": " + hipGetErrorString(e));
+  return WOS_OK;
+}
+
+int wos_selftest_siren_layer(int32_t hidden, int32_t d_in, int64_t n_points, const float* W, const float* b,
+                             const float* X, float* Z, int32_t device) {
+  const std::string fn = "wos_selftest_siren_layer";
+  if (int rc = siren_shape_check(fn, d_in, hidden)) return rc;
+  if (!W || !b || !X || !Z) return fail(WOS_E_INVALID, fn + ": null argument");
+  if (n_points < 1 || n_points > (1LL << 20)) return fail(WOS_E_INVALID, fn + ": n_points must be 1..2^20");
+  HIP_TRY(hipSetDevice(device));
+  DevBufs tmp;
+  const size_t hh = (size_t)hidden * hidden, nx = (size_t)n_points * (1 + d_in) * hidden;
+  float *d_W = nullptr, *d_b = nullptr, *d_pack = nullptr, *d_X = nullptr, *d_Z = nullptr;
+  HIP_TRY(tmp.get(&d_W, hh));
+  HIP_TRY(tmp.get(&d_b, (size_t)hidden));
+  HIP_TRY(tmp.get(&d_pack, hh));
+  HIP_TRY(tmp.get(&d_X, nx));
+  HIP_TRY(tmp.get(&d_Z, nx));
+  HIP_TRY(hipMemcpy(d_W, W, hh * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_b, b, (size_t)hidden * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_X, X, nx * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemset(d_Z, 0, nx * 4));
+  HIP_TRY(wos::launch_siren_layer_selftest(hidden, d_in, n_points, d_W, d_b, d_pack, d_X, d_Z, nullptr));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(Z, d_Z, nx * 4, hipMemcpyDeviceToHost));
   return WOS_OK;
 }
 

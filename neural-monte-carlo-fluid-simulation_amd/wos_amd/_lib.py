@@ -108,6 +108,12 @@ class TapeIndexInfo(C.Structure):
                 ("max_terms_per_cell", C.c_int64), ("bytes", C.c_int64), ("tile_terms", C.c_int32)]
 
 
+class SirenNet(C.Structure):
+    """wos_siren_net: weights / biases are host arrays of n_hidden_layers + 2 pointers."""
+    _fields_ = [("d_in", C.c_int32), ("d_out", C.c_int32), ("hidden", C.c_int32), ("n_hidden_layers", C.c_int32),
+                ("omega", C.c_float), ("weights", C.POINTER(C.c_void_p)), ("biases", C.POINTER(C.c_void_p))]
+
+
 # exported symbols, exactly those declared in include/wos.h
 EXPORTS = (
     "wos_load_obj", "wos_mesh_free", "wos_scene_create", "wos_scene_destroy",
@@ -120,6 +126,7 @@ EXPORTS = (
     "wos_tape_index_build", "wos_tape_index_get_info", "wos_tape_index_read", "wos_tape_vjp_indexed",
     "wos_selftest_tape_rowsum",
     "wos_scene_query",
+    "wos_siren_eval", "wos_selftest_siren_layer",
 )
 
 # include/wos.h WOS_QUERY_*: the boundary wos_scene_query's dist / signed_dist / closest describe
@@ -212,6 +219,12 @@ def load():
     L.wos_selftest_tape_rowsum.restype = C.c_int
     L.wos_selftest_tape_rowsum.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_int64, C.c_int32, C.c_void_p, C.POINTER(C.c_int32), C.c_int32]
+    L.wos_siren_eval.restype = C.c_int
+    L.wos_siren_eval.argtypes = [C.POINTER(SirenNet), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_uint32, C.c_int32, C.c_void_p]
+    L.wos_selftest_siren_layer.restype = C.c_int
+    L.wos_selftest_siren_layer.argtypes = [C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_int32]
     L.wos_default_bvc_params.restype = None
     L.wos_default_bvc_params.argtypes = [C.POINTER(BvcParams)]
     L.wos_bvc.restype = C.c_int

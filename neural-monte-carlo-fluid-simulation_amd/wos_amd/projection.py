@@ -15,13 +15,16 @@ Here the divergence grid stays a CUDA tensor and reaches the engine by device
 pointer (wos_scene_set_source: one device-to-device copy, the geometry stays
 resident), the pressure samples stay a CUDA tensor, and grad p comes back as a CUDA
 tensor that the loss indexes in place -- no host round trip anywhere.  The SIREN runs
-in PyTorch-ROCm: its Linear layers are the dense contractions (hipBLASLt / MFMA).
+in PyTorch-ROCm: its Linear layers are the dense contractions (hipBLASLt / MFMA).  For the
+source alone there is a second path without autograd: source_from_network evaluates the
+network and its divergence in the fused forward-mode kernel of wos_amd.siren.
 """
 import numpy as np
 import torch
 import torch.nn as nn
 
 from . import engine as _engine
+from . import siren as _siren
 
 
 class Sine(nn.Module):
@@ -260,6 +263,23 @@ class PressureProjector:
             return (-divergence(u, grid, create_graph=True)[..., 0]).contiguous()
         div = divergence(u, grid)
         return (-div[..., 0]).detach().contiguous()
+
+    def source_from_network(self, network, resolution, size, wrap=None):
+        """source_from_velocity for a velocity that is the SIREN itself, through the fused forward-mode
+        kernel (wos_amd.siren.eval) instead of autograd: the same grid, the same shape, dtype and
+        sign, detached and contiguous, ready for solve(div).  `network`: a Siren, the reference's MLP
+        or their .net (siren.pack).  wrap=None: div = trace J straight from the kernel.
+        wrap(x, u_net) -> u: the time-stepper's pointwise masks and weights around the network
+        (query_velocity, src/2d/models/base.py:158-180); the kernel returns the network's value and
+        Jacobian and siren.divergence_with_wrap applies the chain rule through `wrap` alone.
+        There is no create_graph here: the kernel has no backward pass, and the differentiable path
+        stays source_from_velocity(..., create_graph=True)."""
+        sampler = sample_uniform_2d if self.dim == 2 else sample_uniform_3d
+        grid = sampler(resolution, size, with_boundary=True, device=self.device)
+        if wrap is None:
+            return (-_siren.eval(network, grid, value=False, divergence=True)).contiguous()
+        u, jac = _siren.eval(network, grid, value=True, jacobian=True)
+        return (-_siren.divergence_with_wrap(grid, u, jac, wrap)).contiguous()
 
     def sample_state(self, pts=None):
         """The state words solve() will give the pressure samples, or `pts` [N, dim]
