@@ -1,0 +1,296 @@
+// wos_capi_probes.cpp -- entry points that need neither a scene's workspace nor the device context:
+// the self-test probes (wos_selftest_*, kernels in wos_selftest.hip) and the fused SIREN
+// (wos_siren_eval, wos_siren.hip).  Each call owns what it allocates.
+#include "wos_capi.h"
+
+using namespace wos::capi;
+
+extern "C" {
+
+int wos_selftest_math(int32_t which, const double* x, double* out, int64_t n, int32_t device) {
+  if (!x || !out || n < 0) return fail(WOS_E_INVALID, "wos_selftest_math: bad argument");
+  if (n == 0) return WOS_OK;
+  HIP_TRY(hipSetDevice(device));
+  double *dx = nullptr, *dy = nullptr;
+  HIP_TRY(hipMalloc((void**)&dx, n * sizeof(double)));
+  hipError_t e = hipMalloc((void**)&dy, n * sizeof(double));
+  if (e == hipSuccess) e = hipMemcpy(dx, x, n * sizeof(double), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = wos::launch_math_selftest(which, dx, dy, n, nullptr);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = hipMemcpy(out, dy, n * sizeof(double), hipMemcpyDeviceToHost);
+  hipFree(dx);
+  hipFree(dy);
+  if (e != hipSuccess) return fail(WOS_E_DEVICE, std::string("wos_selftest_math: ") + hipGetErrorString(e));
+  return WOS_OK;
+}
+
+int wos_selftest_lhs(uint64_t key, const int64_t* gidx, int64_t n, int32_t n_pairs, int32_t dim, int32_t jump_lds,
+                     float* out, int32_t device) {
+  if (!gidx || !out || n < 0 || n > (1 << 20) || n_pairs < 1 || n_pairs > (1 << 14) || (dim != 2 && dim != 3))
+    return fail(WOS_E_INVALID, "wos_selftest_lhs: bad argument");
+  if (n == 0) return WOS_OK;
+  // diagonal draws + shuffle draws, a table of exactly that many jump constants
+  const int draws = 2 * (2 * n_pairs) * (dim - 1);
+  const int jn = jump_lds ? std::min(draws, wos::kLhsJumpMax) : 0;
+  // (the probe launches without raising the kernel's dynamic LDS limit)
+  if (wos::lhs_selftest_lds_bytes(n_pairs, dim, jn) > 64 * 1024)
+    return fail(WOS_E_CAPACITY, "wos_selftest_lhs: n_pairs exceed the probe's LDS");
+  std::vector<uint64_t> t(2 * (size_t)draws);
+  uint64_t A = 1u, Cc = 0u;
+  for (int k = 0; k < draws; k++) {
+    t[2 * k] = A; t[2 * k + 1] = Cc;
+    A = A * wos::kPcgMult;
+    Cc = Cc * wos::kPcgMult + wos::kPcgInc;
+  }
+  const size_t nout = (size_t)n * 2 * n_pairs * (dim - 1);
+  HIP_TRY(hipSetDevice(device));
+  uint64_t* dj = nullptr;
+  long long* di = nullptr;
+  float* dout = nullptr;
+  hipError_t e = hipMalloc((void**)&dj, t.size() * sizeof(uint64_t));
+  if (e == hipSuccess) e = hipMalloc((void**)&di, n * sizeof(long long));
+  if (e == hipSuccess) e = hipMalloc((void**)&dout, nout * sizeof(float));
+  if (e == hipSuccess) e = hipMemcpy(dj, t.data(), t.size() * sizeof(uint64_t), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(di, gidx, n * sizeof(long long), hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    wos::DevParams dp{};
+    dp.n_pairs = n_pairs;
+    dp.n_walks = 2 * n_pairs;
+    dp.n_anti = 2;
+    dp.seed = key;
+    dp.jump = dj;
+    dp.n_jump = draws;
+    dp.lhs_jump_n = jn;
+    e = wos::launch_lhs_selftest(dim, dp, di, (int)n, dout, nullptr);
+  }
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = hipMemcpy(out, dout, nout * sizeof(float), hipMemcpyDeviceToHost);
+  hipFree(dj);
+  hipFree(di);
+  hipFree(dout);
+  if (e != hipSuccess) return fail(WOS_E_DEVICE, std::string("wos_selftest_lhs: ") + hipGetErrorString(e));
+  return WOS_OK;
+}
+
+int wos_selftest_lhs_permute(int32_t impl, const int32_t* partner, const float* values, int32_t nstrat, int32_t sd,
+                             int32_t slots, int32_t count, float* out, int32_t device) {
+  const int max_strata = wos::lhs_permute_selftest_max_strata(impl), cap = wos::lhs_permute_selftest_slots(impl);
+  const bool packed = impl == WOS_LHS_PACK_R1 || impl == WOS_LHS_PACK_R2;
+  if (!partner || !values || !out || count < 0 || count > (1 << 16))
+    return fail(WOS_E_INVALID, "wos_selftest_lhs_permute: bad argument");
+  if (max_strata == 0) return fail(WOS_E_INVALID, "wos_selftest_lhs_permute: unknown impl");
+  if (nstrat < 1 || nstrat > max_strata)
+    return fail(WOS_E_INVALID, "wos_selftest_lhs_permute: nstrat does not fit impl " + std::to_string(impl) + " (at most " +
+                                   std::to_string(max_strata) + ")");
+  if (sd < 1 || sd > 2 || (packed && sd != 2) || slots < 1 || slots > cap)
+    return fail(WOS_E_INVALID, "wos_selftest_lhs_permute: sd or slots do not fit impl " + std::to_string(impl));
+  if (count == 0) return WOS_OK;
+  const size_t per = (size_t)cap * nstrat * sd, total = per * count;
+  // the swap partner of step j is one of j .. nstrat - 1 (every slot's table is loaded)
+  for (size_t k = 0; k < total; k++) {
+    const int j = (int)(k % nstrat);
+    if (partner[k] < j || partner[k] >= nstrat)
+      return fail(WOS_E_INVALID, "wos_selftest_lhs_permute: partner out of range at " + std::to_string(k));
+  }
+  HIP_TRY(hipSetDevice(device));
+  int* dp = nullptr;
+  float *dv = nullptr, *dout = nullptr;
+  hipError_t e = hipMalloc((void**)&dp, total * sizeof(int));
+  if (e == hipSuccess) e = hipMalloc((void**)&dv, total * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc((void**)&dout, total * sizeof(float));
+  if (e == hipSuccess) e = hipMemcpy(dp, partner, total * sizeof(int), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(dv, values, total * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = wos::launch_lhs_permute_selftest(impl, dp, dv, nstrat, sd, slots, count, dout, nullptr);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = hipMemcpy(out, dout, total * sizeof(float), hipMemcpyDeviceToHost);
+  hipFree(dp);
+  hipFree(dv);
+  hipFree(dout);
+  if (e != hipSuccess) return fail(WOS_E_DEVICE, std::string("wos_selftest_lhs_permute: ") + hipGetErrorString(e));
+  return WOS_OK;
+}
+
+int wos_selftest_lhs_plan(int32_t n_pairs, int32_t dim, int32_t* out) {
+  if (!out || n_pairs < 1 || n_pairs > (1 << 20) || (dim != 2 && dim != 3))
+    return fail(WOS_E_INVALID, "wos_selftest_lhs_plan: bad argument");
+  wos::lhs_plan(n_pairs, dim, out);
+  out[6] = (int32_t)kLdsDynamicMax;
+  return WOS_OK;
+}
+
+int wos_selftest_tape_rowsum(const uint32_t* row, int64_t n_rows, const uint32_t* id, const float* w, const float* a,
+                             const float* c, int64_t n_tasks, int32_t n_channels, float* out, int32_t* tile_terms,
+                             int32_t device) {
+  if (tile_terms) *tile_terms = wos::kTapeIndexTile;
+  if (!row || !id || !w || !a || !c || !out) return fail(WOS_E_INVALID, "wos_selftest_tape_rowsum: null argument");
+  if (n_rows < 1 || n_rows >= 0xFFFFFFFFLL || n_tasks < 1 || n_tasks > (1LL << 30) || n_channels < 1 ||
+      n_channels > wos::kMaxChannels || row[0] != 0)
+    return fail(WOS_E_INVALID, "wos_selftest_tape_rowsum: bad argument");
+  for (int64_t r = 0; r < n_rows; r++)
+    if (row[r + 1] < row[r]) return fail(WOS_E_INVALID, "wos_selftest_tape_rowsum: row offsets decrease at " + std::to_string(r));
+  const uint32_t n_terms = row[n_rows];
+  std::vector<uint32_t> cell(n_terms);
+  for (int64_t r = 0; r < n_rows; r++)
+    for (uint32_t i = row[r]; i < row[r + 1]; i++) cell[i] = (uint32_t)r;
+  for (uint32_t i = 0; i < n_terms; i++)
+    if ((int64_t)(id[i] & 0x7FFFFFFFu) >= n_tasks)
+      return fail(WOS_E_INVALID, "wos_selftest_tape_rowsum: id out of range at " + std::to_string(i));
+  HIP_TRY(hipSetDevice(device));
+  DevBufs tmp;
+  uint32_t *d_row = nullptr, *d_cell = nullptr, *d_id = nullptr;
+  float *d_w = nullptr, *d_part = nullptr, *d_a = nullptr, *d_c = nullptr, *d_out = nullptr;
+  const size_t ct = (size_t)n_channels * n_tasks, co = (size_t)n_channels * n_rows;
+  HIP_TRY(tmp.get(&d_row, (size_t)n_rows + 1));
+  HIP_TRY(tmp.get(&d_cell, n_terms));
+  HIP_TRY(tmp.get(&d_id, n_terms));
+  HIP_TRY(tmp.get(&d_w, n_terms));
+  HIP_TRY(tmp.get(&d_part, (size_t)wos::tape_index_tiles(n_terms) * 2 * wos::kMaxChannels));
+  HIP_TRY(tmp.get(&d_a, ct));
+  HIP_TRY(tmp.get(&d_c, ct));
+  HIP_TRY(tmp.get(&d_out, co));
+  HIP_TRY(hipMemcpy(d_row, row, ((size_t)n_rows + 1) * 4, hipMemcpyHostToDevice));
+  if (n_terms > 0) {
+    HIP_TRY(hipMemcpy(d_cell, cell.data(), (size_t)n_terms * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_id, id, (size_t)n_terms * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_w, w, (size_t)n_terms * 4, hipMemcpyHostToDevice));
+  }
+  HIP_TRY(hipMemcpy(d_a, a, ct * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_c, c, ct * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemset(d_out, 0, co * 4));
+  const wos::DevTapeIndex ix{d_row, d_cell, d_id, d_w, d_part, n_terms};
+  HIP_TRY(wos::launch_tape_rowsum(ix, n_rows, n_channels, n_tasks, d_a, d_c, d_out, nullptr));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(out, d_out, co * 4, hipMemcpyDeviceToHost));
+  return WOS_OK;
+}
+
+// ---- fused SIREN (wos_siren.hip) -------------------------------------------------------------
+static int siren_shape_check(const std::string& fn, int32_t d_in, int32_t hidden) {
+  if (d_in != 2 && d_in != 3) return fail(WOS_E_INVALID, fn + ": d_in must be 2 or 3, got " + std::to_string(d_in));
+  if (hidden < 32 || hidden > wos::kSirenMaxHidden || hidden % 32 != 0)
+    return fail(WOS_E_INVALID, fn + ": hidden must be a multiple of 32 in 32.." + std::to_string(wos::kSirenMaxHidden) +
+                                   ", got " + std::to_string(hidden));
+  return WOS_OK;
+}
+
+// No scene, no workspace, no lock: the call owns what it allocates.  Device pointers: the packed
+// weights are a stream-ordered allocation, so WOS_ASYNC needs no host wait to free them.  Host
+// pointers: one staging allocation, freed after the call's own synchronise.
+int wos_siren_eval(const wos_siren_net* net, const float* pts, int64_t n, float* u, float* jac, float* div,
+                   uint32_t flags, int32_t device, void* stream) {
+  const std::string fn = "wos_siren_eval";
+  if (!net) return fail(WOS_E_INVALID, fn + ": null net");
+  if (int rc = siren_shape_check(fn, net->d_in, net->hidden)) return rc;
+  if (net->d_out < 1 || net->d_out > 3)
+    return fail(WOS_E_INVALID, fn + ": d_out must be 1..3, got " + std::to_string(net->d_out));
+  if (net->n_hidden_layers < 0 || net->n_hidden_layers > wos::kSirenMaxHiddenLayers)
+    return fail(WOS_E_INVALID, fn + ": n_hidden_layers must be 0.." + std::to_string(wos::kSirenMaxHiddenLayers) +
+                                   ", got " + std::to_string(net->n_hidden_layers));
+  if (!std::isfinite(net->omega)) return fail(WOS_E_INVALID, fn + ": omega must be finite");
+  const int D = net->d_in, DO = net->d_out, H = net->hidden, L = net->n_hidden_layers, NL = L + 2;
+  if (!net->weights || !net->biases) return fail(WOS_E_INVALID, fn + ": null weights or biases array");
+  for (int l = 0; l < NL; l++)
+    if (!net->weights[l] || !net->biases[l])
+      return fail(WOS_E_INVALID, fn + ": null weights or biases pointer of layer " + std::to_string(l));
+  if (!u && !jac && !div) return fail(WOS_E_INVALID, fn + ": no output requested (u, jac and div are all null)");
+  if (div && DO != D)
+    return fail(WOS_E_INVALID, fn + ": div needs d_out == d_in, got d_out " + std::to_string(DO) + ", d_in " +
+                                   std::to_string(D));
+  if (n < 0) return fail(WOS_E_INVALID, fn + ": negative point count");
+  if (n > (int64_t)0x7FFFFFFF * wos::kSirenTile) return fail(WOS_E_INVALID, fn + ": too many points for one call");
+  if (n == 0) return WOS_OK;
+  if (!pts) return fail(WOS_E_INVALID, fn + ": null point buffer");
+  HIP_TRY(hipSetDevice(device));
+  hipStream_t st = (hipStream_t)stream;
+  wos::SirenNet dn{};
+  dn.d_in = D;
+  dn.d_out = DO;
+  dn.H = H;
+  dn.L = L;
+  dn.omega = net->omega;
+  const size_t pack_n = wos::siren_pack_floats(H, L);
+  if (flags & WOS_PTRS_DEVICE) {
+    for (int l = 0; l < NL; l++) { dn.w[l] = net->weights[l]; dn.b[l] = net->biases[l]; }
+    float* packed = nullptr;
+    if (pack_n > 0) HIP_TRY(hipMallocAsync((void**)&packed, pack_n * sizeof(float), st));
+    hipError_t e = wos::launch_siren_pack(dn, packed, st);
+    if (e == hipSuccess) e = wos::launch_siren_eval(dn, packed, pts, n, u, jac, div, st);
+    if (packed) {
+      const hipError_t e2 = hipFreeAsync(packed, st);
+      if (e == hipSuccess) e = e2;
+    }
+    if (e == hipSuccess && !(flags & WOS_ASYNC)) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return fail(WOS_E_DEVICE, fn + ": " + hipGetErrorString(e));
+    return WOS_OK;
+  }
+  // one temporary: packed | weights and biases layer by layer | pts | u | jac | div (floats)
+  const size_t N = (size_t)n;
+  size_t o_w[wos::kSirenMaxLayers], o_b[wos::kSirenMaxLayers], n_w[wos::kSirenMaxLayers], n_b[wos::kSirenMaxLayers];
+  size_t off = pack_n;
+  for (int l = 0; l < NL; l++) {
+    n_b[l] = l == NL - 1 ? (size_t)DO : (size_t)H;
+    n_w[l] = n_b[l] * (l == 0 ? (size_t)D : (size_t)H);
+    o_w[l] = off;
+    off += n_w[l];
+    o_b[l] = off;
+    off += n_b[l];
+  }
+  const size_t o_pts = off, o_u = o_pts + N * D, o_j = o_u + (u ? N * DO : 0), o_d = o_j + (jac ? N * DO * D : 0),
+               total = o_d + (div ? N : 0);
+  float* tmp = nullptr;
+  if (hipMalloc((void**)&tmp, total * sizeof(float)) != hipSuccess)
+    return fail(WOS_E_NOMEM, fn + ": cannot allocate " + std::to_string(total * sizeof(float)) + " bytes of staging");
+  const auto run = [&]() -> hipError_t {
+    hipError_t e;
+    for (int l = 0; l < NL; l++) {
+      if ((e = hipMemcpyAsync(tmp + o_w[l], net->weights[l], n_w[l] * sizeof(float), hipMemcpyHostToDevice, st)) != hipSuccess)
+        return e;
+      if ((e = hipMemcpyAsync(tmp + o_b[l], net->biases[l], n_b[l] * sizeof(float), hipMemcpyHostToDevice, st)) != hipSuccess)
+        return e;
+      dn.w[l] = tmp + o_w[l];
+      dn.b[l] = tmp + o_b[l];
+    }
+    if ((e = hipMemcpyAsync(tmp + o_pts, pts, N * D * sizeof(float), hipMemcpyHostToDevice, st)) != hipSuccess) return e;
+    if ((e = wos::launch_siren_pack(dn, tmp, st)) != hipSuccess) return e;
+    if ((e = wos::launch_siren_eval(dn, tmp, tmp + o_pts, n, u ? tmp + o_u : nullptr, jac ? tmp + o_j : nullptr,
+                                    div ? tmp + o_d : nullptr, st)) != hipSuccess)
+      return e;
+    if (u && (e = hipMemcpyAsync(u, tmp + o_u, N * DO * sizeof(float), hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
+    if (jac && (e = hipMemcpyAsync(jac, tmp + o_j, N * DO * D * sizeof(float), hipMemcpyDeviceToHost, st)) != hipSuccess)
+      return e;
+    if (div && (e = hipMemcpyAsync(div, tmp + o_d, N * sizeof(float), hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
+    return hipStreamSynchronize(st);
+  };
+  const hipError_t e = run();
+  if (e != hipSuccess) hipStreamSynchronize(st);  // nothing may still use tmp when it is freed
+  hipFree(tmp);
+  if (e != hipSuccess) return fail(WOS_E_DEVICE, fn + ": " + hipGetErrorString(e));
+  return WOS_OK;
+}
+
+int wos_selftest_siren_layer(int32_t hidden, int32_t d_in, int64_t n_points, const float* W, const float* b,
+                             const float* X, float* Z, int32_t device) {
+  const std::string fn = "wos_selftest_siren_layer";
+  if (int rc = siren_shape_check(fn, d_in, hidden)) return rc;
+  if (!W || !b || !X || !Z) return fail(WOS_E_INVALID, fn + ": null argument");
+  if (n_points < 1 || n_points > (1LL << 20)) return fail(WOS_E_INVALID, fn + ": n_points must be 1..2^20");
+  HIP_TRY(hipSetDevice(device));
+  DevBufs tmp;
+  const size_t hh = (size_t)hidden * hidden, nx = (size_t)n_points * (1 + d_in) * hidden;
+  float *d_W = nullptr, *d_b = nullptr, *d_pack = nullptr, *d_X = nullptr, *d_Z = nullptr;
+  HIP_TRY(tmp.get(&d_W, hh));
+  HIP_TRY(tmp.get(&d_b, (size_t)hidden));
+  HIP_TRY(tmp.get(&d_pack, hh));
+  HIP_TRY(tmp.get(&d_X, nx));
+  HIP_TRY(tmp.get(&d_Z, nx));
+  HIP_TRY(hipMemcpy(d_W, W, hh * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_b, b, (size_t)hidden * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_X, X, nx * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemset(d_Z, 0, nx * 4));
+  HIP_TRY(wos::launch_siren_layer_selftest(hidden, d_in, n_points, d_W, d_b, d_pack, d_X, d_Z, nullptr));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(Z, d_Z, nx * 4, hipMemcpyDeviceToHost));
+  return WOS_OK;
+}
+
+}  // extern "C"

@@ -129,7 +129,7 @@ __global__ void wos_math_selftest_kernel(int which, const double* x, double* out
 
 
 // ---------------------------------------------------------------------------
-// host-side launchers (called from wos_capi.hip)
+// host-side launchers (called from wos_capi_*.cpp)
 // ---------------------------------------------------------------------------
 // the kernels of a variant: every unit is asked, the one that owns an instantiation answers
 static UnitKernels kernels_of(const KernelVariant& v) {

@@ -157,7 +157,7 @@ void lhs_plan(int n_pairs, int dim, int32_t* out) {
   out[3] = P > 1 ? 1 : (n_pairs + kWave - 1) / kWave;
   out[4] = draws <= kLhsJumpMax ? 0 : 1;
   out[5] = (int32_t)((size_t)2 * P * lhs_floats * sizeof(float) + fb_union_bytes(P * lhs_floats, nstrat));
-  out[6] = 0;  // the LDS budget: the caller's (wos_capi.hip kLdsDynamicMax)
+  out[6] = 0;  // the LDS budget: the caller's (wos_capi.h kLdsDynamicMax)  
   out[7] = (int32_t)kPtGrab;
   out[8] = nstrat <= 4 * kWave ? (nstrat + kWave - 1) / kWave : 0;
 }

@@ -21,7 +21,7 @@ def sweep_cases():
 
 
 def n_pairs_of(n_walks, anti):
-    """wos_capi.hip dev_params: walks per antithetic iteration set."""
+    """wos_capi_solve.cpp dev_params: walks per antithetic iteration set."""
     return max(1, n_walks // 2) if anti else n_walks
 
 

@@ -1,5 +1,6 @@
 """GPU tests of the per-step scene hand-off (wos_scene_set_source, the shared
-per-device workspace and the geometry cache of csrc/wos_capi.hip).  The reference
+per-device workspace of csrc/wos_capi_ctx.cpp and the geometry cache of
+csrc/wos_capi_scene.cpp).  The reference
 builds a fresh Scene(sceneConfig, div) every projection (model_split.py:185-202);
 every cheaper path here must give bit-identical p and grad p."""
 import numpy as np
