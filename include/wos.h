@@ -14,6 +14,7 @@
 #ifndef WOS_H
 #define WOS_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -562,6 +563,44 @@ int wos_siren_eval(const wos_siren_net *net, const float *pts, int64_t n,
  * hidden and d_in as wos_siren_eval; n_points >= 1. */
 int wos_selftest_siren_layer(int32_t hidden, int32_t d_in, int64_t n_points, const float *W, const float *b,
                              const float *X, float *Z, int32_t device);
+
+/* ---- Fused SIREN backward: gradients of (u, jac, div) with respect to the weights -------------
+ * The vector-Jacobian product of wos_siren_eval's three outputs with the cotangents g_u[n*d_out],
+ * g_jac[n*d_out*d_in] and g_div[n] (each may be NULL and counts as zero; all three NULL is
+ * WOS_E_INVALID, as is g_div with d_out != d_in), summed over the n points (added within ABI 10:
+ * new entry points only; csrc/wos_siren_vjp.hip, DESIGN.md "Fused SIREN backward"):
+ *   grad_weights[l], grad_biases[l]   l = 0 .. n_hidden_layers + 1, the shapes of net's weights[l]
+ *                                     and biases[l]; written, not accumulated
+ * i.e. the gradient of  sum_p (g_u . u + g_jac . jac + g_div div)  with the seeds
+ * Jb[i][k] = g_jac[i][k] + g_div [i == k].  There is no gradient with respect to the points or omega.
+ * The forward is recomputed by wos_siren_eval's own code (the same pre-activation bits, OCML
+ * sincosf); all arithmetic is f32.  The points are walked in chunks of whole 32-point tiles; per
+ * chunk the layers' columns are stashed in a temporary of at most workspace_bytes (0: 256 MiB),
+ * (2 n_hidden_layers + 1) * hidden * (1 + d_in) * 4 bytes per point; a non-zero workspace_bytes
+ * that cannot hold one tile is WOS_E_CAPACITY.  The per-slice and per-tile partial sums come on top
+ * (up to about a quarter of the stash).  Sums run in a fixed order without atomics: the same call with the same
+ * n and workspace_bytes returns the same bits; different n or workspace_bytes may differ in the last
+ * bits.  Envelope and pointer rules are wos_siren_eval's: host pointers (staged, blocking),
+ * WOS_PTRS_DEVICE, or WOS_PTRS_DEVICE | WOS_ASYNC on `stream`; grad_weights and grad_biases are
+ * host arrays of pointers like net's.  n == 0 writes zeros; n < 0 or a NULL gradient pointer is
+ * WOS_E_INVALID. */
+int wos_siren_vjp(const wos_siren_net *net, const float *pts, int64_t n,
+                  const float *g_u, const float *g_jac, const float *g_div,
+                  float *const *grad_weights, float *const *grad_biases,
+                  size_t workspace_bytes,
+                  uint32_t flags, int32_t device, void *stream);
+
+/* Device self-test of wos_siren_vjp's two hidden-layer products, host pointers, blocking; dZ, X and
+ * dX are [n_points][1 + d_in][hidden], W and dW [hidden][hidden] row-major:
+ *   dX[p][s] = W^T dZ[p][s]             the transposed fragment-ordered copy of W through the
+ *                                       forward's own product
+ *   dW = sum over p, s of dZ[p][s] X[p][s]^T   the weight-gradient kernel with its split-K
+ *                                       reduction; the padding columns of the last tile hold ones
+ *                                       and must not count
+ * hidden and d_in as wos_siren_eval; n_points 1 .. 65536. */
+int wos_selftest_siren_vjp_layer(int32_t hidden, int32_t d_in, int64_t n_points,
+                                 const float *W, const float *dZ, const float *X,
+                                 float *dX, float *dW, int32_t device);
 
 const char *wos_last_error(void);
 int32_t wos_abi_version(void);

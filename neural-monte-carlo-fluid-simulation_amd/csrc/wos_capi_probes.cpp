@@ -1,6 +1,6 @@
 // wos_capi_probes.cpp -- entry points that need neither a scene's workspace nor the device context:
 // the self-test probes (wos_selftest_*, kernels in wos_selftest.hip) and the fused SIREN
-// (wos_siren_eval, wos_siren.hip).  Each call owns what it allocates.
+// (wos_siren_eval, wos_siren.hip; wos_siren_vjp, wos_siren_vjp.hip).  Each call owns what it allocates.
 #include "wos_capi.h"
 
 using namespace wos::capi;
@@ -173,12 +173,8 @@ static int siren_shape_check(const std::string& fn, int32_t d_in, int32_t hidden
   return WOS_OK;
 }
 
-// No scene, no workspace, no lock: the call owns what it allocates.  Device pointers: the packed
-// weights are a stream-ordered allocation, so WOS_ASYNC needs no host wait to free them.  Host
-// pointers: one staging allocation, freed after the call's own synchronise.
-int wos_siren_eval(const wos_siren_net* net, const float* pts, int64_t n, float* u, float* jac, float* div,
-                   uint32_t flags, int32_t device, void* stream) {
-  const std::string fn = "wos_siren_eval";
+// the envelope of both entry points: shape, omega and the pointer arrays
+static int siren_net_check(const std::string& fn, const wos_siren_net* net) {
   if (!net) return fail(WOS_E_INVALID, fn + ": null net");
   if (int rc = siren_shape_check(fn, net->d_in, net->hidden)) return rc;
   if (net->d_out < 1 || net->d_out > 3)
@@ -187,11 +183,22 @@ int wos_siren_eval(const wos_siren_net* net, const float* pts, int64_t n, float*
     return fail(WOS_E_INVALID, fn + ": n_hidden_layers must be 0.." + std::to_string(wos::kSirenMaxHiddenLayers) +
                                    ", got " + std::to_string(net->n_hidden_layers));
   if (!std::isfinite(net->omega)) return fail(WOS_E_INVALID, fn + ": omega must be finite");
-  const int D = net->d_in, DO = net->d_out, H = net->hidden, L = net->n_hidden_layers, NL = L + 2;
+  const int NL = net->n_hidden_layers + 2;
   if (!net->weights || !net->biases) return fail(WOS_E_INVALID, fn + ": null weights or biases array");
   for (int l = 0; l < NL; l++)
     if (!net->weights[l] || !net->biases[l])
       return fail(WOS_E_INVALID, fn + ": null weights or biases pointer of layer " + std::to_string(l));
+  return WOS_OK;
+}
+
+// No scene, no workspace, no lock: the call owns what it allocates.  Device pointers: the packed
+// weights are a stream-ordered allocation, so WOS_ASYNC needs no host wait to free them.  Host
+// pointers: one staging allocation, freed after the call's own synchronise.
+int wos_siren_eval(const wos_siren_net* net, const float* pts, int64_t n, float* u, float* jac, float* div,
+                   uint32_t flags, int32_t device, void* stream) {
+  const std::string fn = "wos_siren_eval";
+  if (int rc = siren_net_check(fn, net)) return rc;
+  const int D = net->d_in, DO = net->d_out, H = net->hidden, L = net->n_hidden_layers, NL = L + 2;
   if (!u && !jac && !div) return fail(WOS_E_INVALID, fn + ": no output requested (u, jac and div are all null)");
   if (div && DO != D)
     return fail(WOS_E_INVALID, fn + ": div needs d_out == d_in, got d_out " + std::to_string(DO) + ", d_in " +
@@ -290,6 +297,176 @@ int wos_selftest_siren_layer(int32_t hidden, int32_t d_in, int64_t n_points, con
   HIP_TRY(wos::launch_siren_layer_selftest(hidden, d_in, n_points, d_W, d_b, d_pack, d_X, d_Z, nullptr));
   HIP_TRY(hipDeviceSynchronize());
   HIP_TRY(hipMemcpy(Z, d_Z, nx * 4, hipMemcpyDeviceToHost));
+  return WOS_OK;
+}
+
+// ---- fused SIREN backward (wos_siren_vjp.hip) ------------------------------------------------
+constexpr size_t kSirenVjpDefaultStash = (size_t)256 << 20;  // the stash's cap when workspace_bytes is 0
+
+// One temporary per call: packed | packedT | H zeros | the plan's work; with host pointers also
+// the staged network, points, cotangents and gradients.  Stream-ordered with device pointers.
+int wos_siren_vjp(const wos_siren_net* net, const float* pts, int64_t n, const float* g_u, const float* g_jac,
+                  const float* g_div, float* const* grad_weights, float* const* grad_biases, size_t workspace_bytes,
+                  uint32_t flags, int32_t device, void* stream) {
+  const std::string fn = "wos_siren_vjp";
+  if (int rc = siren_net_check(fn, net)) return rc;
+  const int D = net->d_in, DO = net->d_out, H = net->hidden, L = net->n_hidden_layers, NL = L + 2;
+  if (!g_u && !g_jac && !g_div)
+    return fail(WOS_E_INVALID, fn + ": no cotangent given (g_u, g_jac and g_div are all null)");
+  if (g_div && DO != D)
+    return fail(WOS_E_INVALID, fn + ": g_div needs d_out == d_in, got d_out " + std::to_string(DO) + ", d_in " +
+                                   std::to_string(D));
+  if (!grad_weights || !grad_biases) return fail(WOS_E_INVALID, fn + ": null grad_weights or grad_biases array");
+  for (int l = 0; l < NL; l++)
+    if (!grad_weights[l] || !grad_biases[l])
+      return fail(WOS_E_INVALID, fn + ": null grad_weights or grad_biases pointer of layer " + std::to_string(l));
+  if (n < 0) return fail(WOS_E_INVALID, fn + ": n is negative");
+  if (n > (int64_t)0x7FFFFFFF * wos::kSirenTile) return fail(WOS_E_INVALID, fn + ": n: too many points for one call");
+  const size_t tile_bytes = wos::siren_vjp_stash_floats_per_tile(D, H, L) * sizeof(float);
+  if (workspace_bytes != 0 && workspace_bytes < tile_bytes)
+    return fail(WOS_E_CAPACITY, fn + ": workspace_bytes " + std::to_string(workspace_bytes) +
+                                    " cannot hold one tile's stash of " + std::to_string(tile_bytes) + " bytes");
+  if (n > 0 && !pts) return fail(WOS_E_INVALID, fn + ": null point buffer");
+  size_t n_w[wos::kSirenMaxLayers], n_b[wos::kSirenMaxLayers];
+  for (int l = 0; l < NL; l++) {
+    n_b[l] = l == NL - 1 ? (size_t)DO : (size_t)H;
+    n_w[l] = n_b[l] * (l == 0 ? (size_t)D : (size_t)H);
+  }
+  const bool dev_ptrs = (flags & WOS_PTRS_DEVICE) != 0;
+  if (n == 0 && !dev_ptrs) {
+    for (int l = 0; l < NL; l++) {
+      std::fill(grad_weights[l], grad_weights[l] + n_w[l], 0.0f);
+      std::fill(grad_biases[l], grad_biases[l] + n_b[l], 0.0f);
+    }
+    return WOS_OK;
+  }
+  HIP_TRY(hipSetDevice(device));
+  hipStream_t st = (hipStream_t)stream;
+  wos::SirenNet dn{};
+  dn.d_in = D;
+  dn.d_out = DO;
+  dn.H = H;
+  dn.L = L;
+  dn.omega = net->omega;
+  wos::SirenGrads dg{};
+  int cus = 0;
+  HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
+  const int per_cu = std::max<int>(1, (int)(kLdsDynamicMax / wos::siren_vjp_tile_lds_bytes(D, H)));
+  const wos::SirenVjpPlan plan =
+      wos::siren_vjp_plan(dn, n, workspace_bytes ? workspace_bytes : kSirenVjpDefaultStash, cus * per_cu);
+  const size_t pack_n = wos::siren_pack_floats(H, L);
+  const size_t o_packT = pack_n, o_zero = 2 * pack_n, o_work = o_zero + (size_t)H, dev_total = o_work + plan.total();
+  const auto run = [&](float* tmp, const float* d_pts, const float* d_gu, const float* d_gj, const float* d_gd) -> hipError_t {
+    if (n == 0) return wos::launch_siren_vjp(dn, nullptr, nullptr, nullptr, nullptr, 0, d_gu, d_gj, d_gd, dg, plan, nullptr, st);
+    hipError_t e;
+    if ((e = hipMemsetAsync(tmp + o_zero, 0, (size_t)H * sizeof(float), st)) != hipSuccess) return e;
+    if ((e = wos::launch_siren_pack(dn, tmp, st)) != hipSuccess) return e;
+    if ((e = wos::launch_siren_pack_transposed(dn, tmp + o_packT, st)) != hipSuccess) return e;
+    return wos::launch_siren_vjp(dn, tmp, tmp + o_packT, tmp + o_zero, d_pts, n, d_gu, d_gj, d_gd, dg, plan, tmp + o_work, st);
+  };
+  if (dev_ptrs) {
+    for (int l = 0; l < NL; l++) {
+      dn.w[l] = net->weights[l];
+      dn.b[l] = net->biases[l];
+      dg.w[l] = grad_weights[l];
+      dg.b[l] = grad_biases[l];
+    }
+    float* tmp = nullptr;
+    if (n > 0 && hipMallocAsync((void**)&tmp, dev_total * sizeof(float), st) != hipSuccess)
+      return fail(WOS_E_NOMEM, fn + ": cannot allocate " + std::to_string(dev_total * sizeof(float)) + " bytes of workspace");
+    hipError_t e = run(tmp, pts, g_u, g_jac, g_div);
+    if (tmp) {
+      const hipError_t e2 = hipFreeAsync(tmp, st);
+      if (e == hipSuccess) e = e2;
+    }
+    if (e == hipSuccess && !(flags & WOS_ASYNC)) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return fail(WOS_E_DEVICE, fn + ": " + hipGetErrorString(e));
+    return WOS_OK;
+  }
+  // host pointers: ... | weights, biases and their gradients layer by layer | pts | g_u | g_jac | g_div
+  const size_t N = (size_t)n;
+  size_t o_w[wos::kSirenMaxLayers], o_b[wos::kSirenMaxLayers], o_gw[wos::kSirenMaxLayers], o_gb[wos::kSirenMaxLayers];
+  size_t off = dev_total;
+  for (int l = 0; l < NL; l++) {
+    o_w[l] = off;
+    off += n_w[l];
+    o_b[l] = off;
+    off += n_b[l];
+    o_gw[l] = off;
+    off += n_w[l];
+    o_gb[l] = off;
+    off += n_b[l];
+  }
+  const size_t o_pts = off, o_u = o_pts + N * D, o_j = o_u + (g_u ? N * DO : 0), o_d = o_j + (g_jac ? N * DO * D : 0),
+               total = o_d + (g_div ? N : 0);
+  float* tmp = nullptr;
+  if (hipMalloc((void**)&tmp, total * sizeof(float)) != hipSuccess)
+    return fail(WOS_E_NOMEM, fn + ": cannot allocate " + std::to_string(total * sizeof(float)) + " bytes of staging");
+  const auto staged = [&]() -> hipError_t {
+    hipError_t e;
+    const auto up = [&](size_t o, const float* src, size_t count) {
+      return hipMemcpyAsync(tmp + o, src, count * sizeof(float), hipMemcpyHostToDevice, st);
+    };
+    for (int l = 0; l < NL; l++) {
+      if ((e = up(o_w[l], net->weights[l], n_w[l])) != hipSuccess) return e;
+      if ((e = up(o_b[l], net->biases[l], n_b[l])) != hipSuccess) return e;
+      dn.w[l] = tmp + o_w[l];
+      dn.b[l] = tmp + o_b[l];
+      dg.w[l] = tmp + o_gw[l];
+      dg.b[l] = tmp + o_gb[l];
+    }
+    if ((e = up(o_pts, pts, N * D)) != hipSuccess) return e;
+    if (g_u && (e = up(o_u, g_u, N * DO)) != hipSuccess) return e;
+    if (g_jac && (e = up(o_j, g_jac, N * DO * D)) != hipSuccess) return e;
+    if (g_div && (e = up(o_d, g_div, N)) != hipSuccess) return e;
+    if ((e = run(tmp, tmp + o_pts, g_u ? tmp + o_u : nullptr, g_jac ? tmp + o_j : nullptr, g_div ? tmp + o_d : nullptr)) !=
+        hipSuccess)
+      return e;
+    for (int l = 0; l < NL; l++) {
+      if ((e = hipMemcpyAsync(grad_weights[l], dg.w[l], n_w[l] * sizeof(float), hipMemcpyDeviceToHost, st)) != hipSuccess)
+        return e;
+      if ((e = hipMemcpyAsync(grad_biases[l], dg.b[l], n_b[l] * sizeof(float), hipMemcpyDeviceToHost, st)) != hipSuccess)
+        return e;
+    }
+    return hipStreamSynchronize(st);
+  };
+  const hipError_t e = staged();
+  if (e != hipSuccess) hipStreamSynchronize(st);  // nothing may still use tmp when it is freed
+  hipFree(tmp);
+  if (e != hipSuccess) return fail(WOS_E_DEVICE, fn + ": " + hipGetErrorString(e));
+  return WOS_OK;
+}
+
+int wos_selftest_siren_vjp_layer(int32_t hidden, int32_t d_in, int64_t n_points, const float* W, const float* dZ,
+                                 const float* X, float* dX, float* dW, int32_t device) {
+  const std::string fn = "wos_selftest_siren_vjp_layer";
+  if (int rc = siren_shape_check(fn, d_in, hidden)) return rc;
+  if (!W || !dZ || !X || !dX || !dW) return fail(WOS_E_INVALID, fn + ": null argument");
+  if (n_points < 1 || n_points > (1LL << 16)) return fail(WOS_E_INVALID, fn + ": n_points must be 1..2^16");
+  HIP_TRY(hipSetDevice(device));
+  DevBufs tmp;
+  const size_t hh = (size_t)hidden * hidden, nx = (size_t)n_points * (1 + d_in) * hidden;
+  float *d_W = nullptr, *d_zero = nullptr, *d_pack = nullptr, *d_dZ = nullptr, *d_X = nullptr, *d_dX = nullptr,
+        *d_dW = nullptr, *d_work = nullptr;
+  HIP_TRY(tmp.get(&d_W, hh));
+  HIP_TRY(tmp.get(&d_zero, (size_t)hidden));
+  HIP_TRY(tmp.get(&d_pack, hh));
+  HIP_TRY(tmp.get(&d_dZ, nx));
+  HIP_TRY(tmp.get(&d_X, nx));
+  HIP_TRY(tmp.get(&d_dX, nx));
+  HIP_TRY(tmp.get(&d_dW, hh));
+  HIP_TRY(tmp.get(&d_work, wos::siren_vjp_layer_selftest_floats(hidden, d_in, n_points)));
+  HIP_TRY(hipMemcpy(d_W, W, hh * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemset(d_zero, 0, (size_t)hidden * 4));
+  HIP_TRY(hipMemcpy(d_dZ, dZ, nx * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_X, X, nx * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemset(d_dX, 0, nx * 4));
+  HIP_TRY(hipMemset(d_dW, 0, hh * 4));
+  HIP_TRY(wos::launch_siren_vjp_layer_selftest(hidden, d_in, n_points, d_W, d_pack, d_zero, d_dZ, d_X, d_dX, d_dW, d_work,
+                                               nullptr));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(dX, d_dX, nx * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(dW, d_dW, hh * 4, hipMemcpyDeviceToHost));
   return WOS_OK;
 }
 

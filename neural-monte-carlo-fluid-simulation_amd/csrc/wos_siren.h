@@ -38,4 +38,53 @@ hipError_t launch_siren_eval(const SirenNet& net, const float* packed, const flo
 hipError_t launch_siren_layer_selftest(int H, int d_in, int64_t n, const float* W, const float* b, float* packed,
                                        const float* X, float* Z, hipStream_t s);
 
+// The same kernel on weights that are already fragment-ordered (launch_siren_pack's layout, or
+// launch_siren_pack_transposed's for Z = W^T X).
+hipError_t launch_siren_layer_packed(int H, int d_in, int64_t n, const float* packed, const float* b, const float* X,
+                                     float* Z, hipStream_t s);
+
+// ---- backward (wos_siren_vjp.hip) --------------------------------------------------------------
+// packedT[l][r][q][lane][e] = W[8 q + 2 e + (lane >> 5)][32 r + (lane & 31)]: launch_siren_pack's copy of W^T.
+hipError_t launch_siren_pack_transposed(const SirenNet& net, float* packedT, hipStream_t s);
+
+// Gradient pointers of one network, shapes of SirenNet's w and b.
+struct SirenGrads {
+  float* w[kSirenMaxLayers];
+  float* b[kSirenMaxLayers];
+};
+
+// The backward's temporaries for chunks of `tiles` 32-point tiles, in floats.
+struct SirenVjpPlan {
+  int tiles;         // tiles per chunk
+  int slices;        // split-K slices of the weight-gradient kernel per chunk
+  size_t stash;      // (2 L + 1) H C 32 floats per tile: X_0 .. X_L (first the pre-activations) and dZ_1 .. dZ_L
+  size_t tile_part;  // per-tile partials of dWo, dbo, db_0 .. db_L and dW0
+  size_t slice_part; // per-slice partials of dW_1 .. dW_L
+  size_t total() const { return stash + tile_part + slice_part; }
+};
+inline size_t siren_vjp_stash_floats_per_tile(int d_in, int H, int L) { return (size_t)(2 * L + 1) * H * (1 + d_in) * kSirenTile; }
+inline size_t siren_vjp_tile_part_floats(const SirenNet& net) {
+  return (size_t)net.d_out * net.H + net.d_out + (size_t)(net.L + 1) * net.H + (size_t)net.H * net.d_in;
+}
+constexpr int kSirenWgradSliceBlocks = 16;  // 32-column blocks of K per split-K slice
+// resident_tiles: how many tile workgroups the device holds at once (0: unknown); when the points
+// need several chunks, a chunk is a whole multiple of it, so that no chunk ends in a thin round.
+SirenVjpPlan siren_vjp_plan(const SirenNet& net, int64_t n, size_t stash_cap_bytes, int resident_tiles);
+size_t siren_vjp_tile_lds_bytes(int d_in, int H);  // dynamic LDS of one tile workgroup
+
+// grads = the vector-Jacobian product of (u, J, div) with (g_u, g_jac, g_div), each may be null,
+// summed over the n points; written, not accumulated.  packed / packedT: the two fragment-ordered
+// copies; zeros: H zero floats; work: plan.total() floats.  The same n and plan give the same bits.
+hipError_t launch_siren_vjp(const SirenNet& net, const float* packed, const float* packedT, const float* zeros,
+                            const float* pts, int64_t n, const float* g_u, const float* g_jac, const float* g_div,
+                            const SirenGrads& grads, const SirenVjpPlan& plan, float* work, hipStream_t s);
+
+// wos_selftest_siren_vjp_layer's device half: dX = W^T dZ from the transposed pack and
+// siren_hidden_gemm, dW = sum dZ X^T from the weight-gradient kernel and its reduction.  dZ, X, dX
+// [n][1 + d_in][H]; packedT, zeros as above; work: siren_vjp_layer_selftest_floats(H, d_in, n).
+size_t siren_vjp_layer_selftest_floats(int H, int d_in, int64_t n);
+hipError_t launch_siren_vjp_layer_selftest(int H, int d_in, int64_t n, const float* W, float* packedT, const float* zeros,
+                                           const float* dZ, const float* X, float* dX, float* dW, float* work,
+                                           hipStream_t s);
+
 }  // namespace wos

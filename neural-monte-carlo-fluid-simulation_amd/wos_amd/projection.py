@@ -264,7 +264,7 @@ class PressureProjector:
         div = divergence(u, grid)
         return (-div[..., 0]).detach().contiguous()
 
-    def source_from_network(self, network, resolution, size, wrap=None):
+    def source_from_network(self, network, resolution, size, wrap=None, differentiable=False):
         """source_from_velocity for a velocity that is the SIREN itself, through the fused forward-mode
         kernel (wos_amd.siren.eval) instead of autograd: the same grid, the same shape, dtype and
         sign, detached and contiguous, ready for solve(div).  `network`: a Siren, the reference's MLP
@@ -272,10 +272,17 @@ class PressureProjector:
         wrap(x, u_net) -> u: the time-stepper's pointwise masks and weights around the network
         (query_velocity, src/2d/models/base.py:158-180); the kernel returns the network's value and
         Jacobian and siren.divergence_with_wrap applies the chain rule through `wrap` alone.
-        There is no create_graph here: the kernel has no backward pass, and the differentiable path
-        stays source_from_velocity(..., create_graph=True)."""
+        differentiable=True: the same bits, attached to the network's parameters (wos_amd.siren.apply;
+        with a wrap through its elementwise graph as well), so solve(div, differentiable=True) and
+        loss.backward() fill network.parameters()' .grad through the fused backward kernel
+        (wos_amd.siren.vjp) with no autograd graph over the network."""
         sampler = sample_uniform_2d if self.dim == 2 else sample_uniform_3d
         grid = sampler(resolution, size, with_boundary=True, device=self.device)
+        if differentiable:
+            if wrap is None:
+                return (-_siren.apply(network, grid, value=False, divergence=True)).contiguous()
+            u, jac = _siren.apply(network, grid, value=True, jacobian=True)
+            return (-_siren.divergence_with_wrap(grid, u, jac, wrap, create_graph=True)).contiguous()
         if wrap is None:
             return (-_siren.eval(network, grid, value=False, divergence=True)).contiguous()
         u, jac = _siren.eval(network, grid, value=True, jacobian=True)

@@ -4,8 +4,10 @@ The reference's projection step differentiates its velocity network by autograd
 (get_divergence, src/2d/models/model_split.py:230-236; divergence, diff_ops.py:45-51): one
 forward and `dim` backward passes with every activation in HBM.  eval() runs the same MLP
 (networks.py:25-68) in forward mode in one kernel: per point the value and its d_in tangents
-go through the layers together and only u, J or div come back.  Not differentiable: training
-through the projection keeps PressureProjector.source_from_velocity(create_graph=True).
+go through the layers together and only u, J or div come back.  vjp() is its backward with
+respect to the weights (wos_siren_vjp, csrc/wos_siren_vjp.hip), apply() the two as one autograd
+function over a module's own parameters: PressureProjector.source_from_network(differentiable=True)
+trains through the projection without an autograd graph over the network.
 """
 import collections
 import ctypes as C
@@ -173,18 +175,192 @@ def selftest_layer(W, b, X, device=0):
     return Z
 
 
-def divergence_with_wrap(x, u_net, J, wrap):
+def _cotangent(name, g, shape, like_torch, device):
+    """One cotangent as a contiguous float32 [n, ...] array of the points' kind, or None."""
+    if g is None:
+        return None
+    if tuple(g.shape) != shape:
+        raise ValueError(f"siren.vjp: {name} must have shape {shape}, got {tuple(g.shape)}")
+    if like_torch:
+        import torch
+        if not _is_torch(g) or g.device != device:
+            raise ValueError(f"siren.vjp: {name} must be a tensor on {device}, like the points")
+        return g.detach().to(torch.float32).contiguous()
+    if _is_torch(g):
+        g = g.detach().cpu().numpy()
+    return np.ascontiguousarray(g, dtype=np.float32)
+
+
+def vjp(net, x, *, grad_value=None, grad_jacobian=None, grad_divergence=None, stream=None, workspace_bytes=None):
+    """The backward of eval() with respect to the network: for the cotangents grad_value [..., d_out],
+    grad_jacobian [..., d_out, d_in] and grad_divergence [...] of eval's three outputs at the points
+    x [..., d_in] (any subset, at least one), (grad_weights, grad_biases) -- two lists in pack()
+    order, the gradient of sum(grad_value * u) + sum(grad_jacobian * J) + sum(grad_divergence * div)
+    summed over the points, float32.  A torch CUDA tensor in: torch tensors out, enqueued on
+    `stream` as in eval() without a host synchronisation; numpy (or a CPU tensor) in: numpy out,
+    blocking.  workspace_bytes caps the per-chunk stash (None: the library's 256 MiB).  The same
+    call gives the same bits every time; there is no gradient with respect to x or omega."""
+    p = net if isinstance(net, PackedSiren) else pack(net)
+    if grad_value is None and grad_jacobian is None and grad_divergence is None:
+        raise ValueError("siren.vjp: no cotangent given (grad_value, grad_jacobian and grad_divergence are all None)")
+    if grad_divergence is not None and p.d_out != p.d_in:
+        raise ValueError(f"siren.vjp: grad_divergence needs d_out == d_in, got d_out {p.d_out}, d_in {p.d_in}")
+    if len(x.shape) < 1 or x.shape[-1] != p.d_in:
+        raise ValueError(f"siren.vjp: points must be [..., {p.d_in}], got shape {tuple(x.shape)}")
+    lead = tuple(x.shape[:-1])
+    tails = ((p.d_out,), (p.d_out, p.d_in), ())
+    names = ("grad_value", "grad_jacobian", "grad_divergence")
+    on_gpu = _is_torch(x) and x.is_cuda
+    g = [_cotangent(names[k], c, lead + tails[k], on_gpu, x.device if on_gpu else None)
+         for k, c in enumerate((grad_value, grad_jacobian, grad_divergence))]
+    ws = 0 if workspace_bytes is None else int(workspace_bytes)
+    if ws < 0:
+        raise ValueError(f"siren.vjp: workspace_bytes must be >= 0, got {workspace_bytes}")
+    nl = p.n_hidden_layers + 2
+    L = _lib.load()
+    if on_gpu:
+        import torch
+        if any(t.device != x.device for t in p.weights + p.biases):
+            raise ValueError(f"siren.vjp: the points are on {x.device}, the network on {p.weights[0].device}")
+        xs = x.detach().to(torch.float32).contiguous().reshape(-1, p.d_in)
+        n = xs.shape[0]
+        gw = [torch.empty_like(t) for t in p.weights]
+        gb = [torch.empty_like(t) for t in p.biases]
+        cur = torch.cuda.current_stream(xs.device)
+        held = [xs] + [t for t in g if t is not None] + gw + gb + p.weights + p.biases
+        if stream is None:
+            s = cur.cuda_stream
+        else:
+            ts = stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.ExternalStream(int(stream),
+                                                                                                device=xs.device)
+            s = ts.cuda_stream
+            ts.wait_stream(cur)  # points, cotangents, weights and fresh outputs belong to torch's current stream
+            for t in held:
+                t.record_stream(ts)  # ... and are used on `stream`: the allocator must wait for it
+        st, keep = _net_struct(p, [t.data_ptr() for t in p.weights], [t.data_ptr() for t in p.biases])
+        pw = (C.c_void_p * nl)(*[t.data_ptr() for t in gw])
+        pb = (C.c_void_p * nl)(*[t.data_ptr() for t in gb])
+        check(L.wos_siren_vjp(C.byref(st), xs.data_ptr(), n, *[None if t is None else t.data_ptr() for t in g],
+                              pw, pb, ws, _lib.WOS_PTRS_DEVICE | _lib.WOS_ASYNC, xs.device.index or 0, s),
+              "wos_siren_vjp")
+        del keep, held
+        return gw, gb
+    if _is_torch(x):
+        x = x.detach().cpu().numpy()
+    xs = np.ascontiguousarray(x, dtype=np.float32).reshape(-1, p.d_in)
+    n = xs.shape[0]
+    host = [np.ascontiguousarray(t.cpu().numpy()) for t in p.weights + p.biases]
+    st, keep = _net_struct(p, [a.ctypes.data for a in host[:nl]], [a.ctypes.data for a in host[nl:]])
+    gw = [np.empty(a.shape, np.float32) for a in host[:nl]]
+    gb = [np.empty(a.shape, np.float32) for a in host[nl:]]
+    pw = (C.c_void_p * nl)(*[a.ctypes.data for a in gw])
+    pb = (C.c_void_p * nl)(*[a.ctypes.data for a in gb])
+    dev = p.weights[0].device.index or 0 if p.weights[0].is_cuda else 0
+    s = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
+    check(L.wos_siren_vjp(C.byref(st), xs.ctypes.data, n, *[None if a is None else a.ctypes.data for a in g],
+                          pw, pb, ws, 0, dev, s), "wos_siren_vjp")
+    del keep, host
+    return gw, gb
+
+
+def selftest_vjp_layer(W, dZ, X, device=0):
+    """wos_selftest_siren_vjp_layer: the backward's two hidden-layer products alone.  W [H, H],
+    dZ and X [n, 1 + d_in, H] (numpy) -> (dX [n, 1 + d_in, H] = dZ W, dW [H, H] = sum_{p,s} dZ[p,s] X[p,s]^T)."""
+    W = np.ascontiguousarray(W, np.float32)
+    dZ = np.ascontiguousarray(dZ, np.float32)
+    X = np.ascontiguousarray(X, np.float32)
+    if W.ndim != 2 or W.shape[0] != W.shape[1] or X.ndim != 3 or X.shape[2] != W.shape[0] or dZ.shape != X.shape:
+        raise ValueError("siren.selftest_vjp_layer: W [H, H], dZ and X [n, 1 + d_in, H]")
+    dX, dW = np.empty_like(X), np.empty_like(W)
+    check(_lib.load().wos_selftest_siren_vjp_layer(W.shape[0], X.shape[1] - 1, X.shape[0], W.ctypes.data, dZ.ctypes.data,
+                                                   X.ctypes.data, dX.ctypes.data, dW.ctypes.data, device),
+          "wos_selftest_siren_vjp_layer")
+    return dX, dW
+
+
+_apply_function = None
+
+
+def _apply_fn():
+    """The autograd function behind apply(), defined at first use (this module imports without torch)."""
+    global _apply_function
+    if _apply_function is not None:
+        return _apply_function
+    import torch
+
+    class _SirenApply(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, x, shape, want, *params):
+            nl = len(params) // 2
+            p = PackedSiren(*shape, [t.detach() for t in params[:nl]], [t.detach() for t in params[nl:]])
+            out = eval(p, x, value=want[0], jacobian=want[1], divergence=want[2])
+            out = out if isinstance(out, tuple) else (out,)
+            ctx.shape, ctx.want = shape, want
+            ctx.set_materialize_grads(False)
+            ctx.save_for_backward(x.detach(), *params)
+            return tuple(torch.as_tensor(o) for o in out)
+
+        @staticmethod
+        @torch.autograd.function.once_differentiable
+        def backward(ctx, *grads):
+            x, *params = ctx.saved_tensors
+            nl = len(params) // 2
+            p = PackedSiren(*ctx.shape, [t.detach() for t in params[:nl]], [t.detach() for t in params[nl:]])
+            g, it = [None, None, None], iter(grads)
+            for k in range(3):
+                if ctx.want[k]:
+                    g[k] = next(it)
+            gw, gb = vjp(p, x, grad_value=g[0], grad_jacobian=g[1], grad_divergence=g[2])
+            return (None, None, None) + tuple(torch.as_tensor(t) for t in gw + gb)
+
+    _apply_function = _SirenApply
+    return _apply_function
+
+
+def apply(module, x, *, value=True, jacobian=False, divergence=False):
+    """eval() as a differentiable function of the module's own parameters: the same outputs with the
+    same bits, attached to module.parameters() through one autograd node whose backward is vjp()
+    with whichever cotangents arrive (once differentiable: a second-order request raises).
+    `module`: what pack() takes, as a module (its Linear layers' weight and bias tensors are the
+    inputs).  x is a constant: there is no gradient with respect to the points, and an x that
+    requires grad is refused."""
+    import torch.nn as nn
+    p = pack(module)
+    if not (value or jacobian or divergence):
+        raise ValueError("siren.apply: no output requested")
+    if divergence and p.d_out != p.d_in:
+        raise ValueError(f"siren.apply: divergence needs d_out == d_in, got d_out {p.d_out}, d_in {p.d_in}")
+    if getattr(x, "requires_grad", False):
+        raise ValueError("siren.apply: x.requires_grad is set, and there is no gradient with respect to the points; "
+                         "pass x.detach()")
+    seq = module if isinstance(module, nn.Sequential) else module.net
+    lin = [m for m in seq if isinstance(m, nn.Linear)]
+    params = [m.weight for m in lin] + [m.bias for m in lin]
+    out = _apply_fn().apply(x, tuple(p[:5]), (bool(value), bool(jacobian), bool(divergence)), *params)
+    return out[0] if len(out) == 1 else out
+
+
+def divergence_with_wrap(x, u_net, J, wrap, create_graph=False):
     """div of u = wrap(x, N(x)) from the network's value u_net = N(x) [..., d_out] and Jacobian
     J [..., d_out, d_in] (eval(..., jacobian=True)), for a pointwise `wrap` -- the time-stepper's
     query_velocity (src/2d/models/base.py:158-180), which clamps and weights the network's output
     with position-dependent masks.  Chain rule, with autograd through `wrap` alone (an elementwise
     graph: no network in it): div = sum_i [ d wrap_i / d x_i + sum_m d wrap_i / d N_m * J[m, i] ].
     `wrap` must not modify its arguments in place.  Pure torch: runs wherever x lives; returns a
-    detached tensor [...] of x's dtype.  wrap = lambda x, u: u gives trace J exactly."""
+    detached tensor [...] of x's dtype.  wrap = lambda x, u: u gives trace J exactly.
+    create_graph=True: u_net and J are used as they come (apply(..., value=True, jacobian=True)),
+    the derivatives of `wrap` keep their graph and the result stays attached, so its gradient
+    reaches whatever produced u_net and J through the elementwise graph of `wrap` only."""
     import torch
     xl = x.detach().requires_grad_(True)
-    ul = u_net.detach().to(xl.dtype).requires_grad_(True)
-    Jd = J.detach().to(xl.dtype)
+    if create_graph:
+        ul = u_net.to(xl.dtype)
+        if not ul.requires_grad:
+            ul = ul.detach().requires_grad_(True)
+        Jd = J.to(xl.dtype)
+    else:
+        ul = u_net.detach().to(xl.dtype).requires_grad_(True)
+        Jd = J.detach().to(xl.dtype)
     u = wrap(xl, ul)
     if u.shape[-1] != xl.shape[-1]:
         raise ValueError(f"divergence_with_wrap: wrap returned {u.shape[-1]} components for {xl.shape[-1]} coordinates")
@@ -194,11 +370,12 @@ def divergence_with_wrap(x, u_net, J, wrap):
         if not ui.requires_grad:  # a component that depends on neither x nor the network: a constant
             term = torch.zeros_like(xl[..., 0])
         else:
-            gx, gn = torch.autograd.grad(ui, (xl, ul), torch.ones_like(ui), retain_graph=True, allow_unused=True)
+            gx, gn = torch.autograd.grad(ui, (xl, ul), torch.ones_like(ui), retain_graph=True, allow_unused=True,
+                                         create_graph=create_graph)
             term = (gn * Jd[..., :, i]).sum(-1) if gn is not None else None
             if gx is not None:
                 term = gx[..., i] if term is None else gx[..., i] + term
             if term is None:
                 term = torch.zeros_like(xl[..., 0])
         div = term if div is None else div + term
-    return div.detach()
+    return div if create_graph else div.detach()
