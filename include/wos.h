@@ -517,6 +517,26 @@ int wos_selftest_lhs_permute(int32_t impl, const int32_t *partner, const float *
                              int32_t sd, int32_t slots, int32_t count, float *out, int32_t device);
 int wos_selftest_lhs_plan(int32_t n_pairs, int32_t dim, int32_t *out);
 
+/* Device self-test of the Yukawa rejection sampler's decision functions (rejectionSampleGreensFn,
+ * distributions.h:362-383), for the GPU tests (added within ABI 10: a new entry point only;
+ * csrc/wos_selftest.hip).  Item i is the ball of radius R[i] with absorption lambda[i] and the
+ * radius draw r = x[i] R[i]; `dim` holds for the call.  The kernel builds the ball and the
+ * sampler's per-ball constants as a solve does and calls the shipped functions.  The u draws a
+ * stream can produce are u_k = k 2^-23, k = 0 .. 2^23 - 1; each test is a prefix or a suffix of
+ * them, so its edge describes its decision at every draw.  edges[i][6], 2^23 meaning "none":
+ *   [0] a   draws the certified float test accepts (a prefix; 2D: none decided once mu R >= 80)
+ *   [1] r0  first draw the certified float test rejects (a suffix)
+ *   [2] e   draws the exact test of the sequential loop accepts
+ *   [3] e3  the same for the cooperative sampler's exact 3D test (2D: e)
+ *   [4] q   first draw the per-ball certain reject takes (closed form and tabulated bound)
+ *   [5] xr  first draw the radius-dependent certain reject takes (3D; 2D: none)
+ * The shortcuts are sound iff a <= e <= min(r0, q, xr).  vals[i][3] = the ball's norm, the
+ * sampler's bound and 1 / (norm bound) as the kernels form them.  flags[i] bit j is set when test j
+ * is not false below its edge and true at it.  n = 0 succeeds; a null pointer, n < 0 or dim
+ * outside 2..3 is WOS_E_INVALID. */
+int wos_selftest_rejection(int32_t dim, const float *R, const float *lambda, const float *x, int64_t n,
+                           int32_t *edges, float *vals, int32_t *flags, int32_t device);
+
 /* Device self-test of the indexed adjoint's sum kernels (csrc/wos_tape_index.hip) on a
  * caller-supplied index, without a scene: row [n_rows + 1] (row[0] = 0, non-decreasing), id and
  * w [row[n_rows]] (id & 0x7FFFFFFF < n_tasks; bit 31: take c), a and c [n_channels][n_tasks],

@@ -182,6 +182,8 @@ wos::DevTasks task_view_in(float* d_tasks, int32_t* d_pstate, int64_t pstate_cap
 wos::DevTasks task_view(DevCtx& c, int dim, int64_t T, int32_t wpp, int channels = 1);
 // state_k = A_k * state_0 + C_k for the PCG32 LCG (multiplier kPcgMult, increment kPcgInc)
 int ensure_jump(DevCtx& c, int k_needed);
+// the rejection bound tables [2D | 3D] of DevParams::rej_tab (host, computed once per process)
+const std::vector<float>& rejection_tables();
 
 // ---- the enqueue protocol of everything that runs on the shared workspace (Boundary) ----
 // 1. the next ticket's slot for n_batches batches timed by n_events boundary events (q.bev), holding

@@ -60,7 +60,7 @@ static void ctx_free(DevCtx& c) {
 }
 
 // the rejection bound tables (host, computed once per process)
-static const std::vector<float>& rejection_tables() {
+const std::vector<float>& rejection_tables() {
   static std::once_flag once;
   // [2D bound | 3D bound] (DevParams::rej_tab)
   static std::vector<float> t(2 * wos::kRejTabBins);

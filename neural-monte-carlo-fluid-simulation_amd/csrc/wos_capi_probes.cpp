@@ -118,6 +118,36 @@ int wos_selftest_lhs_plan(int32_t n_pairs, int32_t dim, int32_t* out) {
   return WOS_OK;
 }
 
+int wos_selftest_rejection(int32_t dim, const float* R, const float* lambda, const float* x, int64_t n, int32_t* edges,
+                           float* vals, int32_t* flags, int32_t device) {
+  if (!R || !lambda || !x || !edges || !vals || !flags || n < 0 || n > (1LL << 26) || (dim != 2 && dim != 3))
+    return fail(WOS_E_INVALID, "wos_selftest_rejection: bad argument");
+  if (n == 0) return WOS_OK;
+  const std::vector<float>& tab = rejection_tables();
+  const size_t N = (size_t)n;
+  HIP_TRY(hipSetDevice(device));
+  DevBufs tmp;
+  float *d_tab = nullptr, *d_R = nullptr, *d_lam = nullptr, *d_x = nullptr, *d_vals = nullptr;
+  int32_t *d_edges = nullptr, *d_flags = nullptr;
+  HIP_TRY(tmp.get(&d_tab, tab.size()));
+  HIP_TRY(tmp.get(&d_R, N));
+  HIP_TRY(tmp.get(&d_lam, N));
+  HIP_TRY(tmp.get(&d_x, N));
+  HIP_TRY(tmp.get(&d_edges, N * 6));
+  HIP_TRY(tmp.get(&d_vals, N * 3));
+  HIP_TRY(tmp.get(&d_flags, N));
+  HIP_TRY(hipMemcpy(d_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_R, R, N * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_lam, lambda, N * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_x, x, N * 4, hipMemcpyHostToDevice));
+  HIP_TRY(wos::launch_rejection_selftest(dim, d_tab, d_R, d_lam, d_x, n, d_edges, d_vals, d_flags, nullptr));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(edges, d_edges, N * 6 * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(vals, d_vals, N * 3 * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(flags, d_flags, N * 4, hipMemcpyDeviceToHost));
+  return WOS_OK;
+}
+
 int wos_selftest_tape_rowsum(const uint32_t* row, int64_t n_rows, const uint32_t* id, const float* w, const float* a,
                              const float* c, int64_t n_tasks, int32_t n_channels, float* out, int32_t* tile_terms,
                              int32_t device) {

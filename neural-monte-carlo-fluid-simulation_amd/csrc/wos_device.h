@@ -1529,8 +1529,12 @@ __device__ __forceinline__ float k1_fast(float x) {
 // K0 and I0 of the rejection fast path at one argument: the polynomials of
 // k0_fast / i0_fast, with I0 and x^-1/2 shared (k0_fast at x <= 2 re-evaluates I0) and
 // the divisions by / of x as reciprocal products.  The reciprocals add ~1 ulp to y,
-// far inside the 8e-6 band the decisions are certified with (the GPU self-test checks
-// the <= 2e-6 error against the double-precision A&S functions).
+// far inside the 8e-6 band the decisions are certified with: the GPU self-test checks
+// the <= 2e-6 error against the double-precision A&S functions, and over the sweep of
+// tests/test_gpu_rejection.py the exact test's edge lies within 0.10 of a half band of
+// the band's centre (0.031 over the bands of 256 draws or more, where the draw grid no
+// longer counts): a 10x margin, 9.2e-5 of the draws undecided on average
+// (profiles/rejection_band.json).
 __device__ __forceinline__ void k0i0_fast(float x, float* k0, float* i0) {
   const float rs = __builtin_amdgcn_rsqf(x);
   const float rx = __builtin_amdgcn_rcpf(x);
@@ -1560,6 +1564,15 @@ __device__ __forceinline__ void k0i0_fast(float x, float* k0, float* i0) {
   *k0 = kv;
   *i0 = iv;
 }
+
+// What the fast tests allow for rho = A0 / A1 gone subnormal, then 0 (2D from mu R ~ 44, 3D from
+// ~ 52), where the exact path rounds (I0 A0) / A1 resp. (A0 sinh) / A1 instead: an absolute error of
+// rho of at most 2^-150, kRhoUlp with a 4x margin.  3D adds kRhoUlp sinh |c| to its band.  In 2D
+// I0(mu r) |c| < I0(80) 1.67 80 = 3.3e35 (bound >= 0.6 sqrt(lambda) and norm ~ 1 / lambda there), so
+// the error stays below 2.4e-10 and the band's absolute floor kRejFloor2 covers it at no cost per
+// iteration; the draws are 1.2e-7 apart, so the floor leaves at most one more of them undecided.
+constexpr float kRhoUlp = 0x1p-148f;
+constexpr float kRejFloor2 = 1e-8f;
 
 // Certain-reject bound of the Yukawa rejection test.  The test accepts iff
 // u < T(r) = (K0(mu r) - rho I0(mu r)) r / (norm bound) (2D) or
@@ -1656,7 +1669,8 @@ __device__ __forceinline__ void sample_volume(const DevParams& prm, Gfn<DIM, RB>
       const float ip = i0v * rho;
       const float c = g.r * invNB;
       const float Tf = (k0 - ip) * c;
-      const float M = 8e-6f * (__builtin_fabsf(k0) + __builtin_fabsf(ip)) * c + 2e-6f * __builtin_fabsf(Tf) + 1e-30f;
+      const float M = 8e-6f * (__builtin_fabsf(k0) + __builtin_fabsf(ip)) * __builtin_fabsf(c) +
+                      2e-6f * __builtin_fabsf(Tf) + kRejFloor2;  // rej_fast_decide's band
       if (u < Tf - M) decided = 1;
       else if (u > Tf + M) decided = 0;
     }
@@ -1801,7 +1815,10 @@ __device__ __forceinline__ void rej_draws(const DevParams& prm, uint64_t s0, int
   *x = draw_float(st * kPcgMult + kPcgInc);
 }
 
-// fast decision of one iteration: 1 accept, 0 reject, -1 undecided (see sample_volume)
+// fast decision of one iteration: 1 accept, 0 reject, -1 undecided (see sample_volume).
+// The band is relative to the two terms of Tf, so it holds for either sign of c = r invNB (a tiny
+// ball's float norm can cancel to <= 0: |c| keeps the band from inverting).  The floor kRejFloor2
+// covers the one absolute error, rho's underflow.  A non-finite invNB leaves M non-finite: undecided.
 __device__ __forceinline__ int rej_fast_decide(float u, float r, float sqrtL, float rho, float invNB) {
   const float mur = r * sqrtL;
   float k0, i0v;
@@ -1809,15 +1826,20 @@ __device__ __forceinline__ int rej_fast_decide(float u, float r, float sqrtL, fl
   const float ip = i0v * rho;
   const float c = r * invNB;
   const float Tf = (k0 - ip) * c;
-  const float M = 8e-6f * (__builtin_fabsf(k0) + __builtin_fabsf(ip)) * c + 2e-6f * __builtin_fabsf(Tf) + 1e-30f;
+  const float M = 8e-6f * (__builtin_fabsf(k0) + __builtin_fabsf(ip)) * __builtin_fabsf(c) +
+                  2e-6f * __builtin_fabsf(Tf) + kRejFloor2;
   return u < Tf - M ? 1 : (u > Tf + M ? 0 : -1);
 }
 
 // 3D analogue: e = exp(-mu r) from exp_fast (<= ~3 ulp) and an approximate
 // reciprocal; the band M covers their error carried through the cancellation in
 // sinh(mu r) = (1 - e^2) / 2e and Q = e - (A0/A1) sinh, plus the rounding of the
-// exact path's float/double steps (~4 ulp of T), with a >= 4x margin.  Non-finite
-// or underflowed e leaves M non-finite: undecided.
+// exact path's float/double steps (~4 ulp of T), with a >= 4x margin by that count; measured
+// (tests/test_gpu_rejection.py, profiles/rejection_band.json) the exact test's edge lies within
+// 0.125 of a half band of the band's centre -- 8x -- over every band of 16 draws or more (0.053
+// over those of 256 or more), and 2.1e-4 of the draws stay undecided on average.  As in 2D the band
+// takes |c| (the float norm of a ball below mu R ~ 5e-3 cancels to <= 0) and kRhoUlp sinh |c| for
+// rho gone subnormal (mu R >~ 52).  Non-finite or underflowed e leaves M non-finite: undecided.
 __device__ __forceinline__ int rej_fast_decide3(float u, float r, float sqrtL, float rho, float invNB) {
   const float mur = r * sqrtL;
   const float e = exp_fast(-mur);
@@ -1826,8 +1848,8 @@ __device__ __forceinline__ int rej_fast_decide3(float u, float r, float sqrtL, f
   const float Q = e - rho * sh;
   const float c = r * invNB;
   const float Tf = Q * c;
-  const float ar = __builtin_fabsf(rho);
-  const float M = (2e-6f * e + ar * (3e-7f * ie + 2e-6f * e + 4e-6f * __builtin_fabsf(sh))) * c +
+  const float ar = __builtin_fabsf(rho), as = __builtin_fabsf(sh);
+  const float M = (2e-6f * e + ar * (3e-7f * ie + 2e-6f * e + 4e-6f * as) + kRhoUlp * as) * __builtin_fabsf(c) +
                   4e-6f * __builtin_fabsf(Tf) + 1e-30f;
   return u < Tf - M ? 1 : (u > Tf + M ? 0 : -1);
 }
@@ -1837,7 +1859,9 @@ __device__ __forceinline__ int rej_fast_decide3(float u, float r, float sqrtL, f
 // rho = A0/A1 >= 0 and sinh >= 0 (the exact path's float subtraction of a non-negative term
 // cannot exceed e^{-mu r} either).  The bound carries a 0.1 % relative margin (hardware exp2,
 // the rounding of mu r and of the exact path's divisions: ~1e-5) plus 1e-6 R invNB absolute,
-// so u above it is the exact test's reject.  r = 0 and mu r >= 80 are left to the tests.
+// so u above it is the exact test's reject.  r = 0 and mu r >= 80 are left to the tests, and so is
+// a ball whose float norm cancelled to <= 0 (kb <= 0): there T = Q r invNB is the rounding noise of
+// Q near r = R, of either sign, and the bound would be negative.
 // Round 2 measured the screen alone (every iteration still paid for the fast test whenever a
 // lane of its wave needed it); the own generation now screens its whole block first and runs
 // the fast test on the survivors only (tests/test_rejection_bounds.py checks the bound).
@@ -1846,7 +1870,7 @@ __device__ __forceinline__ int rej_fast_decide3(float u, float r, float sqrtL, f
 // in e below mu r = 80, far inside the margin).  t > -115 keeps mu r < 79.7.
 __device__ __forceinline__ bool rej_xreject3(float u, float r, float kz, float kb, float xabs) {
   const float t = r * kz;
-  if (!(r > 0.0f) || !(t > -115.0f)) return false;
+  if (!(r > 0.0f) || !(t > -115.0f) || !(kb > 0.0f)) return false;
   return u > __builtin_fmaf(r * kb, __builtin_amdgcn_exp2f(t), xabs);
 }
 

@@ -63,6 +63,11 @@ hipError_t launch_lhs_permute_selftest(int impl, const int* partner, const float
 int lhs_permute_selftest_slots(int impl);
 int lhs_permute_selftest_max_strata(int impl);  // 0: not a shuffle the probe runs
 void lhs_plan(int n_pairs, int dim, int32_t* out);  // wos_selftest_lhs_plan's out[0..8] but [6]
+// probe of the rejection sampler's decision functions (wos_selftest.hip; include/wos.h
+// wos_selftest_rejection): n items (R, lambda, x), edges [n][6], vals [n][3], flags [n];
+// rej_tab: the device copy of the bound tables (DevParams::rej_tab)
+hipError_t launch_rejection_selftest(int dim, const float* rej_tab, const float* R, const float* lambda, const float* x,
+                                     int64_t n, int32_t* edges, float* vals, int32_t* flags, hipStream_t s);
 
 // boundary value caching (wos_bvc.hip), 2D
 hipError_t launch_bvc_point_info(const DevScene& sc, const float* pts, int64_t n, float* dd, float* nd,

@@ -2,9 +2,11 @@
 // (wos_selftest_lhs, wos_selftest_lhs_permute, wos_selftest_lhs_plan; include/wos.h).
 // The probes call build_lhs, lhs_permute_reg and lhs_permute of wos_device.h themselves, on
 // the LDS layout wos_first_ball_kernel gives one wave, so a test can pin every regime of the
-// sampler against the oracle's sequential loop without a full solve.  A translation unit of
-// its own: what a unit instantiates changes its kernels' inlining and scratch (DESIGN.md
-// "Kernel variants"), and these instantiations must not touch the five kernel units.
+// sampler against the oracle's sequential loop without a full solve.  And a probe of the rejection
+// sampler's decision functions (wos_selftest_rejection): the edge of each one over every draw a
+// stream can produce.  A translation unit of its own: what a unit instantiates changes its
+// kernels' inlining and scratch (DESIGN.md "Kernel variants"), and these instantiations must not
+// touch the five kernel units.
 #include "wos_device.h"
 #include "wos_launch.h"
 #include "../../include/wos.h"
@@ -160,6 +162,122 @@ void lhs_plan(int n_pairs, int dim, int32_t* out) {
   out[6] = 0;  // the LDS budget: the caller's (wos_capi.h kLdsDynamicMax)  
   out[7] = (int32_t)kPtGrab;
   out[8] = nstrat <= 4 * kWave ? (nstrat + kWave - 1) / kWave : 0;
+}
+
+// ---- the rejection sampler's decision functions (wos_selftest_rejection) ------------------------
+// The u draws a stream can produce are k 2^-23, k = 0 .. 2^23 - 1 (draw_float).  Every predicate
+// below compares u with values that do not depend on u, so over k it is a prefix or a suffix and
+// its edge is found by bisection; the shipped functions are called as they stand.
+constexpr int kRejDraws = 1 << 23;
+enum { kRejEdgeA, kRejEdgeR0, kRejEdgeE, kRejEdgeE3, kRejEdgeQ, kRejEdgeXr, kRejEdges };
+
+// smallest k in [0, 2^23] at which pred(k 2^-23) holds, for a predicate that is false, then true
+template <typename Pred>
+__device__ __forceinline__ int rej_first_true(Pred pred) {
+  int lo = 0, hi = kRejDraws;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (pred((float)mid * 0x1p-23f)) hi = mid;
+    else lo = mid + 1;
+  }
+  return lo;
+}
+
+// the predicate once more on either side of its edge: false below, true at it
+template <typename Pred>
+__device__ __forceinline__ bool rej_edge_holds(Pred pred, int edge) {
+  if (edge > 0 && pred((float)(edge - 1) * 0x1p-23f)) return false;
+  if (edge < kRejDraws && !pred((float)edge * 0x1p-23f)) return false;
+  return true;
+}
+
+template <int DIM>
+__global__ __launch_bounds__(256) void wos_rejection_selftest_kernel(const DevParams prm, const float* __restrict__ Rs,
+                                                                     const float* __restrict__ lams,
+                                                                     const float* __restrict__ xs, int64_t n,
+                                                                     int32_t* __restrict__ edges,
+                                                                     float* __restrict__ vals,
+                                                                     int32_t* __restrict__ flags) {
+  // the bound table in LDS, as stage_rej_jump stages it for every kernel that samples
+  for (int i = threadIdx.x; i < 2 * kRejTabBins; i += blockDim.x) s_rej_tab[i] = prm.rej_tab[i];
+  __syncthreads();
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float zero[DIM] = {};
+  Gfn<DIM> g;
+  g.init(true, lams[i]);
+  g.update_ball(zero, Rs[i], false);
+  // the preamble of sample_volume / sample_volume_wave (wos_device.h), restated
+  const float R = g.R, lam = g.lambda, sl = g.sqrtLambda;
+  const float a = DIM == 2 ? 2.2f : 2.0f, b = DIM == 2 ? 0.6f : 0.5f;
+  const float bound = R <= lam ? smax(smax(a / R, a / lam), smax(b * __builtin_sqrtf(R), b * sl))
+                               : smax(smin(a / R, a / lam), smin(b * __builtin_sqrtf(R), b * sl));
+  const float nrm = g.norm();
+  const float rho = g.A0 / g.A1;
+  const float invNB = 1.0f / (nrm * bound);
+  const float quick = rej_quick_bound<DIM>(prm, g.R, g.muR, g.sqrtLambda, invNB);
+  // the 3D own generation's folded constants (sample_volume_wave, phase A)
+  const float xabs = 1e-6f * g.R * invNB;
+  const float kz = g.sqrtLambda * -1.44269502f, kb = invNB * 1.001f;
+  const float r = xs[i] * R;
+
+  // the callers take the 2D fast test only below mu R = 80
+  const bool fast = DIM == 3 || g.muR < 80.0f;
+  const auto fast_decide = [&](float u) {
+    if (!fast) return -1;
+    if constexpr (DIM == 2) return rej_fast_decide(u, r, sl, rho, invNB);
+    else return rej_fast_decide3(u, r, sl, rho, invNB);
+  };
+  const auto not_fast_accept = [&](float u) { return fast_decide(u) != 1; };
+  const auto fast_reject = [&](float u) { return fast_decide(u) == 0; };
+  // the exact test of sample_volume
+  const auto not_exact_accept = [&](float u) {
+    g.r = r;
+    const float p = g.evaluate() / nrm;
+    const float pdfRadius = p / pdf_sphere_uniform<DIM>(g.r);
+    return !(u < pdfRadius / bound);
+  };
+  const auto not_exact3_accept = [&](float u) {
+    if constexpr (DIM == 3) return rej_exact_decide3(u, r, g.R, sl, g.A0, g.A1, nrm, bound) != 1;
+    else return not_exact_accept(u);
+  };
+  const auto quick_reject = [&](float u) { return u > quick; };
+  const auto x_reject = [&](float u) {
+    if constexpr (DIM == 3) return rej_xreject3(u, r, kz, kb, xabs);
+    else return false;
+  };
+
+  int32_t e[kRejEdges];
+  e[kRejEdgeA] = rej_first_true(not_fast_accept);
+  e[kRejEdgeR0] = rej_first_true(fast_reject);
+  e[kRejEdgeE] = rej_first_true(not_exact_accept);
+  e[kRejEdgeE3] = rej_first_true(not_exact3_accept);
+  e[kRejEdgeQ] = rej_first_true(quick_reject);
+  e[kRejEdgeXr] = rej_first_true(x_reject);
+  int32_t f = 0;
+  if (!rej_edge_holds(not_fast_accept, e[kRejEdgeA])) f |= 1 << kRejEdgeA;
+  if (!rej_edge_holds(fast_reject, e[kRejEdgeR0])) f |= 1 << kRejEdgeR0;
+  if (!rej_edge_holds(not_exact_accept, e[kRejEdgeE])) f |= 1 << kRejEdgeE;
+  if (!rej_edge_holds(not_exact3_accept, e[kRejEdgeE3])) f |= 1 << kRejEdgeE3;
+  if (!rej_edge_holds(quick_reject, e[kRejEdgeQ])) f |= 1 << kRejEdgeQ;
+  if (!rej_edge_holds(x_reject, e[kRejEdgeXr])) f |= 1 << kRejEdgeXr;
+  for (int k = 0; k < kRejEdges; k++) edges[i * kRejEdges + k] = e[k];
+  vals[i * 3 + 0] = nrm;
+  vals[i * 3 + 1] = bound;
+  vals[i * 3 + 2] = invNB;
+  flags[i] = f;
+}
+
+hipError_t launch_rejection_selftest(int dim, const float* rej_tab, const float* R, const float* lambda, const float* x,
+                                     int64_t n, int32_t* edges, float* vals, int32_t* flags, hipStream_t s) {
+  DevParams prm{};
+  prm.rej_tab = rej_tab;
+  const unsigned grid = (unsigned)((n + 255) / 256);
+  if (dim == 2)
+    hipLaunchKernelGGL(wos_rejection_selftest_kernel<2>, dim3(grid), dim3(256), 0, s, prm, R, lambda, x, n, edges, vals, flags);
+  else
+    hipLaunchKernelGGL(wos_rejection_selftest_kernel<3>, dim3(grid), dim3(256), 0, s, prm, R, lambda, x, n, edges, vals, flags);
+  return hipGetLastError();
 }
 
 }  // namespace wos

@@ -124,7 +124,7 @@ EXPORTS = (
     "wos_tape_record", "wos_tape_solve", "wos_tape_get_info", "wos_tape_destroy",
     "wos_tape_vjp", "wos_tape_read",
     "wos_tape_index_build", "wos_tape_index_get_info", "wos_tape_index_read", "wos_tape_vjp_indexed",
-    "wos_selftest_tape_rowsum",
+    "wos_selftest_tape_rowsum", "wos_selftest_rejection",
     "wos_scene_query",
     "wos_siren_eval", "wos_selftest_siren_layer",
     "wos_siren_vjp", "wos_selftest_siren_vjp_layer",
@@ -248,6 +248,9 @@ def load():
                                            C.c_int32, C.c_void_p, C.c_int32]
     L.wos_selftest_lhs_plan.restype = C.c_int
     L.wos_selftest_lhs_plan.argtypes = [C.c_int32, C.c_int32, C.c_void_p]
+    L.wos_selftest_rejection.restype = C.c_int
+    L.wos_selftest_rejection.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_int32]
     L.wos_last_error.restype = C.c_char_p
     L.wos_last_error.argtypes = []
     L.wos_abi_version.restype = C.c_int32

@@ -754,6 +754,25 @@ def selftest_math(which, x, device=0):
     return out
 
 
+def selftest_rejection(dim, R, lam, x, device=0):
+    """The rejection sampler's decision functions on the balls (R, lam) at the radius draws
+    x R, run by the kernels' own device code (wos_selftest_rejection).  Returns the edges
+    int32 [n, 6] = (a, r0, e, e3, q, xr) over the draws u_k = k 2^-23, vals float32 [n, 3] =
+    (norm, bound, 1 / (norm bound)) and the shape flags int32 [n]."""
+    R = np.ascontiguousarray(R, dtype=np.float32).reshape(-1)
+    lam = np.ascontiguousarray(lam, dtype=np.float32).reshape(-1)
+    x = np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
+    if not (R.size == lam.size == x.size):
+        raise WosError("R, lam and x must have one length")
+    edges = np.empty((R.size, 6), np.int32)
+    vals = np.empty((R.size, 3), np.float32)
+    flags = np.empty(R.size, np.int32)
+    check(_lib.load().wos_selftest_rejection(int(dim), R.ctypes.data, lam.ctypes.data, x.ctypes.data, R.size,
+                                             edges.ctypes.data, vals.ctypes.data, flags.ctypes.data, device),
+          "wos_selftest_rejection")
+    return edges, vals, flags
+
+
 def selftest_lhs(key, gidx, n_pairs, dim, jump_lds=True, device=0):
     """The first-ball kernel's stratified samples of the point indices gidx, built by the
     kernel's own device code (wos_selftest_lhs): float32 [n, 2 n_pairs, dim - 1]."""

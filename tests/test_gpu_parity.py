@@ -292,6 +292,28 @@ def test_cube3d_bit_exact(gpu, oracle):
     _compare(oracle, osc, sc, cfg, cfg["points"])
 
 
+@pytest.mark.parametrize("lam", [1.0, 1e-2])
+def test_cube3d_small_lambda_near_face_bit_exact(gpu, oracle, lam):
+    """3D balls below mu R ~ 5e-3, whose float norm (1 - mu R / sinh(mu R)) / lambda cancels to
+    <= 0: no lambda 350 / 50 scene reaches them (R < 2.5e-4), lambda 1 and 1e-2 do with every
+    ball near a wall.  Half of the points lie within 5e-3 of a face.  The sampler's shortcuts
+    must leave every decision to what the exact test says there too
+    (tests/test_gpu_rejection.py pins them draw by draw)."""
+    import kat_cases
+    c = kat_cases.cube3d(lam, 1, 1, 1, n_walks=16, npts=150, res=16)
+    pts = c["points"].copy()
+    rng = np.random.default_rng(41)
+    half = pts.shape[0] // 2
+    axis, side = rng.integers(0, 3, half), rng.choice([-1.0, 1.0], half)
+    pts[np.arange(half), axis] = (side * (1.0 - rng.uniform(1.2e-3, 5e-3, half))).astype(np.float32)
+    cfg = {"solver": c["solver"], "output": c["output"]}
+    osc = oracle.OracleScene(c["vertices"], c["prims"], c["source"], lam, watertight=True)
+    sc = WosScene(c["vertices"], c["prims"], c["source"], lam, watertight=True)
+    _, _, st = _compare(oracle, osc, sc, cfg, pts)
+    assert st["walk_steps"] > 0
+    sc.close()
+
+
 @pytest.mark.parametrize("dim,npts", [(2, 1), (2, 3), (3, 1), (3, 3)])
 def test_lone_walks_bit_exact(gpu, oracle, dim, npts):
     """Solves of one to three near-wall points: the long walks of such points leave the

@@ -52,6 +52,7 @@ def _quick(dim, sl, inv_nb):
     return q if (q > 0 and q < f32(3.0e38)) else f32(3.0e38)
 
 
+@np.errstate(all="ignore")  # r = 0, a zero norm, overflowed members: inf / nan as on the device
 def _thresholds_2d(R, lam, xs):
     sl = f32(np.sqrt(f32(lam)))
     muR = f32(R * sl)
@@ -68,12 +69,13 @@ def _thresholds_2d(R, lam, xs):
         I0 = f32(_bessel(0, mur))
         ev = f32(float(f32(K0 - f32(f32(I0 * A0) / A1))) / TWO_PI)
         p = f32(ev / nrm)
-        pdf = f32(1.0 / (TWO_PI * float(r)))
+        pdf = f32(1.0 / (TWO_PI * np.float64(r)))
         out.append(f32(f32(p / pdf) / bound))
     inv_nb = f32(f32(1.0) / f32(nrm * bound))
-    return np.array(out), _quick(2, sl, inv_nb), (muR, inv_nb)
+    return np.array(out), _quick(2, sl, inv_nb), (muR, inv_nb, nrm, bound)
 
 
+@np.errstate(all="ignore")
 def _thresholds_3d(R, lam, xs):
     sl = f32(np.sqrt(f32(lam)))
     muR = f32(R * sl)
@@ -89,12 +91,12 @@ def _thresholds_3d(R, lam, xs):
         mur = f32(r * sl)
         em = _expf(-mur)
         sh = f32(f32(f32(1.0) - f32(em * em)) / f32(f32(2.0) * em))
-        ev = f32(float(f32(em - f32(f32(A0 * sh) / A1))) / (FOUR_PI * float(r)))
+        ev = f32(np.float64(f32(em - f32(f32(A0 * sh) / A1))) / (FOUR_PI * np.float64(r)))
         p = f32(ev / nrm)
-        pdf = f32(1.0 / ((FOUR_PI * float(r)) * float(r)))
+        pdf = f32(1.0 / ((FOUR_PI * np.float64(r)) * np.float64(r)))
         out.append(f32(f32(p / pdf) / bound))
     inv_nb = f32(f32(1.0) / f32(nrm * bound))
-    return np.array(out), _quick(3, sl, inv_nb), (muR, inv_nb)
+    return np.array(out), _quick(3, sl, inv_nb), (muR, inv_nb, nrm, bound)
 
 
 @pytest.mark.parametrize("dim", [2, 3])
@@ -148,12 +150,16 @@ def test_tabulated_bound_dominates_exact_threshold(rej_table, dim, lam):
         peak = min(1.0, 0.6 / (mu * float(R)))
         xs = np.unique(np.concatenate([np.linspace(1e-4, 1.0, 400), peak * np.linspace(0.3, 1.7, 141)]))
         xs = xs[(xs > 0) & (xs <= 1.0)].astype(np.float32)
-        T, q, (muR, inv_nb) = (_thresholds_2d if dim == 2 else _thresholds_3d)(f32(R), f32(lam), xs)
+        T, q, (muR, inv_nb, _, _) = (_thresholds_2d if dim == 2 else _thresholds_3d)(f32(R), f32(lam), xs)
         T = T[np.isfinite(T)]
         k = int(f32(8.0) * f32(np.sqrt(f32(muR))))
-        if k >= tab.shape[0] or not (inv_nb > 0):
+        if k >= tab.shape[0]:
             continue
         qt = f32(f32(R * tab[k]) * inv_nb)
+        if not (inv_nb > 0):
+            # a ball whose float norm cancelled to <= 0: neither form may reject anything
+            assert q == f32(3.0e38) and not (0 < qt < f32(3.0e38)), (dim, lam, float(R), float(q), float(qt))
+            continue
         assert T.max() <= qt, (dim, lam, float(R), float(T.max()), float(qt))
         tighter.append(float(qt) / float(q))
     # orders of magnitude tighter for small balls (mu R << 1: the closed form ignores
@@ -165,7 +171,8 @@ def test_tabulated_bound_dominates_exact_threshold(rej_table, dim, lam):
 def _xbound3(R, lam, xs, inv_nb):
     """rej_xreject3's bound fma(r kb, 2^(r kz), xabs) with kz = -sqrtL log2(e), kb = 1.001 invNB,
     xabs = 1e-6 R invNB, in the kernel's float order (2^t in double here; the kernel's hardware
-    exp2 is within a few ulp of it, far inside the 0.1 % margin).  Returns the bound and t."""
+    exp2 is within a few ulp of it, far inside the 0.1 % margin).  kb <= 0 switches the screen
+    off: a bound of +inf.  Returns the bound and t."""
     sl = f32(np.sqrt(f32(lam)))
     kz = f32(sl * f32(-1.44269502))
     kb = f32(f32(inv_nb) * f32(1.001))
@@ -173,6 +180,8 @@ def _xbound3(R, lam, xs, inv_nb):
     r = (xs * R).astype(np.float32)
     t = (r * kz).astype(np.float32)
     e = np.exp2(t.astype(np.float64))
+    if not (kb > 0):
+        return np.full(r.shape, np.inf), t
     return (r * kb).astype(np.float64) * e + float(xabs), t
 
 
@@ -187,16 +196,25 @@ def test_radius_bound_3d_dominates_exact_threshold(lam):
     mu = np.sqrt(lam)
     radii = np.concatenate([np.exp(rng.uniform(np.log(1e-4), np.log(3.0), 40)), [1e-3, 0.02, 0.05, 0.5, 2.0],
                             np.array([0.5, 2.5, 10.0, 40.0, 70.0, 79.0, 79.9]) / mu])
-    caught = []
+    caught, degenerate = [], 0
     for R in radii.astype(np.float32):
         peak = min(1.0, 1.0 / (mu * float(R)))
         xs = np.unique(np.concatenate([np.linspace(1e-5, 1.0, 600), rng.uniform(0, 1, 300),
                                        peak * np.linspace(0.3, 1.7, 141), 1.0 - np.logspace(-7.5, -2, 60)]))
         xs = xs[(xs > 0) & (xs <= 1.0)].astype(np.float32)
-        T, q, (muR, inv_nb) = _thresholds_3d(f32(R), f32(lam), xs)
-        if not (inv_nb > 0 and np.isfinite(inv_nb)):
-            continue
+        T, q, (muR, inv_nb, _, _) = _thresholds_3d(f32(R), f32(lam), xs)
         B, t = _xbound3(f32(R), lam, xs, inv_nb)
+        if not (inv_nb > 0 and np.isfinite(inv_nb)):
+            # a ball whose float norm cancelled to <= 0 (or to a non-finite 1 / (norm bound)): the
+            # per-ball bound is off, and the screen rejects no draw k 2^-23 the exact test accepts
+            assert q == f32(3.0e38), (lam, float(R), float(q))
+            gate = (xs > 0) & (t > -115.0)
+            with np.errstate(invalid="ignore"):
+                n_acc = np.ceil(np.clip(np.nan_to_num(T.astype(np.float64), nan=0.0), 0.0, 1.0) * 2.0 ** 23)
+                wrong = gate & (n_acc > 0) & ((n_acc - 1) * 2.0 ** -23 > B)
+            assert not wrong.any(), (lam, float(R), xs[wrong][:4], T[wrong][:4], B[wrong][:4])
+            degenerate += 1
+            continue
         ok = np.isfinite(T) & (t > -115.0)
         assert (T[ok] <= B[ok]).all(), (lam, float(R), float((T - B)[ok].max()))
         # share of the reject interval (T, min(q, 1)) of u that the screen resolves
@@ -205,3 +223,4 @@ def test_radius_bound_3d_dominates_exact_threshold(lam):
         if top - Tc.mean() > 0 and muR > 2.0:
             caught.append(float(np.mean(top - Bc) / np.mean(top - Tc)))
     assert caught and np.mean(caught) > 0.6, caught
+    assert degenerate > 0 or lam > 1e-2  # lambda 1e-2: every ball below R ~ 0.05 is such a ball
