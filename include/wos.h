@@ -622,6 +622,33 @@ int wos_selftest_siren_vjp_layer(int32_t hidden, int32_t d_in, int64_t n_points,
                                  const float *W, const float *dZ, const float *X,
                                  float *dX, float *dW, int32_t device);
 
+/* ---- Fused SIREN fit step: regression loss of the value and its weight gradients --------------
+ * One iteration of the time-stepper's velocity fits (_advect_velocity, _project_velocity:
+ * src/2d/models/model_split.py:88-120, 274-283) without its optimiser step (added within ABI 10: a
+ * new entry point only; csrc/wos_siren_fit.hip, DESIGN.md "Fused SIREN fit step"):
+ *   loss[0] = 1 / (n d_out) * sum_p sum_i (scale[p][i] u_i(x_p) - target[p][i])^2
+ *   grad_weights[l], grad_biases[l]   its gradient, l = 0 .. n_hidden_layers + 1, the shapes of net's
+ *                                     weights[l] and biases[l]; written, not accumulated
+ * target[n*d_out]; scale[n*d_out] or NULL (= 1): a wrap u = s(x) * N(x) + c(x) that is diagonal-affine
+ * in the network's output is scale = s with c folded into the target.  grad_weights and grad_biases
+ * both NULL: the loss alone, with no backward sweep and no stash, the same bits as the full call's
+ * loss.  Exactly one of them NULL, a NULL entry in either, a NULL loss or target and n <= 0 (a mean
+ * over nothing) are WOS_E_INVALID.  u is wos_siren_eval's value chain (the same bits); all arithmetic
+ * is f32: r = fma(scale, u, -target), the seed d loss / d u = (scale (r + r)) (1 / (n d_out)), the sum
+ * of r r in a fixed blocked order divided once by n d_out.  The points are walked in chunks of whole
+ * 32-point tiles; per chunk the layers' pre-activations are stashed in a temporary of at most
+ * workspace_bytes (0: 256 MiB), (2 n_hidden_layers + 1) * hidden * 4 bytes per point; a non-zero
+ * workspace_bytes that cannot hold one tile is WOS_E_CAPACITY.  No atomics: the same call with the
+ * same n and workspace_bytes returns the same bits in loss and in every gradient.  Envelope and
+ * pointer rules are wos_siren_vjp's: host pointers (staged, blocking), WOS_PTRS_DEVICE, or
+ * WOS_PTRS_DEVICE | WOS_ASYNC on `stream`; loss is a pointer of the same kind as pts.  There is no
+ * gradient with respect to the points, scale, target or omega. */
+int wos_siren_fit(const wos_siren_net *net, const float *pts, int64_t n,
+                  const float *target, const float *scale, float *loss,
+                  float *const *grad_weights, float *const *grad_biases,
+                  size_t workspace_bytes,
+                  uint32_t flags, int32_t device, void *stream);
+
 const char *wos_last_error(void);
 int32_t wos_abi_version(void);
 int32_t wos_device_count(void);

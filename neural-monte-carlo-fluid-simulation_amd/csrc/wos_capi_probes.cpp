@@ -1,6 +1,7 @@
 // wos_capi_probes.cpp -- entry points that need neither a scene's workspace nor the device context:
 // the self-test probes (wos_selftest_*, kernels in wos_selftest.hip) and the fused SIREN
-// (wos_siren_eval, wos_siren.hip; wos_siren_vjp, wos_siren_vjp.hip).  Each call owns what it allocates.
+// (wos_siren_eval, wos_siren.hip; wos_siren_vjp, wos_siren_vjp.hip; wos_siren_fit, wos_siren_fit.hip).  Each call
+// owns what it allocates.
 #include "wos_capi.h"
 
 using namespace wos::capi;
@@ -453,6 +454,134 @@ int wos_siren_vjp(const wos_siren_net* net, const float* pts, int64_t n, const f
         hipSuccess)
       return e;
     for (int l = 0; l < NL; l++) {
+      if ((e = hipMemcpyAsync(grad_weights[l], dg.w[l], n_w[l] * sizeof(float), hipMemcpyDeviceToHost, st)) != hipSuccess)
+        return e;
+      if ((e = hipMemcpyAsync(grad_biases[l], dg.b[l], n_b[l] * sizeof(float), hipMemcpyDeviceToHost, st)) != hipSuccess)
+        return e;
+    }
+    return hipStreamSynchronize(st);
+  };
+  const hipError_t e = staged();
+  if (e != hipSuccess) hipStreamSynchronize(st);  // nothing may still use tmp when it is freed
+  hipFree(tmp);
+  if (e != hipSuccess) return fail(WOS_E_DEVICE, fn + ": " + hipGetErrorString(e));
+  return WOS_OK;
+}
+
+// ---- fused SIREN fit step (wos_siren_fit.hip) ------------------------------------------------
+// One temporary per call: packed | packedT | H zeros | the plan's work (loss only: packed | the
+// tiles' sums); with host pointers also the staged network, points, target, scale, loss and
+// gradients.  Stream-ordered with device pointers.
+int wos_siren_fit(const wos_siren_net* net, const float* pts, int64_t n, const float* target, const float* scale,
+                  float* loss, float* const* grad_weights, float* const* grad_biases, size_t workspace_bytes,
+                  uint32_t flags, int32_t device, void* stream) {
+  const std::string fn = "wos_siren_fit";
+  if (int rc = siren_net_check(fn, net)) return rc;
+  const int D = net->d_in, DO = net->d_out, H = net->hidden, L = net->n_hidden_layers, NL = L + 2;
+  if (!loss) return fail(WOS_E_INVALID, fn + ": null loss");
+  if (!target) return fail(WOS_E_INVALID, fn + ": null target");
+  if ((grad_weights == nullptr) != (grad_biases == nullptr))
+    return fail(WOS_E_INVALID, fn + ": exactly one of grad_weights and grad_biases is null (both null: the loss alone)");
+  const bool grads = grad_weights != nullptr;
+  if (grads)
+    for (int l = 0; l < NL; l++)
+      if (!grad_weights[l] || !grad_biases[l])
+        return fail(WOS_E_INVALID, fn + ": null grad_weights or grad_biases pointer of layer " + std::to_string(l));
+  if (n <= 0) return fail(WOS_E_INVALID, fn + ": n must be positive (a mean over nothing), got " + std::to_string(n));
+  if (n > (int64_t)0x7FFFFFFF * wos::kSirenTile) return fail(WOS_E_INVALID, fn + ": n: too many points for one call");
+  const size_t tile_bytes = wos::siren_fit_stash_floats_per_tile(H, L) * sizeof(float);
+  if (workspace_bytes != 0 && workspace_bytes < tile_bytes)
+    return fail(WOS_E_CAPACITY, fn + ": workspace_bytes " + std::to_string(workspace_bytes) +
+                                    " cannot hold one tile's stash of " + std::to_string(tile_bytes) + " bytes");
+  if (!pts) return fail(WOS_E_INVALID, fn + ": null point buffer");
+  size_t n_w[wos::kSirenMaxLayers], n_b[wos::kSirenMaxLayers];
+  for (int l = 0; l < NL; l++) {
+    n_b[l] = l == NL - 1 ? (size_t)DO : (size_t)H;
+    n_w[l] = n_b[l] * (l == 0 ? (size_t)D : (size_t)H);
+  }
+  HIP_TRY(hipSetDevice(device));
+  hipStream_t st = (hipStream_t)stream;
+  wos::SirenNet dn{};
+  dn.d_in = D;
+  dn.d_out = DO;
+  dn.H = H;
+  dn.L = L;
+  dn.omega = net->omega;
+  wos::SirenGrads dg{};
+  int cus = 0;
+  HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
+  const int per_cu = std::max<int>(1, (int)(kLdsDynamicMax / wos::siren_fit_tile_lds_bytes(D, H)));
+  const wos::SirenFitPlan plan =
+      wos::siren_fit_plan(dn, n, workspace_bytes ? workspace_bytes : kSirenVjpDefaultStash, cus * per_cu);
+  const size_t pack_n = wos::siren_pack_floats(H, L);
+  const size_t o_packT = pack_n, o_zero = 2 * pack_n, o_work = grads ? o_zero + (size_t)H : pack_n,
+               dev_total = o_work + plan.total(grads);
+  const auto run = [&](float* tmp, const float* d_pts, const float* d_target, const float* d_scale, float* d_loss) -> hipError_t {
+    hipError_t e;
+    if ((e = wos::launch_siren_pack(dn, tmp, st)) != hipSuccess) return e;
+    if (!grads)
+      return wos::launch_siren_fit(dn, tmp, nullptr, nullptr, d_pts, n, d_target, d_scale, d_loss, nullptr, plan, tmp + o_work, st);
+    if ((e = hipMemsetAsync(tmp + o_zero, 0, (size_t)H * sizeof(float), st)) != hipSuccess) return e;
+    if ((e = wos::launch_siren_pack_transposed(dn, tmp + o_packT, st)) != hipSuccess) return e;
+    return wos::launch_siren_fit(dn, tmp, tmp + o_packT, tmp + o_zero, d_pts, n, d_target, d_scale, d_loss, &dg, plan,
+                                 tmp + o_work, st);
+  };
+  if (flags & WOS_PTRS_DEVICE) {
+    for (int l = 0; l < NL; l++) {
+      dn.w[l] = net->weights[l];
+      dn.b[l] = net->biases[l];
+      if (grads) {
+        dg.w[l] = grad_weights[l];
+        dg.b[l] = grad_biases[l];
+      }
+    }
+    float* tmp = nullptr;
+    if (hipMallocAsync((void**)&tmp, dev_total * sizeof(float), st) != hipSuccess)
+      return fail(WOS_E_NOMEM, fn + ": cannot allocate " + std::to_string(dev_total * sizeof(float)) + " bytes of workspace");
+    hipError_t e = run(tmp, pts, target, scale, loss);
+    const hipError_t e2 = hipFreeAsync(tmp, st);
+    if (e == hipSuccess) e = e2;
+    if (e == hipSuccess && !(flags & WOS_ASYNC)) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return fail(WOS_E_DEVICE, fn + ": " + hipGetErrorString(e));
+    return WOS_OK;
+  }
+  // host pointers: ... | weights, biases and their gradients layer by layer | pts | target | scale | loss
+  const size_t N = (size_t)n;
+  size_t o_w[wos::kSirenMaxLayers], o_b[wos::kSirenMaxLayers], o_gw[wos::kSirenMaxLayers], o_gb[wos::kSirenMaxLayers];
+  size_t off = dev_total;
+  for (int l = 0; l < NL; l++) {
+    o_w[l] = off;
+    off += n_w[l];
+    o_b[l] = off;
+    off += n_b[l];
+    o_gw[l] = off;
+    off += grads ? n_w[l] : 0;
+    o_gb[l] = off;
+    off += grads ? n_b[l] : 0;
+  }
+  const size_t o_pts = off, o_t = o_pts + N * D, o_s = o_t + N * DO, o_loss = o_s + (scale ? N * DO : 0), total = o_loss + 1;
+  float* tmp = nullptr;
+  if (hipMalloc((void**)&tmp, total * sizeof(float)) != hipSuccess)
+    return fail(WOS_E_NOMEM, fn + ": cannot allocate " + std::to_string(total * sizeof(float)) + " bytes of staging");
+  const auto staged = [&]() -> hipError_t {
+    hipError_t e;
+    const auto up = [&](size_t o, const float* src, size_t count) {
+      return hipMemcpyAsync(tmp + o, src, count * sizeof(float), hipMemcpyHostToDevice, st);
+    };
+    for (int l = 0; l < NL; l++) {
+      if ((e = up(o_w[l], net->weights[l], n_w[l])) != hipSuccess) return e;
+      if ((e = up(o_b[l], net->biases[l], n_b[l])) != hipSuccess) return e;
+      dn.w[l] = tmp + o_w[l];
+      dn.b[l] = tmp + o_b[l];
+      dg.w[l] = tmp + o_gw[l];
+      dg.b[l] = tmp + o_gb[l];
+    }
+    if ((e = up(o_pts, pts, N * D)) != hipSuccess) return e;
+    if ((e = up(o_t, target, N * DO)) != hipSuccess) return e;
+    if (scale && (e = up(o_s, scale, N * DO)) != hipSuccess) return e;
+    if ((e = run(tmp, tmp + o_pts, tmp + o_t, scale ? tmp + o_s : nullptr, tmp + o_loss)) != hipSuccess) return e;
+    if ((e = hipMemcpyAsync(loss, tmp + o_loss, sizeof(float), hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
+    for (int l = 0; grads && l < NL; l++) {
       if ((e = hipMemcpyAsync(grad_weights[l], dg.w[l], n_w[l] * sizeof(float), hipMemcpyDeviceToHost, st)) != hipSuccess)
         return e;
       if ((e = hipMemcpyAsync(grad_biases[l], dg.b[l], n_b[l] * sizeof(float), hipMemcpyDeviceToHost, st)) != hipSuccess)

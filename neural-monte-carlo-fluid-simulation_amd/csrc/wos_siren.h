@@ -79,6 +79,24 @@ hipError_t launch_siren_vjp(const SirenNet& net, const float* packed, const floa
                             const float* pts, int64_t n, const float* g_u, const float* g_jac, const float* g_div,
                             const SirenGrads& grads, const SirenVjpPlan& plan, float* work, hipStream_t s);
 
+// The backward's two generic launches, shared with the fit step (wos_siren_fit.hip).
+// A row of partials is cut into segments, each with its own destination: dst[k] receives the
+// elements [end[k - 1], end[k]) of the row.
+constexpr int kReduceSegs = 12;
+struct SirenReduceSegs {
+  int n;
+  int end[kReduceSegs];
+  float* dst[kReduceSegs];
+};
+// dst(e) = (accumulate ? dst(e) : 0) + sum over i < n_part of part[i * stride + e], in an order
+// that depends on n_part alone.
+hipError_t siren_reduce(const float* part, int n_part, size_t stride, const SirenReduceSegs& segs, bool accumulate,
+                        hipStream_t s);
+// part[slice][l] [H][H] = dZ_l X_{l-1}^T over the slice's column blocks: ds, xs [L][tiles][H][C * 32]
+// (layer_stride apart), C columns per point, columns of points past n_valid masked.
+hipError_t siren_wgrad(const float* ds, const float* xs, size_t layer_stride, int H, int C, int tiles, int64_t n_valid,
+                       float* part, int L, hipStream_t s);
+
 // wos_selftest_siren_vjp_layer's device half: dX = W^T dZ from the transposed pack and
 // siren_hidden_gemm, dW = sum dZ X^T from the weight-gradient kernel and its reduction.  dZ, X, dX
 // [n][1 + d_in][H]; packedT, zeros as above; work: siren_vjp_layer_selftest_floats(H, d_in, n).
@@ -86,5 +104,29 @@ size_t siren_vjp_layer_selftest_floats(int H, int d_in, int64_t n);
 hipError_t launch_siren_vjp_layer_selftest(int H, int d_in, int64_t n, const float* W, float* packedT, const float* zeros,
                                            const float* dZ, const float* X, float* dX, float* dW, float* work,
                                            hipStream_t s);
+
+// ---- fit step (wos_siren_fit.hip) --------------------------------------------------------------
+// The fit step's temporaries for chunks of `tiles` 32-point tiles, in floats.  One column per point.
+struct SirenFitPlan {
+  int tiles;          // tiles per chunk
+  int slices;         // split-K slices of the weight-gradient kernel per chunk
+  size_t stash;       // (2 L + 1) H 32 floats per tile: z_0 .. z_L (then a_0 .. a_{L-1}) and dz_1 .. dz_L
+  size_t tile_part;   // per-tile partials of dWo, dbo, db_0 .. db_L and dW0 (the backward's layout)
+  size_t slice_part;  // per-slice partials of dW_1 .. dW_L
+  size_t loss_part;   // per-tile sums of squared residuals
+  size_t total(bool grads) const { return grads ? stash + tile_part + slice_part + loss_part : loss_part; }
+};
+inline size_t siren_fit_stash_floats_per_tile(int H, int L) { return (size_t)(2 * L + 1) * H * kSirenTile; }
+// The chunking follows from the stash's cap whether or not gradients are asked for: the loss-only
+// call sums in the full call's order.
+SirenFitPlan siren_fit_plan(const SirenNet& net, int64_t n, size_t stash_cap_bytes, int resident_tiles);
+size_t siren_fit_tile_lds_bytes(int d_in, int H);  // dynamic LDS of one tile workgroup
+
+// loss[0] = 1 / (n d_out) sum (scale u - target)^2 (scale null: 1) and, with grads non-null, its
+// gradient (written, not accumulated).  grads null: the loss alone -- packedT, zeros may be null,
+// work holds plan.total(false) floats.  n >= 1.  The same n and plan give the same bits.
+hipError_t launch_siren_fit(const SirenNet& net, const float* packed, const float* packedT, const float* zeros,
+                            const float* pts, int64_t n, const float* target, const float* scale, float* loss,
+                            const SirenGrads* grads, const SirenFitPlan& plan, float* work, hipStream_t s);
 
 }  // namespace wos

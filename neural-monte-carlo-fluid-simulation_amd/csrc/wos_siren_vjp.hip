@@ -360,15 +360,6 @@ __global__ __launch_bounds__(256) void siren_wgrad_kernel(const float* __restric
     }
 }
 
-// A row of partials is cut into segments, each with its own destination: dst[k] receives the
-// elements [end[k - 1], end[k]) of the row.
-constexpr int kReduceSegs = 12;
-struct SirenReduceSegs {
-  int n;
-  int end[kReduceSegs];
-  float* dst[kReduceSegs];
-};
-
 // dst(e) = (accumulate ? dst(e) : 0) + sum over i < n_part of part[i * stride + e].  Eight threads
 // per element: thread y adds the partials i = y, y + 8, ... as a chain, then thread 0 adds the
 // eight chains' sums in the order y = 0 .. 7.  The order depends on n_part alone.
@@ -437,16 +428,16 @@ SirenVjpPlan siren_vjp_plan(const SirenNet& net, int64_t n, size_t stash_cap_byt
   return p;
 }
 
-static hipError_t siren_reduce(const float* part, int n_part, size_t stride, const SirenReduceSegs& segs, bool accumulate,
-                               hipStream_t s) {
+hipError_t siren_reduce(const float* part, int n_part, size_t stride, const SirenReduceSegs& segs, bool accumulate,
+                        hipStream_t s) {
   const int count = segs.end[segs.n - 1];
   hipLaunchKernelGGL(siren_reduce_kernel, dim3((unsigned)((count + 31) / 32)), dim3(256), 0, s, part, n_part, stride,
                      segs, count, accumulate ? 1 : 0);
   return hipGetLastError();
 }
 
-static hipError_t siren_wgrad(const float* ds, const float* xs, size_t layer_stride, int H, int C, int tiles,
-                              int64_t n_valid, float* part, int L, hipStream_t s) {
+hipError_t siren_wgrad(const float* ds, const float* xs, size_t layer_stride, int H, int C, int tiles, int64_t n_valid,
+                       float* part, int L, hipStream_t s) {
   const int TB = (H + kWgradTile - 1) / kWgradTile, n_kb = tiles * C;
   const int slices = (n_kb + kSirenWgradSliceBlocks - 1) / kSirenWgradSliceBlocks;
   hipLaunchKernelGGL(siren_wgrad_kernel, dim3(TB * TB, slices, L), dim3(256), 0, s, ds, xs, layer_stride, H, C, n_kb,

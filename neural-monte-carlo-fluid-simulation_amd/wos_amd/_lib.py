@@ -128,6 +128,7 @@ EXPORTS = (
     "wos_scene_query",
     "wos_siren_eval", "wos_selftest_siren_layer",
     "wos_siren_vjp", "wos_selftest_siren_vjp_layer",
+    "wos_siren_fit",
 )
 
 # include/wos.h WOS_QUERY_*: the boundary wos_scene_query's dist / signed_dist / closest describe
@@ -228,6 +229,10 @@ def load():
                                            C.c_void_p, C.c_int32]
     L.wos_siren_vjp.restype = C.c_int
     L.wos_siren_vjp.argtypes = [C.POINTER(SirenNet), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_size_t, C.c_uint32, C.c_int32,
+                                C.c_void_p]
+    L.wos_siren_fit.restype = C.c_int
+    L.wos_siren_fit.argtypes = [C.POINTER(SirenNet), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                 C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_size_t, C.c_uint32, C.c_int32,
                                 C.c_void_p]
     L.wos_selftest_siren_vjp_layer.restype = C.c_int

@@ -19,6 +19,8 @@ in PyTorch-ROCm: its Linear layers are the dense contractions (hipBLASLt / MFMA)
 source alone there is a second path without autograd: source_from_network evaluates the
 network and its divergence in the fused forward-mode kernel of wos_amd.siren.
 """
+import weakref
+
 import numpy as np
 import torch
 import torch.nn as nn
@@ -369,3 +371,68 @@ class PressureProjector:
         with torch.no_grad():
             target = velocity_prev(x) - grad_p[idx]
         return torch.mean((velocity(x) - target) ** 2)
+
+    def projection_fit_loss(self, network, network_prev, grad_p, n_samples, wrap=None, generator=None):
+        """projection_loss for velocities that are SIRENs, through the fused fit step
+        (wos_amd.siren.fit_loss) instead of an autograd graph over the network: the same
+        torch.randint draw (range rule and generator consumption as projection_loss, so a generator
+        seeded alike selects the same samples), target = wrap(x, network_prev(x)) - grad_p[idx] with
+        the previous network evaluated by wos_amd.siren.eval, and the loss
+        mean((wrap(x, network(x)) - target)^2) attached to network's parameters.  wrap(x, u_net) -> u
+        must be diagonal-affine in u_net (query_velocity's karman and taylorgreen branches;
+        wos_amd.siren.diagonal_wrap refuses any other): its scale goes to the kernel, its offset into
+        the target."""
+        n = self.samples.shape[0]
+        hi = n - 1 if self.dim == 2 else n
+        idx = torch.randint(0, hi, (n_samples,), device=self.device, generator=generator)
+        x = self.samples[idx]
+        with torch.no_grad():
+            u_prev = _siren.eval(network_prev, x)
+            if wrap is None:
+                scale, target = None, u_prev - grad_p[idx]
+            else:
+                scale, offset = _diagonal(wrap, x, u_prev.shape[-1])
+                target = wrap(x, u_prev) - grad_p[idx] - offset
+        return _siren.fit_loss(network, x, target, scale)
+
+
+_checked_wraps = weakref.WeakSet()
+
+
+def _diagonal(wrap, x, d_out):
+    """siren.diagonal_wrap for the two fit losses.  The probe reads its verdict on the host, so a
+    wrap is probed at its first batch only: whether it mixes components does not depend on the
+    points.  A callable that cannot be weakly referenced is probed every time."""
+    known = wrap in _checked_wraps
+    out = _siren.diagonal_wrap(wrap, x, d_out, check=not known)
+    if not known:
+        try:
+            _checked_wraps.add(wrap)
+        except TypeError:
+            pass
+    return out
+
+
+def advection_fit_loss(network, network_prev, samples, dt, size, network_tilde=None, wrap=None):
+    """_advect_velocity's loss (src/2d/models/model_split.py:88-120; semi-Lagrangian) for velocities
+    that are SIRENs, through the fused fit step: backtrack x_b = samples - dt * u_prev(samples) with
+    the wrapped previous velocity, clamp x_b to `size` ([x0, x1, y0, y1(, z0, z1)]), take
+    target = u_prev(x_b) -- or 2 u_prev(x_b) - u_tilde(x_b) when network_tilde is given (the
+    reference's `flag` branch) -- and return mean((wrap(samples, network(samples)) - target)^2)
+    attached to network's parameters (wos_amd.siren.fit_loss).  Every no-grad evaluation runs in
+    wos_amd.siren.eval.  wrap as in PressureProjector.projection_fit_loss."""
+    x = samples.detach()
+    with torch.no_grad():
+        def query(net, pts):
+            u = _siren.eval(net, pts)
+            return u if wrap is None else wrap(pts, u)
+        back = x - query(network_prev, x) * dt
+        back = torch.stack([back[..., k].clamp(min=size[2 * k], max=size[2 * k + 1]) for k in range(x.shape[-1])], dim=-1)
+        target = query(network_prev, back)
+        if network_tilde is not None:
+            target = 2 * target - query(network_tilde, back)
+        scale = None
+        if wrap is not None:
+            scale, offset = _diagonal(wrap, x, target.shape[-1])
+            target = target - offset
+    return _siren.fit_loss(network, x, target, scale)

@@ -7,7 +7,10 @@ forward and `dim` backward passes with every activation in HBM.  eval() runs the
 go through the layers together and only u, J or div come back.  vjp() is its backward with
 respect to the weights (wos_siren_vjp, csrc/wos_siren_vjp.hip), apply() the two as one autograd
 function over a module's own parameters: PressureProjector.source_from_network(differentiable=True)
-trains through the projection without an autograd graph over the network.
+trains through the projection without an autograd graph over the network.  fit() is one iteration
+of the time-stepper's velocity fits -- the regression loss of the value and its weight gradients in
+one value-only pass (wos_siren_fit, csrc/wos_siren_fit.hip) -- fit_loss() the same as an autograd
+scalar, diagonal_wrap() the (scale, offset) form of query_velocity's masks that fit() takes.
 """
 import collections
 import ctypes as C
@@ -379,3 +382,207 @@ def divergence_with_wrap(x, u_net, J, wrap, create_graph=False):
                 term = torch.zeros_like(xl[..., 0])
         div = term if div is None else div + term
     return div if create_graph else div.detach()
+
+
+def _fit_operand(name, a, shape, like_torch, device):
+    """target / scale as a contiguous float32 [n, d_out] array of the points' kind."""
+    if tuple(a.shape) != shape:
+        raise ValueError(f"siren.fit: {name} must have shape {shape}, got {tuple(a.shape)}")
+    if like_torch:
+        import torch
+        if not _is_torch(a) or a.device != device:
+            raise ValueError(f"siren.fit: {name} must be a tensor on {device}, like the points")
+        return a.detach().to(torch.float32).contiguous()
+    if _is_torch(a):
+        a = a.detach().cpu().numpy()
+    return np.ascontiguousarray(a, dtype=np.float32)
+
+
+fit_calls = collections.Counter()  # "loss_only" / "grads": how many times fit() went down either path
+
+
+def fit(net, x, target, scale=None, *, grads=True, stream=None, workspace_bytes=None):
+    """One step of the time-stepper's velocity fits without its optimiser (wos_siren_fit,
+    csrc/wos_siren_fit.hip): loss = mean((scale * net(x) - target)^2) over the points x [..., d_in]
+    and the outputs, target and scale [..., d_out] (scale=None: 1), and its gradient with respect to
+    every weight and bias.  Returns (loss, grad_weights, grad_biases), the two lists in pack() order,
+    or the loss alone with grads=False: no backward sweep, no stash, no gradient buffer, the same
+    bits in the loss.  A torch CUDA tensor in: torch tensors out (loss a 0-d device tensor), enqueued
+    on `stream` as in eval() without a host synchronisation; numpy (or a CPU tensor) in: numpy out
+    (loss a numpy float32 scalar), blocking.  workspace_bytes caps the per-chunk stash (None: the
+    library's 256 MiB).  net(x) is eval()'s value bit for bit; the same call gives the same bits
+    every time.  There is no gradient with respect to x, target, scale or omega."""
+    p = net if isinstance(net, PackedSiren) else pack(net)
+    if len(x.shape) < 1 or x.shape[-1] != p.d_in:
+        raise ValueError(f"siren.fit: points must be [..., {p.d_in}], got shape {tuple(x.shape)}")
+    lead = tuple(x.shape[:-1])
+    on_gpu = _is_torch(x) and x.is_cuda
+    dev = x.device if on_gpu else None
+    if target is None:
+        raise ValueError("siren.fit: target is None")
+    t = _fit_operand("target", target, lead + (p.d_out,), on_gpu, dev)
+    sc = None if scale is None else _fit_operand("scale", scale, lead + (p.d_out,), on_gpu, dev)
+    n = 1
+    for k in lead:
+        n *= int(k)
+    if n <= 0:
+        raise ValueError("siren.fit: no points (n must be positive: the loss is a mean)")
+    ws = 0 if workspace_bytes is None else int(workspace_bytes)
+    if ws < 0:
+        raise ValueError(f"siren.fit: workspace_bytes must be >= 0, got {workspace_bytes}")
+    nl = p.n_hidden_layers + 2
+    L = _lib.load()
+    fit_calls["grads" if grads else "loss_only"] += 1
+    if on_gpu:
+        import torch
+        if any(w.device != x.device for w in p.weights + p.biases):
+            raise ValueError(f"siren.fit: the points are on {x.device}, the network on {p.weights[0].device}")
+        xs = x.detach().to(torch.float32).contiguous().reshape(-1, p.d_in)
+        loss = torch.empty((), dtype=torch.float32, device=xs.device)
+        gw, gb, flat = [], [], None
+        if grads:  # one buffer, the tensors views of it in pack() order: fit_loss scales it in one launch
+            flat = torch.empty(sum(a.numel() for a in p.weights + p.biases), dtype=torch.float32, device=xs.device)
+            views, at = [], 0
+            for a in p.weights + p.biases:
+                views.append(flat[at:at + a.numel()].view(a.shape))
+                at += a.numel()
+            gw, gb = views[:nl], views[nl:]
+        cur = torch.cuda.current_stream(xs.device)
+        held = [xs, t, loss] + ([] if sc is None else [sc]) + ([] if flat is None else [flat]) + p.weights + p.biases
+        if stream is None:
+            s = cur.cuda_stream
+        else:
+            ts = stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.ExternalStream(int(stream),
+                                                                                                device=xs.device)
+            s = ts.cuda_stream
+            ts.wait_stream(cur)  # points, target, weights and fresh outputs belong to torch's current stream
+            for a in held:
+                a.record_stream(ts)  # ... and are used on `stream`: the allocator must wait for it
+        st, keep = _net_struct(p, [w.data_ptr() for w in p.weights], [b.data_ptr() for b in p.biases])
+        pw = (C.c_void_p * nl)(*[a.data_ptr() for a in gw]) if grads else None
+        pb = (C.c_void_p * nl)(*[a.data_ptr() for a in gb]) if grads else None
+        check(L.wos_siren_fit(C.byref(st), xs.data_ptr(), n, t.data_ptr(), None if sc is None else sc.data_ptr(),
+                              loss.data_ptr(), pw, pb, ws, _lib.WOS_PTRS_DEVICE | _lib.WOS_ASYNC,
+                              xs.device.index or 0, s), "wos_siren_fit")
+        del keep, held
+        return (loss, gw, gb) if grads else loss
+    if _is_torch(x):
+        x = x.detach().cpu().numpy()
+    xs = np.ascontiguousarray(x, dtype=np.float32).reshape(-1, p.d_in)
+    host = [np.ascontiguousarray(w.cpu().numpy()) for w in p.weights + p.biases]
+    st, keep = _net_struct(p, [a.ctypes.data for a in host[:nl]], [a.ctypes.data for a in host[nl:]])
+    loss = np.empty((), np.float32)
+    gw = [np.empty(a.shape, np.float32) for a in host[:nl]] if grads else []
+    gb = [np.empty(a.shape, np.float32) for a in host[nl:]] if grads else []
+    pw = (C.c_void_p * nl)(*[a.ctypes.data for a in gw]) if grads else None
+    pb = (C.c_void_p * nl)(*[a.ctypes.data for a in gb]) if grads else None
+    dev = p.weights[0].device.index or 0 if p.weights[0].is_cuda else 0
+    s = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
+    check(L.wos_siren_fit(C.byref(st), xs.ctypes.data, n, t.ctypes.data, None if sc is None else sc.ctypes.data,
+                          loss.ctypes.data, pw, pb, ws, 0, dev, s), "wos_siren_fit")
+    del keep, host
+    return (loss[()], gw, gb) if grads else loss[()]
+
+
+_fit_function = None
+
+
+def _fit_fn():
+    """The autograd function behind fit_loss(), defined at first use (this module imports without torch)."""
+    global _fit_function
+    if _fit_function is not None:
+        return _fit_function
+    import torch
+
+    class _SirenFitLoss(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, x, target, scale, shape, *params):
+            nl = len(params) // 2
+            p = PackedSiren(*shape, [t.detach() for t in params[:nl]], [t.detach() for t in params[nl:]])
+            # under no_grad, or with no parameter that requires grad, nothing will ask for a backward
+            if not any(ctx.needs_input_grad[4:]):
+                return torch.as_tensor(fit(p, x, target, scale, grads=False))
+            loss, gw, gb = fit(p, x, target, scale)
+            kept = [torch.as_tensor(t) for t in gw + gb]
+            ctx.shapes = [tuple(t.shape) for t in kept]
+            # the device path hands out views of one buffer: keep that; otherwise gather one
+            base = kept[0]._base if all(t._base is not None and t._base is kept[0]._base for t in kept) else None
+            ctx.save_for_backward(base if base is not None else torch.cat([t.reshape(-1) for t in kept]))
+            return torch.as_tensor(loss)
+
+        @staticmethod
+        @torch.autograd.function.once_differentiable
+        def backward(ctx, g):
+            scaled, out, at = g * ctx.saved_tensors[0], [], 0
+            for shape, need in zip(ctx.shapes, ctx.needs_input_grad[4:]):
+                count = math.prod(shape)
+                out.append(scaled[at:at + count].view(shape) if need else None)
+                at += count
+            return (None, None, None, None) + tuple(out)
+
+    _fit_function = _SirenFitLoss
+    return _fit_function
+
+
+def fit_loss(module, x, target, scale=None):
+    """mean((scale * module(x) - target)^2) as a differentiable scalar of the module's own
+    parameters, through one autograd node over fit(): the forward computes the loss and every
+    parameter gradient in the fused step and keeps the gradients, the backward multiplies them by
+    the incoming scalar (once differentiable: a second-order request raises; retain_graph=True works,
+    nothing is recomputed).  Under torch.no_grad(), or when no parameter requires grad, only the
+    loss-only path runs and no gradient buffer is allocated.  `module`: what pack() takes, as a
+    module.  x, target and scale are constants: one that requires grad is refused."""
+    import torch
+    import torch.nn as nn
+    p = pack(module)
+    for name, a in (("x", x), ("target", target), ("scale", scale)):
+        if getattr(a, "requires_grad", False):
+            raise ValueError(f"siren.fit_loss: {name}.requires_grad is set, and there is no gradient with respect to "
+                             f"{name}; pass {name}.detach()")
+    seq = module if isinstance(module, nn.Sequential) else module.net
+    lin = [m for m in seq if isinstance(m, nn.Linear)]
+    params = [m.weight for m in lin] + [m.bias for m in lin]
+    if not torch.is_grad_enabled():
+        params = [t.detach() for t in params]
+    return _fit_fn().apply(x, target, scale, tuple(p[:5]), *params)
+
+
+_probes = {}  # diagonal_wrap's probe of the last (shape, dtype, device)
+
+
+def diagonal_wrap(wrap, x, d_out, check=True):
+    """(scale, offset) [..., d_out] of a pointwise wrap that is diagonal-affine in the network's
+    output, wrap(x, N) = scale * N + offset -- the time-stepper's query_velocity for karman (inlet
+    clamp, wall and obstacle weights) and taylorgreen (src/2d/models/base.py:169-189):
+    offset = wrap(x, 0), scale = wrap(x, 1) - offset.  check=True probes one random N and raises
+    ValueError unless wrap(x, N) equals scale * N + offset to float rounding: a wrap that mixes the
+    output's components (the jpipe branch) is not covered by fit()'s `scale` and keeps the
+    siren.apply + autograd route.  Pure torch, detached, of x's dtype on x's device."""
+    import torch
+    with torch.no_grad():
+        xd = x.detach()
+        shape = tuple(xd.shape[:-1]) + (int(d_out),)
+        zero = torch.zeros(shape, dtype=xd.dtype, device=xd.device)
+        offset = wrap(xd, zero.clone())
+        if tuple(offset.shape) != shape:
+            raise ValueError(f"siren.diagonal_wrap: wrap returned shape {tuple(offset.shape)} for an output of {shape}")
+        scale = wrap(xd, torch.ones_like(zero)) - offset
+        if check:
+            key = (shape, xd.dtype, xd.device)
+            probe = _probes.get(key)
+            if probe is None:  # one random N per shape, dtype and device, in [0.5, 2.5): no entry is 0 or 1
+                gen = torch.Generator(device="cpu").manual_seed(20240229)
+                probe = (torch.rand(shape, generator=gen, dtype=torch.float64) * 2.0 + 0.5).to(xd.dtype).to(xd.device)
+                _probes.clear()
+                _probes[key] = probe
+            got = wrap(xd, probe.clone())
+            want = scale * probe + offset
+            eps = torch.finfo(xd.dtype).eps
+            tol = 8 * eps * (scale.abs() * probe.abs() + offset.abs() + got.abs())
+            bad = (got - want).abs() > tol
+            if bool(bad.any()):
+                name = getattr(wrap, "__name__", type(wrap).__name__)
+                raise ValueError(f"siren.diagonal_wrap: wrap '{name}' is not diagonal-affine in the network's output "
+                                 f"(it mixes components or is nonlinear: {int(bad.sum())} of {bad.numel()} entries "
+                                 f"differ from scale * N + offset); keep the siren.apply route for it")
+    return scale, offset
