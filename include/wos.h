@@ -649,6 +649,76 @@ int wos_siren_fit(const wos_siren_net *net, const float *pts, int64_t n,
                   size_t workspace_bytes,
                   uint32_t flags, int32_t device, void *stream);
 
+/* ---- Fused Adam step: clip_grad_norm_ and torch.optim.Adam.step() in one call -----------------
+ * The optimiser of the velocity fits (update_network, src/2d/models/base.py:130-152), for any list
+ * of float tensors (added within ABI 10: new entry points only; csrc/wos_siren_train.hip, DESIGN.md
+ * "Fused Adam step and the device-resident fit loop").  n_tensors is 1..20; counts, params and grads
+ * are host arrays of n_tensors entries; exp_avg and exp_avg_sq are single flat buffers of sum(counts)
+ * floats in the order of params; step >= 1 is the step being taken.  Torch's single-tensor Adam with
+ * amsgrad, weight decay and maximize off, f32 with one operation per rounding; from the double
+ * parameters the host computes, each rounded to float once, b2 = beta2, omb1 = 1 - beta1,
+ * omb2 = 1 - beta2, bc2 = sqrt(1 - beta2^step), ss = lr / (1 - beta1^step); per element
+ *   g' = g * c                        (only when clipping)
+ *   m' = m + omb1 * (g' - m)
+ *   v' = v * b2 + (omb2 * g') * g'
+ *   p' = p - ss * (m' / (sqrtf(v') / bc2 + eps))
+ * max_grad_norm > 0 clips: norm = sqrtf(sum g^2), one workgroup of 256 threads summing in a fixed
+ * order over the flat order of the tensors, c = min(max_grad_norm / (norm + 1e-6f), 1); grad_norm
+ * (may be NULL) then receives the unclipped norm.  max_grad_norm <= 0: no norm is computed, grad_norm
+ * is not written.  grads are read, never written (torch's clip scales them in place; this does not).
+ * No atomics: the same call gives the same bits.  Denormal intermediates are not part of the contract.
+ * Pointer rules are wos_siren_fit's: params[k], grads[k], exp_avg, exp_avg_sq and grad_norm are host
+ * pointers (staged, blocking), WOS_PTRS_DEVICE, or WOS_PTRS_DEVICE | WOS_ASYNC on `stream`.
+ * WOS_E_INVALID, naming the field, before any device work: a NULL pointer or entry, n_tensors out of
+ * range, a count <= 0, step < 1, a non-finite lr, beta1 or beta2 outside [0, 1), eps < 0 or not
+ * finite, a non-finite max_grad_norm. */
+typedef struct wos_adam_params {      /* doubles, as torch.optim.Adam holds them */
+    double lr, beta1, beta2, eps;
+    double max_grad_norm;             /* <= 0: no clipping (the reference's default, grad_clip = -1) */
+} wos_adam_params;
+int wos_adam_step(int32_t n_tensors, const int64_t *counts,
+                  float *const *params, const float *const *grads,
+                  float *exp_avg, float *exp_avg_sq,
+                  int64_t step, const wos_adam_params *opt, float *grad_norm,
+                  uint32_t flags, int32_t device, void *stream);
+
+/* ---- Device-resident fit loop: n_iters iterations of gather -> fit step -> Adam step ----------
+ * The projection fit's training loop (_project_velocity, model_split.py:274-283, in _training_loop,
+ * base.py:130-152) on a fixed pool of samples: pool_pts[n_pool*d_in], pool_target[n_pool*d_out],
+ * pool_scale[n_pool*d_out] or NULL, idx[n_iters*batch].  Iteration i gathers the rows idx[i][j] of the
+ * three pool arrays into a contiguous batch, runs wos_siren_fit's step on it (n = batch, the same
+ * workspace_bytes and chunking; the loss to losses[i]) and then wos_adam_step with
+ * step = step0 + i + 1 over weights[0..], biases[0..] -- exp_avg and exp_avg_sq are flat in that
+ * order.  Bit for bit, in the loss, every parameter and both moments, iteration i is those calls
+ * made separately.
+ * THIS IS THE ONE ENTRY POINT THAT WRITES THROUGH net->weights[l] AND net->biases[l]: the network
+ * is updated in place.
+ * Device pointers only: without WOS_PTRS_DEVICE the call is WOS_E_INVALID.  One stream-ordered
+ * temporary per call holds the packed weights, the batch, the gradients and the fit step's work.
+ * An index outside [0, n_pool) is clamped (no out-of-bounds read) and counted in status[1]; a
+ * blocking call that ends with status[1] != 0 returns WOS_E_INVALID.
+ * Early stop (the reference's `if early_stop and loss <= 1.1e-10: break` after update_network):
+ * stop_loss < 0 never stops.  Otherwise iteration i's update is applied; then, in stream order, a
+ * sticky device flag is set when losses[i] <= stop_loss, and every later iteration's Adam step and
+ * loss write are no-ops.  losses is filled with NaN at the start, so losses[j] is NaN from the stop
+ * on; status[0] is the number of iterations applied.  check_every = 0 enqueues all n_iters
+ * iterations without a host synchronisation; check_every = c > 0 (blocking calls only: with
+ * WOS_ASYNC it is WOS_E_INVALID) synchronises after every c iterations, reads the flag and stops
+ * enqueuing.  The results are the same bits either way.  With check_every = 0 a stop does not shorten
+ * the call: every remaining iteration still runs its gather, both packs, the fit step and the norm
+ * kernel, only the Adam update and the loss write being switched off; a caller that expects early
+ * stops sets check_every.
+ * WOS_E_INVALID: n_iters, batch or n_pool <= 0, step0 < 0, a NULL idx, losses, status, pool_pts or
+ * pool_target, a NaN stop_loss, wos_adam_step's parameter rules, wos_siren_eval's envelope.
+ * A non-zero workspace_bytes below one tile is WOS_E_CAPACITY, as in wos_siren_fit. */
+int wos_siren_fit_run(const wos_siren_net *net,
+                      const float *pool_pts, const float *pool_target, const float *pool_scale, int64_t n_pool,
+                      const int64_t *idx, int64_t n_iters, int64_t batch,
+                      float *exp_avg, float *exp_avg_sq, int64_t step0, const wos_adam_params *opt,
+                      float stop_loss, int32_t check_every,
+                      float *losses, int64_t *status,
+                      size_t workspace_bytes, uint32_t flags, int32_t device, void *stream);
+
 const char *wos_last_error(void);
 int32_t wos_abi_version(void);
 int32_t wos_device_count(void);

@@ -1,7 +1,7 @@
 // wos_capi_probes.cpp -- entry points that need neither a scene's workspace nor the device context:
 // the self-test probes (wos_selftest_*, kernels in wos_selftest.hip) and the fused SIREN
-// (wos_siren_eval, wos_siren.hip; wos_siren_vjp, wos_siren_vjp.hip; wos_siren_fit, wos_siren_fit.hip).  Each call
-// owns what it allocates.
+// (wos_siren_eval, wos_siren.hip; wos_siren_vjp, wos_siren_vjp.hip; wos_siren_fit, wos_siren_fit.hip;
+// wos_adam_step and wos_siren_fit_run, wos_siren_train.hip).  Each call owns what it allocates.
 #include "wos_capi.h"
 
 using namespace wos::capi;
@@ -626,6 +626,254 @@ int wos_selftest_siren_vjp_layer(int32_t hidden, int32_t d_in, int64_t n_points,
   HIP_TRY(hipDeviceSynchronize());
   HIP_TRY(hipMemcpy(dX, d_dX, nx * 4, hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(dW, d_dW, hh * 4, hipMemcpyDeviceToHost));
+  return WOS_OK;
+}
+
+// ---- fused Adam step and the device-resident fit loop (wos_siren_train.hip) --------------------
+static_assert(wos::kAdamMaxTensors == 20, "include/wos.h documents n_tensors as 1..20");
+static_assert(sizeof(wos_adam_params) == 5 * sizeof(double), "wos_adam_params is five doubles (wos_amd/_lib.py AdamParams)");
+static_assert(sizeof(wos::AdamSegs) + sizeof(wos::AdamScalars) + 4 * sizeof(void*) <= 4096,
+              "adam_update_kernel's arguments, the segment table included, fit the kernel argument segment");
+static int adam_params_check(const std::string& fn, const wos_adam_params* opt) {
+  if (!opt) return fail(WOS_E_INVALID, fn + ": null opt");
+  if (!std::isfinite(opt->lr)) return fail(WOS_E_INVALID, fn + ": lr must be finite");
+  if (!(opt->beta1 >= 0.0 && opt->beta1 < 1.0))
+    return fail(WOS_E_INVALID, fn + ": beta1 must be in [0, 1), got " + std::to_string(opt->beta1));
+  if (!(opt->beta2 >= 0.0 && opt->beta2 < 1.0))
+    return fail(WOS_E_INVALID, fn + ": beta2 must be in [0, 1), got " + std::to_string(opt->beta2));
+  if (!(opt->eps >= 0.0) || !std::isfinite(opt->eps))
+    return fail(WOS_E_INVALID, fn + ": eps must be finite and >= 0, got " + std::to_string(opt->eps));
+  if (!std::isfinite(opt->max_grad_norm)) return fail(WOS_E_INVALID, fn + ": max_grad_norm must be finite");
+  return WOS_OK;
+}
+
+// the step's five scalars in double from the double parameters, each rounded to float once
+static wos::AdamScalars adam_scalars(const wos_adam_params& o, int64_t step) {
+  wos::AdamScalars s{};
+  s.b2 = (float)o.beta2;
+  s.omb1 = (float)(1.0 - o.beta1);
+  s.omb2 = (float)(1.0 - o.beta2);
+  s.bc2 = (float)std::sqrt(1.0 - std::pow(o.beta2, (double)step));
+  s.ss = (float)(o.lr / (1.0 - std::pow(o.beta1, (double)step)));
+  s.eps = (float)o.eps;
+  s.max_norm = (float)o.max_grad_norm;
+  return s;
+}
+
+// Device pointers: stream-ordered, one float of scratch only when clipping without grad_norm.
+// Host pointers: one staging allocation -- params | grads | exp_avg | exp_avg_sq | norm.
+int wos_adam_step(int32_t n_tensors, const int64_t* counts, float* const* params, const float* const* grads,
+                  float* exp_avg, float* exp_avg_sq, int64_t step, const wos_adam_params* opt, float* grad_norm,
+                  uint32_t flags, int32_t device, void* stream) {
+  const std::string fn = "wos_adam_step";
+  if (n_tensors < 1 || n_tensors > wos::kAdamMaxTensors)
+    return fail(WOS_E_INVALID, fn + ": n_tensors must be 1.." + std::to_string(wos::kAdamMaxTensors) + ", got " +
+                                   std::to_string(n_tensors));
+  if (!counts) return fail(WOS_E_INVALID, fn + ": null counts");
+  if (!params) return fail(WOS_E_INVALID, fn + ": null params array");
+  if (!grads) return fail(WOS_E_INVALID, fn + ": null grads array");
+  if (!exp_avg) return fail(WOS_E_INVALID, fn + ": null exp_avg");
+  if (!exp_avg_sq) return fail(WOS_E_INVALID, fn + ": null exp_avg_sq");
+  wos::AdamSegs segs{};
+  segs.n = n_tensors;
+  int64_t total = 0;
+  for (int k = 0; k < n_tensors; k++) {
+    if (counts[k] <= 0 || counts[k] > (int64_t)1 << 40)
+      return fail(WOS_E_INVALID, fn + ": counts[" + std::to_string(k) + "] must be positive (at most 2^40), got " +
+                                     std::to_string(counts[k]));
+    if (!params[k]) return fail(WOS_E_INVALID, fn + ": null params pointer of tensor " + std::to_string(k));
+    if (!grads[k]) return fail(WOS_E_INVALID, fn + ": null grads pointer of tensor " + std::to_string(k));
+    total += counts[k];
+    segs.end[k] = total;
+  }
+  if (step < 1) return fail(WOS_E_INVALID, fn + ": step must be >= 1 (the step being taken), got " + std::to_string(step));
+  if (int rc = adam_params_check(fn, opt)) return rc;
+  const bool clip = opt->max_grad_norm > 0.0;
+  const wos::AdamScalars sc = adam_scalars(*opt, step);
+  HIP_TRY(hipSetDevice(device));
+  hipStream_t st = (hipStream_t)stream;
+  const auto run = [&](float* m, float* v, float* norm) -> hipError_t {
+    hipError_t e;
+    if (clip && (e = wos::launch_adam_norm(segs, norm, st)) != hipSuccess) return e;
+    return wos::launch_adam_update(segs, m, v, sc, clip ? norm : nullptr, nullptr, st);
+  };
+  if (flags & WOS_PTRS_DEVICE) {
+    for (int k = 0; k < n_tensors; k++) {
+      segs.p[k] = params[k];
+      segs.g[k] = grads[k];
+    }
+    float* scratch = nullptr;
+    if (clip && !grad_norm && hipMallocAsync((void**)&scratch, sizeof(float), st) != hipSuccess)
+      return fail(WOS_E_NOMEM, fn + ": cannot allocate the norm's scratch word");
+    hipError_t e = run(exp_avg, exp_avg_sq, grad_norm ? grad_norm : scratch);
+    if (scratch) {
+      const hipError_t e2 = hipFreeAsync(scratch, st);
+      if (e == hipSuccess) e = e2;
+    }
+    if (e == hipSuccess && !(flags & WOS_ASYNC)) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return fail(WOS_E_DEVICE, fn + ": " + hipGetErrorString(e));
+    return WOS_OK;
+  }
+  const size_t T = (size_t)total, o_g = T, o_m = 2 * T, o_v = 3 * T, o_norm = 4 * T;
+  float* tmp = nullptr;
+  if (hipMalloc((void**)&tmp, (o_norm + 1) * sizeof(float)) != hipSuccess)
+    return fail(WOS_E_NOMEM, fn + ": cannot allocate " + std::to_string((o_norm + 1) * sizeof(float)) + " bytes of staging");
+  const auto staged = [&]() -> hipError_t {
+    hipError_t e;
+    const auto up = [&](size_t o, const float* src, size_t count) {
+      return hipMemcpyAsync(tmp + o, src, count * sizeof(float), hipMemcpyHostToDevice, st);
+    };
+    for (int k = 0; k < n_tensors; k++) {
+      const size_t at = (size_t)(segs.end[k] - counts[k]);
+      if ((e = up(at, params[k], (size_t)counts[k])) != hipSuccess) return e;
+      if ((e = up(o_g + at, grads[k], (size_t)counts[k])) != hipSuccess) return e;
+      segs.p[k] = tmp + at;
+      segs.g[k] = tmp + o_g + at;
+    }
+    if ((e = up(o_m, exp_avg, T)) != hipSuccess) return e;
+    if ((e = up(o_v, exp_avg_sq, T)) != hipSuccess) return e;
+    if ((e = run(tmp + o_m, tmp + o_v, tmp + o_norm)) != hipSuccess) return e;
+    const auto down = [&](float* dst, size_t o, size_t count) {
+      return hipMemcpyAsync(dst, tmp + o, count * sizeof(float), hipMemcpyDeviceToHost, st);
+    };
+    for (int k = 0; k < n_tensors; k++)
+      if ((e = down(params[k], (size_t)(segs.end[k] - counts[k]), (size_t)counts[k])) != hipSuccess) return e;
+    if ((e = down(exp_avg, o_m, T)) != hipSuccess) return e;
+    if ((e = down(exp_avg_sq, o_v, T)) != hipSuccess) return e;
+    if (clip && grad_norm && (e = down(grad_norm, o_norm, 1)) != hipSuccess) return e;
+    return hipStreamSynchronize(st);
+  };
+  const hipError_t e = staged();
+  if (e != hipSuccess) hipStreamSynchronize(st);  // nothing may still use tmp when it is freed
+  hipFree(tmp);
+  if (e != hipSuccess) return fail(WOS_E_DEVICE, fn + ": " + hipGetErrorString(e));
+  return WOS_OK;
+}
+
+// One stream-ordered temporary per run: packed | packedT | H zeros | the plan's work (wos_siren_fit's
+// layout), then the batch's points, target and scale, the flat gradients (weights, then biases: the
+// order of exp_avg) and the state words [stop flag, loss, norm], each on a 256-byte boundary.
+int wos_siren_fit_run(const wos_siren_net* net, const float* pool_pts, const float* pool_target, const float* pool_scale,
+                      int64_t n_pool, const int64_t* idx, int64_t n_iters, int64_t batch, float* exp_avg,
+                      float* exp_avg_sq, int64_t step0, const wos_adam_params* opt, float stop_loss, int32_t check_every,
+                      float* losses, int64_t* status, size_t workspace_bytes, uint32_t flags, int32_t device,
+                      void* stream) {
+  const std::string fn = "wos_siren_fit_run";
+  if (int rc = siren_net_check(fn, net)) return rc;
+  const int D = net->d_in, DO = net->d_out, H = net->hidden, L = net->n_hidden_layers, NL = L + 2;
+  if (!(flags & WOS_PTRS_DEVICE)) return fail(WOS_E_INVALID, fn + ": flags: device pointers only (WOS_PTRS_DEVICE)");
+  if (check_every < 0) return fail(WOS_E_INVALID, fn + ": check_every must be >= 0, got " + std::to_string(check_every));
+  if ((flags & WOS_ASYNC) && check_every > 0)
+    return fail(WOS_E_INVALID, fn + ": check_every > 0 synchronises with the host and cannot be WOS_ASYNC");
+  if (n_iters <= 0) return fail(WOS_E_INVALID, fn + ": n_iters must be positive, got " + std::to_string(n_iters));
+  if (batch <= 0) return fail(WOS_E_INVALID, fn + ": batch must be positive, got " + std::to_string(batch));
+  if (n_pool <= 0) return fail(WOS_E_INVALID, fn + ": n_pool must be positive, got " + std::to_string(n_pool));
+  if (batch > (int64_t)0x7FFFFFFF * wos::kSirenTile) return fail(WOS_E_INVALID, fn + ": batch: too many points for one step");
+  if (n_iters > (int64_t)1 << 40) return fail(WOS_E_INVALID, fn + ": n_iters: too many iterations for one call");
+  if (step0 < 0) return fail(WOS_E_INVALID, fn + ": step0 must be >= 0, got " + std::to_string(step0));
+  if (!pool_pts) return fail(WOS_E_INVALID, fn + ": null pool_pts");
+  if (!pool_target) return fail(WOS_E_INVALID, fn + ": null pool_target");
+  if (!idx) return fail(WOS_E_INVALID, fn + ": null idx");
+  if (!losses) return fail(WOS_E_INVALID, fn + ": null losses");
+  if (!status) return fail(WOS_E_INVALID, fn + ": null status");
+  if (!exp_avg) return fail(WOS_E_INVALID, fn + ": null exp_avg");
+  if (!exp_avg_sq) return fail(WOS_E_INVALID, fn + ": null exp_avg_sq");
+  if (std::isnan(stop_loss)) return fail(WOS_E_INVALID, fn + ": stop_loss is NaN (negative: never stop)");
+  if (int rc = adam_params_check(fn, opt)) return rc;
+  const size_t tile_bytes = wos::siren_fit_stash_floats_per_tile(H, L) * sizeof(float);
+  if (workspace_bytes != 0 && workspace_bytes < tile_bytes)
+    return fail(WOS_E_CAPACITY, fn + ": workspace_bytes " + std::to_string(workspace_bytes) +
+                                    " cannot hold one tile's stash of " + std::to_string(tile_bytes) + " bytes");
+  HIP_TRY(hipSetDevice(device));
+  hipStream_t st = (hipStream_t)stream;
+  wos::SirenNet dn{};
+  dn.d_in = D;
+  dn.d_out = DO;
+  dn.H = H;
+  dn.L = L;
+  dn.omega = net->omega;
+  int cus = 0;
+  HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
+  const int per_cu = std::max<int>(1, (int)(kLdsDynamicMax / wos::siren_fit_tile_lds_bytes(D, H)));
+  const wos::SirenFitPlan plan =
+      wos::siren_fit_plan(dn, batch, workspace_bytes ? workspace_bytes : kSirenVjpDefaultStash, cus * per_cu);
+  const auto pad = [](size_t floats) { return (floats + 63) / 64 * 64; };
+  const size_t pack_n = wos::siren_pack_floats(H, L), B = (size_t)batch;
+  size_t n_par = 0;
+  for (int l = 0; l < NL; l++) n_par += (l == NL - 1 ? (size_t)DO : (size_t)H) * ((l == 0 ? (size_t)D : (size_t)H) + 1);
+  const size_t o_packT = pack_n, o_zero = 2 * pack_n, o_work = o_zero + (size_t)H, o_pts = pad(o_work + plan.total(true)),
+               o_t = o_pts + pad(B * D), o_s = o_t + pad(B * DO), o_g = o_s + (pool_scale ? pad(B * DO) : 0),
+               o_state = o_g + pad(n_par), total = o_state + 64;
+  // the Adam step's tensors and the fit step's gradient pointers: weights, then biases, one flat buffer
+  wos::AdamSegs segs{};
+  wos::SirenGrads dg{};
+  segs.n = 2 * NL;
+  float* tmp = nullptr;
+  if (hipMallocAsync((void**)&tmp, total * sizeof(float), st) != hipSuccess)
+    return fail(WOS_E_NOMEM, fn + ": cannot allocate " + std::to_string(total * sizeof(float)) + " bytes of workspace");
+  size_t at = 0;
+  for (int k = 0; k < 2 * NL; k++) {
+    const int l = k < NL ? k : k - NL;
+    const size_t rows = l == NL - 1 ? (size_t)DO : (size_t)H, count = k < NL ? rows * (l == 0 ? (size_t)D : (size_t)H) : rows;
+    float* g = tmp + o_g + at;
+    segs.p[k] = const_cast<float*>(k < NL ? net->weights[l] : net->biases[l]);
+    segs.g[k] = g;
+    (k < NL ? dg.w[l] : dg.b[l]) = g;
+    at += count;
+    segs.end[k] = (int64_t)at;
+  }
+  for (int l = 0; l < NL; l++) {
+    dn.w[l] = net->weights[l];
+    dn.b[l] = net->biases[l];
+  }
+  int* state = (int*)(tmp + o_state);
+  float *loss = tmp + o_state + 1, *norm = tmp + o_state + 2;
+  float *b_pts = tmp + o_pts, *b_t = tmp + o_t, *b_s = pool_scale ? tmp + o_s : nullptr;
+  const bool clip = opt->max_grad_norm > 0.0;
+  int stopped = 0;  // the flag as last read on the host (check_every > 0)
+  const auto run = [&]() -> hipError_t {
+    hipError_t e;
+    if ((e = hipMemsetAsync(state, 0, 64 * sizeof(float), st)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(status, 0, 2 * sizeof(int64_t), st)) != hipSuccess) return e;
+    if ((e = hipMemsetD32Async((hipDeviceptr_t)losses, 0x7FC00000, (size_t)n_iters, st)) != hipSuccess) return e;
+    int64_t pending = -1;  // the iteration whose commit has not been enqueued yet
+    for (int64_t i = 0; i < n_iters; i++) {
+      if ((e = wos::launch_fit_run_gather(D, DO, pool_pts, pool_target, pool_scale, n_pool, idx + i * batch, batch, b_pts,
+                                          b_t, b_s, state, pending, stop_loss, losses, status, st)) != hipSuccess)
+        return e;
+      if ((e = wos::launch_siren_pack(dn, tmp, st)) != hipSuccess) return e;
+      if ((e = hipMemsetAsync(tmp + o_zero, 0, (size_t)H * sizeof(float), st)) != hipSuccess) return e;
+      if ((e = wos::launch_siren_pack_transposed(dn, tmp + o_packT, st)) != hipSuccess) return e;
+      if ((e = wos::launch_siren_fit(dn, tmp, tmp + o_packT, tmp + o_zero, b_pts, batch, b_t, b_s, loss, &dg, plan,
+                                     tmp + o_work, st)) != hipSuccess)
+        return e;
+      if (clip && (e = wos::launch_adam_norm(segs, norm, st)) != hipSuccess) return e;
+      if ((e = wos::launch_adam_update(segs, exp_avg, exp_avg_sq, adam_scalars(*opt, step0 + i + 1), clip ? norm : nullptr,
+                                       state, st)) != hipSuccess)
+        return e;
+      pending = i;
+      if (check_every > 0 && (i + 1) % check_every == 0 && i + 1 < n_iters) {
+        if ((e = wos::launch_fit_run_commit(state, i, stop_loss, losses, status, st)) != hipSuccess) return e;
+        pending = -1;
+        if ((e = hipMemcpyAsync(&stopped, state, sizeof(int), hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
+        if ((e = hipStreamSynchronize(st)) != hipSuccess) return e;
+        if (stopped) break;
+      }
+    }
+    if (pending >= 0) return wos::launch_fit_run_commit(state, pending, stop_loss, losses, status, st);
+    return hipSuccess;
+  };
+  hipError_t e = run();
+  const hipError_t e2 = hipFreeAsync(tmp, st);
+  if (e == hipSuccess) e = e2;
+  int64_t bad = 0;
+  if (e == hipSuccess && !(flags & WOS_ASYNC)) {
+    e = hipMemcpyAsync(&bad, status + 1, sizeof(int64_t), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+  }
+  if (e != hipSuccess) return fail(WOS_E_DEVICE, fn + ": " + hipGetErrorString(e));
+  if (bad != 0)
+    return fail(WOS_E_INVALID, fn + ": idx: " + std::to_string(bad) + " indices outside [0, n_pool) were clamped (status[1])");
   return WOS_OK;
 }
 

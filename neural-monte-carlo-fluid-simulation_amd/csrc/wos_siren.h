@@ -129,4 +129,37 @@ hipError_t launch_siren_fit(const SirenNet& net, const float* packed, const floa
                             const float* pts, int64_t n, const float* target, const float* scale, float* loss,
                             const SirenGrads* grads, const SirenFitPlan& plan, float* work, hipStream_t s);
 
+// ---- optimiser step and the device-resident fit loop (wos_siren_train.hip) ----------------------
+// The tensors of one Adam step in their flat order: tensor k holds the elements [end[k - 1], end[k])
+// of exp_avg and exp_avg_sq, its parameters at p[k] and its gradients at g[k].
+constexpr int kAdamMaxTensors = 2 * kSirenMaxLayers;
+struct AdamSegs {
+  int n;
+  int64_t end[kAdamMaxTensors];
+  float* p[kAdamMaxTensors];
+  const float* g[kAdamMaxTensors];
+};
+// The step's scalars, each rounded once from double: beta2, 1 - beta1, 1 - beta2, sqrt(1 - beta2^step),
+// lr / (1 - beta1^step), eps, max_grad_norm.
+struct AdamScalars {
+  float b2, omb1, omb2, bc2, ss, eps, max_norm;
+};
+// norm[0] = the L2 norm of all gradients, one workgroup, a fixed order.
+hipError_t launch_adam_norm(const AdamSegs& segs, float* norm, hipStream_t s);
+// norm non-null: the gradients count as g * min(max_norm / (norm[0] + 1e-6f), 1).  stop non-null and
+// stop[0] != 0: nothing is written.
+hipError_t launch_adam_update(const AdamSegs& segs, float* exp_avg, float* exp_avg_sq, const AdamScalars& sc,
+                              const float* norm, const int* stop, hipStream_t s);
+// wos_siren_fit_run's state: state[0] the sticky stop flag, state[1] the bits of the iteration's loss.
+// The gather copies rows idx[0 .. batch) of the pool arrays (pool_scale and scale may be null) into
+// pts / target / scale, clamping and counting (status[1]) an index outside [0, n_pool), and commits
+// iteration prev >= 0 first: unless stopped, losses[prev] = the loss, status[0] = prev + 1, and the
+// flag is set when stop_loss >= 0 and the loss <= stop_loss.  launch_fit_run_commit: the commit alone.
+hipError_t launch_fit_run_gather(int d_in, int d_out, const float* pool_pts, const float* pool_target,
+                                 const float* pool_scale, int64_t n_pool, const int64_t* idx, int64_t batch, float* pts,
+                                 float* target, float* scale, int* state, int64_t prev, float stop_loss, float* losses,
+                                 int64_t* status, hipStream_t s);
+hipError_t launch_fit_run_commit(int* state, int64_t iter, float stop_loss, float* losses, int64_t* status,
+                                 hipStream_t s);
+
 }  // namespace wos

@@ -114,6 +114,12 @@ class SirenNet(C.Structure):
                 ("omega", C.c_float), ("weights", C.POINTER(C.c_void_p)), ("biases", C.POINTER(C.c_void_p))]
 
 
+class AdamParams(C.Structure):
+    """wos_adam_params: doubles, as torch.optim.Adam holds them; max_grad_norm <= 0: no clipping."""
+    _fields_ = [("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double),
+                ("max_grad_norm", C.c_double)]
+
+
 # exported symbols, exactly those declared in include/wos.h
 EXPORTS = (
     "wos_load_obj", "wos_mesh_free", "wos_scene_create", "wos_scene_destroy",
@@ -129,6 +135,7 @@ EXPORTS = (
     "wos_siren_eval", "wos_selftest_siren_layer",
     "wos_siren_vjp", "wos_selftest_siren_vjp_layer",
     "wos_siren_fit",
+    "wos_adam_step", "wos_siren_fit_run",
 )
 
 # include/wos.h WOS_QUERY_*: the boundary wos_scene_query's dist / signed_dist / closest describe
@@ -235,6 +242,15 @@ def load():
     L.wos_siren_fit.argtypes = [C.POINTER(SirenNet), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                 C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_size_t, C.c_uint32, C.c_int32,
                                 C.c_void_p]
+    L.wos_adam_step.restype = C.c_int
+    L.wos_adam_step.argtypes = [C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(AdamParams), C.c_void_p, C.c_uint32,
+                                C.c_int32, C.c_void_p]
+    L.wos_siren_fit_run.restype = C.c_int
+    L.wos_siren_fit_run.argtypes = [C.POINTER(SirenNet), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                    C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(AdamParams),
+                                    C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_int32,
+                                    C.c_void_p]
     L.wos_selftest_siren_vjp_layer.restype = C.c_int
     L.wos_selftest_siren_vjp_layer.argtypes = [C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                                C.c_void_p, C.c_void_p, C.c_int32]

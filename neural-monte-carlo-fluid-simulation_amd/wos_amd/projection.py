@@ -395,6 +395,59 @@ class PressureProjector:
                 target = wrap(x, u_prev) - grad_p[idx] - offset
         return _siren.fit_loss(network, x, target, scale)
 
+    def fit_projection(self, network, network_prev, grad_p, n_samples, n_iters, *, state=None, wrap=None,
+                       generator=None, early_stop=None, iters_per_call=256, lr=1e-4):
+        """The whole training loop of _project_velocity (n_iters iterations of projection_fit_loss,
+        backward and Adam: _training_loop, src/2d/models/base.py:130-152) on the device, through
+        wos_amd.siren.fit_run.  The sample pool, grad_p and the previous network are fixed for the
+        loop, so u_prev = siren.eval(network_prev, samples), the wrap's (scale, offset) and the target
+        wrap(samples, u_prev) - grad_p - offset are computed once over the whole pool; an iteration is
+        then gather by index, fit step, Adam step.  The indices are drawn one
+        torch.randint(0, hi, (n_samples,)) per iteration -- projection_fit_loss's range rule and
+        generator consumption: a generator seeded alike selects the same samples as n_iters calls of
+        projection_fit_loss -- and handed over in blocks of iters_per_call iterations (256 x 16384
+        indices are 33 MB).  Iteration 0's loss is projection_fit_loss's, bit for bit.
+        `network` IS UPDATED IN PLACE.  state: a wos_amd.siren.AdamState to continue (None: a fresh
+        one with `lr`).  early_stop: None, or the loss at or below which the loop stops after that
+        iteration's update (True: the reference's 1.1e-10); it costs one host synchronisation per
+        block, and the losses from the stop on are NaN; no further block is drawn after a stop, but
+        the rest of the stopping block is already enqueued and still pays its gathers and fit steps
+        with the update switched off -- a smaller iters_per_call bounds that cost.
+        Returns (losses [n_iters], state)."""
+        n_iters, per_call = int(n_iters), int(iters_per_call)
+        if n_iters < 1 or per_call < 1:
+            raise ValueError(f"fit_projection: n_iters and iters_per_call must be positive, got {n_iters}, {per_call}")
+        if state is None:
+            state = _siren.AdamState(network, lr=lr)
+        stop = None if early_stop is None or early_stop is False else (1.1e-10 if early_stop is True else float(early_stop))
+        n = self.samples.shape[0]
+        hi = n - 1 if self.dim == 2 else n
+        with torch.no_grad():
+            u_prev = _siren.eval(network_prev, self.samples)
+            if wrap is None:
+                scale, target = None, u_prev - grad_p
+            else:
+                scale, offset = _diagonal(wrap, self.samples, u_prev.shape[-1])
+                target = wrap(self.samples, u_prev) - grad_p - offset
+        losses = []
+        for first in range(0, n_iters, per_call):
+            k = min(per_call, n_iters - first)
+            idx = torch.stack([torch.randint(0, hi, (n_samples,), device=self.device, generator=generator)
+                               for _ in range(k)])
+            block, status = _siren.fit_run(network, state, self.samples, target, scale, idx, stop_loss=stop)
+            losses.append(block)
+            if stop is None:
+                continue
+            # fit_run has synchronised already.  The stopping iteration is applied and counted, so a stop at the
+            # block's last iteration leaves status[0] == k: the last applied loss tells, by the device's own test
+            # (float32 loss <= stop_loss as a float).
+            applied = int(status[0])
+            if applied < k or float(block[applied - 1]) <= float(np.float32(stop)):
+                if first + k < n_iters:
+                    losses.append(torch.full((n_iters - first - k,), float("nan"), dtype=block.dtype, device=block.device))
+                break
+        return torch.cat(losses), state
+
 
 _checked_wraps = weakref.WeakSet()
 

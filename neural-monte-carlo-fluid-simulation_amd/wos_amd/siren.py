@@ -11,6 +11,9 @@ trains through the projection without an autograd graph over the network.  fit()
 of the time-stepper's velocity fits -- the regression loss of the value and its weight gradients in
 one value-only pass (wos_siren_fit, csrc/wos_siren_fit.hip) -- fit_loss() the same as an autograd
 scalar, diagonal_wrap() the (scale, offset) form of query_velocity's masks that fit() takes.
+adam_step() is the loop's optimiser -- clip_grad_norm_ and torch.optim.Adam.step() in one call on an
+AdamState (wos_adam_step, csrc/wos_siren_train.hip) -- and fit_run() K iterations of gather, fit()
+and adam_step() on a fixed pool from one call (wos_siren_fit_run).
 """
 import collections
 import ctypes as C
@@ -545,6 +548,198 @@ def fit_loss(module, x, target, scale=None):
     if not torch.is_grad_enabled():
         params = [t.detach() for t in params]
     return _fit_fn().apply(x, target, scale, tuple(p[:5]), *params)
+
+
+class AdamState:
+    """torch.optim.Adam's state for one network, as wos_adam_step and wos_siren_fit_run take it:
+    exp_avg and exp_avg_sq, flat float32 buffers of zeros on the network's device over
+    weights + biases in pack() order (the order of fit()'s flat gradient buffer), and `step`, the
+    number of steps taken (a Python int).  lr, betas and eps stay Python floats: the library derives
+    the step's scalars from the doubles, as torch does.  max_grad_norm=None (or <= 0): no clipping --
+    the reference's default, grad_clip = -1."""
+
+    def __init__(self, net, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=None):
+        import torch
+        p = net if isinstance(net, PackedSiren) else pack(net)
+        self.lr, self.betas, self.eps = float(lr), (float(betas[0]), float(betas[1])), float(eps)
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.counts = [int(t.numel()) for t in p.weights + p.biases]
+        total = sum(self.counts)
+        self.exp_avg = torch.zeros(total, dtype=torch.float32, device=p.weights[0].device)
+        self.exp_avg_sq = torch.zeros_like(self.exp_avg)
+        self.step = 0
+
+    @property
+    def clips(self):
+        return self.max_grad_norm is not None and self.max_grad_norm > 0
+
+    def params(self):
+        """The wos_adam_params of this state."""
+        return _lib.AdamParams(self.lr, self.betas[0], self.betas[1], self.eps,
+                               self.max_grad_norm if self.clips else -1.0)
+
+
+def _stream_of(stream, held, device):
+    """eval()'s stream discipline: the raw stream to enqueue on, after making `stream` wait for
+    torch's current stream and recording the held tensors on it."""
+    import torch
+    cur = torch.cuda.current_stream(device)
+    if stream is None:
+        return cur.cuda_stream
+    ts = stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.ExternalStream(int(stream), device=device)
+    ts.wait_stream(cur)  # the tensors belong to torch's current stream
+    for t in held:
+        t.record_stream(ts)  # ... and are used on `stream`: the allocator must wait for it
+    return ts.cuda_stream
+
+
+def adam_step(net, grads, state, *, stream=None):
+    """clip_grad_norm_ (when state.max_grad_norm is set) and torch.optim.Adam.step() in one call
+    (wos_adam_step, csrc/wos_siren_train.hip) on the network's weights and biases, with the gradients
+    grads = (grad_weights, grad_biases) as fit() returns them; they are read, never scaled in place.
+    Torch CUDA gradients (the network on the same device): the network's own tensors and the state's
+    moments are updated in place through their data_ptr(), enqueued on `stream` as in eval() without
+    a host synchronisation; returns the unclipped gradient norm (a 0-d device tensor) when clipping
+    is on, else None.  numpy gradients: the host-pointer path, blocking -- the network itself is left
+    alone and (weights, biases, norm or None) come back as numpy, the updated copies in pack() order;
+    the state's moments are updated.  Either way state.step is incremented: the step taken is
+    state.step + 1."""
+    p = net if isinstance(net, PackedSiren) else pack(net)
+    gw, gb = grads
+    nl = p.n_hidden_layers + 2
+    if len(gw) != nl or len(gb) != nl:
+        raise ValueError(f"siren.adam_step: grads must be ({nl} weight gradients, {nl} bias gradients), got "
+                         f"({len(gw)}, {len(gb)})")
+    tensors, g = p.weights + p.biases, list(gw) + list(gb)
+    for k, (t, a) in enumerate(zip(tensors, g)):
+        if tuple(a.shape) != tuple(t.shape):
+            raise ValueError(f"siren.adam_step: gradient {k} has shape {tuple(a.shape)}, its tensor {tuple(t.shape)}")
+    if state.counts != [int(t.numel()) for t in tensors]:
+        raise ValueError("siren.adam_step: state was made for a network of another shape")
+    n = len(tensors)
+    counts = (C.c_int64 * n)(*state.counts)
+    opt = state.params()
+    L = _lib.load()
+    if _is_torch(g[0]) and g[0].is_cuda:
+        import torch
+        dev = g[0].device
+        if any(not _is_torch(a) or a.device != dev or a.dtype != torch.float32 for a in g):
+            raise ValueError(f"siren.adam_step: every gradient must be a float32 tensor on {dev}")
+        if any(t.device != dev for t in tensors) or state.exp_avg.device != dev:
+            raise ValueError(f"siren.adam_step: the gradients are on {dev}, the network on {tensors[0].device}, "
+                             f"the state on {state.exp_avg.device}")
+        g = [a.detach().contiguous() for a in g]
+        norm = torch.empty((), dtype=torch.float32, device=dev) if state.clips else None
+        held = g + tensors + [state.exp_avg, state.exp_avg_sq] + ([] if norm is None else [norm])
+        s = _stream_of(stream, held, dev)
+        pp = (C.c_void_p * n)(*[t.data_ptr() for t in tensors])
+        pg = (C.c_void_p * n)(*[a.data_ptr() for a in g])
+        check(L.wos_adam_step(n, counts, pp, pg, state.exp_avg.data_ptr(), state.exp_avg_sq.data_ptr(), state.step + 1,
+                              C.byref(opt), None if norm is None else norm.data_ptr(),
+                              _lib.WOS_PTRS_DEVICE | _lib.WOS_ASYNC, dev.index or 0, s), "wos_adam_step")
+        del held
+        state.step += 1
+        return norm
+    g = [np.ascontiguousarray(a.detach().cpu().numpy() if _is_torch(a) else a, dtype=np.float32) for a in g]
+    host = [np.array(t.cpu().numpy(), dtype=np.float32, order="C") for t in tensors]  # copies: the net is left alone
+    m, v = state.exp_avg.cpu().numpy().copy(), state.exp_avg_sq.cpu().numpy().copy()
+    norm = np.empty((), np.float32) if state.clips else None
+    pp = (C.c_void_p * n)(*[a.ctypes.data for a in host])
+    pg = (C.c_void_p * n)(*[a.ctypes.data for a in g])
+    dev = tensors[0].device.index or 0 if tensors[0].is_cuda else 0
+    s = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
+    check(L.wos_adam_step(n, counts, pp, pg, m.ctypes.data, v.ctypes.data, state.step + 1, C.byref(opt),
+                          None if norm is None else norm.ctypes.data, 0, dev, s), "wos_adam_step")
+    import torch
+    state.exp_avg.copy_(torch.from_numpy(m))
+    state.exp_avg_sq.copy_(torch.from_numpy(v))
+    state.step += 1
+    return host[:nl], host[nl:], None if norm is None else norm[()]
+
+
+def fit_run(net, state, pool_x, pool_target, pool_scale, idx, *, stop_loss=None, check_every=0, stream=None,
+            workspace_bytes=None):
+    """K iterations of gather -> fit() -> adam_step() in one call (wos_siren_fit_run,
+    csrc/wos_siren_train.hip), for a fit whose samples, target and scale are fixed for the whole loop
+    (the projection fit): iteration i takes the rows idx[i] of pool_x [n_pool, d_in], pool_target and
+    pool_scale [n_pool, d_out] (pool_scale may be None), and equals, bit for bit in the loss, every
+    parameter and both moments, x = pool_x[idx[i]], fit(net, x, ...), adam_step(net, grads, state).
+    THE NETWORK'S OWN TENSORS ARE UPDATED IN PLACE, as are the state's moments.  CUDA tensors only;
+    idx [K, batch] int64, contiguous.  Returns (losses [K] float32, status [2] int64) as device
+    tensors: status[0] the iterations applied, status[1] the indices outside [0, n_pool) (clamped).
+    stop_loss=None: never stop, nothing is read on the host, state.step advances by K.
+    stop_loss >= 0: the reference's early stop -- the first iteration whose loss is <= stop_loss is
+    still applied, every later one is a no-op and its loss stays NaN; state.step then advances by
+    status[0], READ ON THE HOST: one synchronisation per call.  check_every=c > 0 synchronises after
+    every c iterations and stops enqueuing once stopped (the same bits; the call blocks, and a
+    clamped index raises WosError after the run: the iterations are applied, with the row clamped, and
+    state.step has advanced by status[0], so network and state still agree); check_every=0 enqueues
+    everything on `stream` as in eval().  With check_every=0 a stop does not shorten the call: every
+    remaining iteration still runs its gather, packs, fit step and norm kernel, and only the Adam
+    update and the loss write are switched off -- set check_every where early stops are expected."""
+    import torch
+    p = net if isinstance(net, PackedSiren) else pack(net)
+    if not (_is_torch(pool_x) and pool_x.is_cuda):
+        raise ValueError("siren.fit_run: pool_x must be a CUDA tensor (device pointers only)")
+    dev = pool_x.device
+    if pool_x.dim() != 2 or pool_x.shape[1] != p.d_in or pool_x.shape[0] < 1:
+        raise ValueError(f"siren.fit_run: pool_x must be [n_pool, {p.d_in}], got shape {tuple(pool_x.shape)}")
+    n_pool = int(pool_x.shape[0])
+
+    def operand(name, a):
+        if not _is_torch(a) or a.device != dev:
+            raise ValueError(f"siren.fit_run: {name} must be a tensor on {dev}, like pool_x")
+        if tuple(a.shape) != (n_pool, p.d_out):
+            raise ValueError(f"siren.fit_run: {name} must have shape {(n_pool, p.d_out)}, got {tuple(a.shape)}")
+        return a.detach().to(torch.float32).contiguous()
+    xs = pool_x.detach().to(torch.float32).contiguous()
+    t = operand("pool_target", pool_target)
+    sc = None if pool_scale is None else operand("pool_scale", pool_scale)
+    if not _is_torch(idx) or idx.device != dev or idx.dtype != torch.int64 or idx.dim() != 2 or not idx.is_contiguous() \
+            or idx.shape[0] < 1 or idx.shape[1] < 1:
+        raise ValueError(f"siren.fit_run: idx must be a contiguous int64 tensor [K, batch] on {dev}")
+    tensors = p.weights + p.biases
+    if any(w.device != dev for w in tensors) or state.exp_avg.device != dev:
+        raise ValueError(f"siren.fit_run: the pool is on {dev}, the network on {tensors[0].device}, the state on "
+                         f"{state.exp_avg.device}")
+    if state.counts != [int(w.numel()) for w in tensors]:
+        raise ValueError("siren.fit_run: state was made for a network of another shape")
+    ws = 0 if workspace_bytes is None else int(workspace_bytes)
+    if ws < 0:
+        raise ValueError(f"siren.fit_run: workspace_bytes must be >= 0, got {workspace_bytes}")
+    check_every = int(check_every)
+    if check_every < 0:
+        raise ValueError(f"siren.fit_run: check_every must be >= 0, got {check_every}")
+    if stop_loss is not None and not float(stop_loss) >= 0.0:
+        raise ValueError(f"siren.fit_run: stop_loss must be None or >= 0, got {stop_loss}")
+    K, batch = int(idx.shape[0]), int(idx.shape[1])
+    losses = torch.empty(K, dtype=torch.float32, device=dev)
+    status = torch.zeros(2, dtype=torch.int64, device=dev)  # zeros: a call refused before any device work applied nothing
+    held = [xs, t, idx, losses, status, state.exp_avg, state.exp_avg_sq] + ([] if sc is None else [sc]) + tensors
+    s = _stream_of(stream, held, dev)
+    st, keep = _net_struct(p, [w.data_ptr() for w in p.weights], [b.data_ptr() for b in p.biases])
+    opt = state.params()
+    flags = _lib.WOS_PTRS_DEVICE | (0 if check_every > 0 else _lib.WOS_ASYNC)
+    rc = _lib.load().wos_siren_fit_run(C.byref(st), xs.data_ptr(), t.data_ptr(), None if sc is None else sc.data_ptr(),
+                                       n_pool, idx.data_ptr(), K, batch, state.exp_avg.data_ptr(),
+                                       state.exp_avg_sq.data_ptr(), state.step, C.byref(opt),
+                                       -1.0 if stop_loss is None else float(stop_loss), check_every, losses.data_ptr(),
+                                       status.data_ptr(), ws, flags, dev.index or 0, s)
+    del keep, held
+    if rc == -1 and check_every > 0:
+        # The blocking call refuses a clamped index only after the run: its iterations are applied to the
+        # network and the moments, so the state's step follows them before the error is raised.
+        torch.cuda.synchronize(dev)
+        state.step += int(status[0].item())
+    check(rc, "wos_siren_fit_run")
+    if stop_loss is None:
+        state.step += K
+    else:
+        if stream is not None:  # status was written on `stream`: torch's current stream must see it
+            ts = stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.ExternalStream(int(stream), device=dev)
+            torch.cuda.current_stream(dev).wait_stream(ts)
+        state.step += int(status[0].item())
+    return losses, status
 
 
 _probes = {}  # diagonal_wrap's probe of the last (shape, dtype, device)
