@@ -666,7 +666,16 @@ int wos_siren_fit(const wos_siren_net *net, const float *pts, int64_t n,
  * order over the flat order of the tensors, c = min(max_grad_norm / (norm + 1e-6f), 1); grad_norm
  * (may be NULL) then receives the unclipped norm.  max_grad_norm <= 0: no norm is computed, grad_norm
  * is not written.  grads are read, never written (torch's clip scales them in place; this does not).
- * No atomics: the same call gives the same bits.  Denormal intermediates are not part of the contract.
+ * No atomics: the same call gives the same bits.  Subnormal inputs and intermediates are kept (IEEE
+ * gradual underflow, nothing is flushed to zero).
+ * Non-finite gradients behave as clip_grad_norm_ (error_if_nonfinite off) followed by Adam.step() do;
+ * nothing is detected or refused.  c is torch.clamp(max = 1) of the quotient, which keeps a NaN: when
+ * clipping, one NaN gradient makes the norm, c, and so every parameter and both moments of every
+ * tensor NaN; one infinite gradient makes the norm inf and c = 0, so that element goes NaN and every
+ * other one takes the step of a zero gradient.  Without clipping only the element's own p, m and v
+ * are touched (NaN for a NaN gradient; m = v = inf and p = NaN for an infinite one).  In
+ * wos_siren_fit_run a NaN loss is not <= stop_loss and never stops the run: losses[i] stays NaN from
+ * there on and, when clipping, the whole network is NaN after that iteration's step.
  * Pointer rules are wos_siren_fit's: params[k], grads[k], exp_avg, exp_avg_sq and grad_norm are host
  * pointers (staged, blocking), WOS_PTRS_DEVICE, or WOS_PTRS_DEVICE | WOS_ASYNC on `stream`.
  * WOS_E_INVALID, naming the field, before any device work: a NULL pointer or entry, n_tensors out of

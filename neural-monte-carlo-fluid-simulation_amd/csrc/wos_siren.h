@@ -83,6 +83,8 @@ hipError_t launch_siren_vjp(const SirenNet& net, const float* packed, const floa
 // A row of partials is cut into segments, each with its own destination: dst[k] receives the
 // elements [end[k - 1], end[k]) of the row.
 constexpr int kReduceSegs = 12;
+static_assert(kReduceSegs >= kSirenMaxHiddenLayers + 4,
+              "the tiles' partials are cut into L + 4 segments: dWo, dbo, db_0 .. db_L, dW0");
 struct SirenReduceSegs {
   int n;
   int end[kReduceSegs];
@@ -132,7 +134,8 @@ hipError_t launch_siren_fit(const SirenNet& net, const float* packed, const floa
 // ---- optimiser step and the device-resident fit loop (wos_siren_train.hip) ----------------------
 // The tensors of one Adam step in their flat order: tensor k holds the elements [end[k - 1], end[k])
 // of exp_avg and exp_avg_sq, its parameters at p[k] and its gradients at g[k].
-constexpr int kAdamMaxTensors = 2 * kSirenMaxLayers;
+constexpr int kAdamMaxTensors = 20;
+static_assert(kAdamMaxTensors == 2 * kSirenMaxLayers, "wos_siren_fit_run steps a weight and a bias per Linear layer");
 struct AdamSegs {
   int n;
   int64_t end[kAdamMaxTensors];

@@ -20,12 +20,12 @@
 //
 // Arithmetic (f32, fixed order; DESIGN.md "Fused SIREN source"):
 //   layer 0   z = fma(W0[r][d-1], x[d-1], ... fma(W0[r][0], x[0], b0[r]))
-//   hidden    z = the MFMA's own chain over k = 0, 1, ..., H - 1 in that order, started from the
-//             bias: fma(W[r][H-1], a[H-1], ... fma(W[r][0], a[0], b[r])); the tangent columns the
-//             same chain started from 0
+//   hidden    z = the MFMA's own chain over k = 0, 1, ..., H - 1 in that order, started from 0,
+//             then the bias: fma(W[r][H-1], a[H-1], ... fma(W[r][0], a[0], 0)) + b[r]; the tangent
+//             columns the same chain without the bias
 //   both      wz = w * z, (s, c) = sincosf(wz), a = s, oc = w * c, t_k = oc * (W0[r][k] | Z_k)   (OCML; the
 //             value-only kernel drops c)
-//   output    u_i = fma chain over h = 0 .. H - 1 started from b_out[i]; J[i][k] the same from 0
+//   output    u_i = (fma chain over h = 0 .. H - 1 started from 0) + b_out[i]; J[i][k] the chain alone
 //   div       (J[0][0] + J[1][1]) + J[2][2]
 // A point's columns never meet another point's, so its outputs do not depend on n, on its place
 // in the batch or on which outputs were asked for (the value-only kernel carries one column and
@@ -136,9 +136,9 @@ __global__ __launch_bounds__(256) void siren_eval_kernel(const SirenNet net, con
     for (int item = tid; item < DO * cols; item += 256) {
       const int i = item / cols, col = item - i * cols;
       const float* wr = Wo + i * H;
-      float s = col < 32 ? bo[i] : 0.0f;
+      float s = 0.0f;
       for (int h = 0; h < H; h++) s = fmaf(wr[h], Xl[h * cols + col], s);
-      Ol[item] = s;
+      Ol[item] = col < 32 ? s + bo[i] : s;
     }
   }
   __syncthreads();

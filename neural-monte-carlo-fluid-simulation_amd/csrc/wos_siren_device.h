@@ -12,8 +12,10 @@ __device__ __forceinline__ int siren_acc_row(int reg, int lane) { return (reg & 
 
 // One hidden layer's pre-activations of this wave's row tiles r = wave + 4 i (i < RT), for the C
 // column tiles of Xl [H][C * 32] (LDS): acc[i][0] = W X_0 + b, acc[i][c] = W X_c.  Wp: the layer's
-// fragment-ordered weights (launch_siren_pack).  Row tiles past H / 32 compute a duplicate of the
-// last one, which the caller drops.  No barrier inside.
+// fragment-ordered weights (launch_siren_pack).  Every chain starts from 0 and the bias is added to
+// the finished sum, one rounding: a chain started from the bias rounds each of its H partial sums at
+// the bias's magnitude, which at small H is several times the sum's own.  Row tiles past H / 32
+// compute a duplicate of the last one, which the caller drops.  No barrier inside.
 template <int C, int RT>
 __device__ __forceinline__ void siren_hidden_gemm(const float4* __restrict__ Wp, const float* __restrict__ bias,
                                                   const float* Xl, int H, int wave, int lane, f32x16 (&acc)[RT][C]) {
@@ -25,11 +27,9 @@ __device__ __forceinline__ void siren_hidden_gemm(const float4* __restrict__ Wp,
     const int r = min(wave + 4 * i, R - 1);
     wp[i] = Wp + (size_t)r * Q * 64 + lane;
 #pragma unroll
-    for (int reg = 0; reg < 16; reg++) {
-      acc[i][0][reg] = bias[r * 32 + siren_acc_row(reg, lane)];
+    for (int reg = 0; reg < 16; reg++)
 #pragma unroll
-      for (int c = 1; c < C; c++) acc[i][c][reg] = 0.0f;
-    }
+      for (int c = 0; c < C; c++) acc[i][c][reg] = 0.0f;
   }
   const float* xb = Xl + (lane >> 5) * cols + (lane & 31);
   float4 a[RT];
@@ -54,6 +54,15 @@ __device__ __forceinline__ void siren_hidden_gemm(const float4* __restrict__ Wp,
     }
 #pragma unroll
     for (int i = 0; i < RT; i++) a[i] = an[i];
+  }
+  // the bias as one more k-step of column tile 0: A = (b[row], 0), B = (1, 0), so every element takes
+  // fma(b[row], 1, z) = z + b[row], rounded once, and the second k adds an exact zero
+  const float one = lane < 32 ? 1.0f : 0.0f;
+#pragma unroll
+  for (int i = 0; i < RT; i++) {
+    const int r = min(wave + 4 * i, R - 1);
+    const float bv = lane < 32 ? bias[r * 32 + lane] : 0.0f;
+    acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(bv, one, acc[i][0], 0, 0, 0);
   }
 }
 

@@ -119,8 +119,9 @@ __global__ __launch_bounds__(256) void siren_fit_tile_kernel(const SirenNet net,
       float r = 0.0f, ub = 0.0f;
       if (i < DO) {
         const float* wr = Wo + i * H;
-        float u = bo[i];
+        float u = 0.0f;
         for (int h = 0; h < H; h++) u = fmaf(wr[h], Xl[h * cols + j], u);
+        u = u + bo[i];
         const int64_t p = base + j;
         if (p < n) {
           const float sc = scale ? scale[p * DO + i] : 1.0f;

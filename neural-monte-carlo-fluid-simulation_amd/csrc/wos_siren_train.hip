@@ -49,7 +49,7 @@ __global__ __launch_bounds__(256) void adam_update_kernel(const AdamSegs segs, f
   if (norm) {
     const float den = norm[0] + 1e-6f;
     const float q = sc.max_norm / den;
-    c = q < 1.0f ? q : 1.0f;
+    c = q >= 1.0f ? 1.0f : q;  // torch.clamp(max = 1): a NaN norm gives a NaN coefficient, and every element goes NaN
   }
   for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
     int k = 0;

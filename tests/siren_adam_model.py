@@ -35,8 +35,9 @@ def norm32(flat):
 
 
 def clip32(norm, max_grad_norm):
+    """min(max_grad_norm / (norm + 1e-6), 1) as torch.clamp(max=1) takes it: a NaN quotient stays NaN."""
     q = F(max_grad_norm) / (F(norm) + F(1e-6))
-    return q if q < F(1.0) else F(1.0)
+    return F(1.0) if q >= F(1.0) else q
 
 
 def step32(params, grads, m, v, step, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=None):
@@ -110,11 +111,14 @@ def bound(x):
             + e_c * (x["ss"] * np.abs(x["g"]) / x["den"] + np.abs(x["delta"])))
 
 
-def problem(shapes, seed=0, state=True, top=2):
+def problem(shapes, seed=0, state=True, top=2, subnormal=False):
     """(params, grads, m, v) float32 for tensors of `shapes`: gradients over seven decades with exact
     zeros, |g| in {0} U [10^(top - 7), 10^top] -- every intermediate is exactly zero or normal, also
     after a clip to a norm of 0.1 -- and, with state, moments as some earlier steps would leave them
-    (v >= 0).  top=2 keeps the norm of 1000 elements below 1e3, top=0 that of a 3 x 256 network."""
+    (v >= 0).  top=2 keeps the norm of 1000 elements below 1e3, top=0 that of a 3 x 256 network.
+    subnormal: an eighth of the elements (eight at the least) get |g| in [1e-23, 1e-19], so that
+    (1 - beta2) g g is subnormal or underflows to zero; with state, every other one of them has v = 0
+    (v' is that product), every fourth a subnormal v and every third a subnormal m on input."""
     rng = np.random.default_rng(seed)
     total = sum(int(np.prod(s)) for s in shapes)
 
@@ -133,6 +137,16 @@ def problem(shapes, seed=0, state=True, top=2):
         v[m == 0] = 0.0
     else:
         m, v = np.zeros(total, F), np.zeros(total, F)
+    if subnormal:  # drawn last: the values above are those of subnormal=False
+        tiny = rng.choice(total, max(8, total // 8), replace=False)
+
+        def small(lo, hi, count):
+            return (10.0 ** rng.uniform(lo, hi, count) * rng.choice([-1.0, 1.0], count)).astype(F)
+        g[tiny] = small(-23, -19, tiny.size)
+        if state:
+            v[tiny[::2]] = 0.0
+            v[tiny[1::4]] = np.abs(small(-44, -39, tiny[1::4].size))
+            m[tiny[::3]] = small(-44, -39, tiny[::3].size)
 
     def split(flat):
         out, at = [], 0

@@ -29,7 +29,7 @@ def bits(a):
 # ---- 1. lane maps, exact -----------------------------------------------------------------------------
 @pytest.mark.parametrize("n_points", [1, 31, 32, 33, 65])
 @pytest.mark.parametrize("d_in", [2, 3])
-@pytest.mark.parametrize("H", [32, 64, 96, 256])
+@pytest.mark.parametrize("H", [32, 64, 96, 128, 160, 192, 224, 256])
 def test_hidden_layer_lane_maps_exact(gpu, H, d_in, n_points):
     """Integers in [-4, 4]: every sum is at most 256 * 16 + 4 = 4100 in magnitude, exact in f32, so
     a dropped or doubled k, a swapped row and column or a tangent in the wrong column all show."""
@@ -90,33 +90,67 @@ def test_divergence_is_the_ordered_trace_in_3d(gpu):
 
 
 # ---- 3. accuracy -------------------------------------------------------------------------------------
-SHAPES = [(2, 32, 1), (2, 128, 2), (2, 256, 3), (3, 256, 3), (3, 96, 2), (2, 64, 0)]
+SHAPES = [(2, 32, 1, None), (2, 128, 2, None), (2, 256, 3, None), (3, 256, 3, None), (3, 96, 2, None), (2, 64, 0, None),
+          # H / 32 = 5, 6, 7: two row tiles per wave, some waves' second one a dropped duplicate
+          (2, 160, 1, None), (3, 192, 2, None), (2, 224, 3, None),
+          # the reference's depth, and L = 8 at the smallest and the largest width
+          (2, 256, 5, None), (3, 32, 8, None), (3, 256, 8, None),
+          # d_out != d_in: value and Jacobian only
+          (2, 64, 1, 3), (3, 64, 1, 2), (2, 64, 1, 1)]
+
+
+def _id(d, H, L, d_out):
+    return f"d{d}_H{H}_L{L}" + ("" if d_out is None else f"_o{d_out}")
 
 
 @functools.lru_cache(maxsize=None)
-def _reference(d, H, L):
-    """(x, float64 model, float32 autograd path on the GPU) of one shape, computed once."""
-    net, x = sm.make_net(d, H, L), sm.points(d, 193, seed=0)
+def _reference(d, H, L, d_out=None):
+    """(x, float64 model, float32 autograd path on the GPU) of one shape, computed once; div is None
+    where d_out != d_in."""
+    net, x = sm.make_net(d, H, L, d_out), sm.points(d, 193, seed=0)
     ref = sm.model64(net, x)
-    t32 = tuple(t.cpu().numpy() for t in sm.autograd_eval(_cuda_net(d, H, L), torch.from_numpy(x).cuda()))
+    t32 = tuple(None if t is None else t.cpu().numpy()
+                for t in sm.autograd_eval(_cuda_net(d, H, L, d_out), torch.from_numpy(x).cuda()))
     return x, ref, t32
 
 
-@pytest.mark.parametrize("d,H,L", SHAPES, ids=[f"d{d}_H{H}_L{L}" for d, H, L in SHAPES])
-def test_as_accurate_as_the_float32_autograd_path(gpu, d, H, L):
-    x, ref, t32 = _reference(d, H, L)
-    got = siren.eval(_cuda_net(d, H, L), torch.from_numpy(x).cuda(), value=True, jacobian=True, divergence=True)
+@pytest.mark.parametrize("d,H,L,d_out", SHAPES, ids=[_id(*s) for s in SHAPES])
+def test_as_accurate_as_the_float32_autograd_path(gpu, d, H, L, d_out):
+    x, ref, t32 = _reference(d, H, L, d_out)
+    square = d_out is None
+    got = siren.eval(_cuda_net(d, H, L, d_out), torch.from_numpy(x).cuda(), value=True, jacobian=True, divergence=square)
+    names = ("u", "J", "div") if square else ("u", "J")
+    assert len(got) == len(names) and tuple(got[0].shape) == (193, d_out or d) and tuple(got[1].shape) == (193, d_out or d, d)
+    what = f"({d},{H},{L})" if square else f"({d},{H},{L},{d_out})"
     rec = {}
-    for name, g, t, r in zip(("u", "J", "div"), got, t32, ref):
+    for name, g, t, r in zip(names, got, t32, ref):
         rec[name] = sm.error_ratios(g.cpu().numpy(), t, r)
     out = os.environ.get("WOS_SIREN_ACCURACY_OUT")  # a measuring run keeps the figures; the suite writes nothing
     if out:
         with open(out, "a") as f:
-            f.write(json.dumps({"d": d, "hidden": H, "hidden_layers": L, "points": 193,
+            f.write(json.dumps({"d": d, "hidden": H, "hidden_layers": L, **({} if square else {"d_out": d_out}), "points": 193,
                                 **{k: {"rms_ratio": v[0], "max_ratio": v[1], "torch_rms": v[2], "torch_max": v[3]}
                                    for k, v in rec.items()}}) + "\n")
-    for name, g, t, r in zip(("u", "J", "div"), got, t32, ref):
-        sm.assert_as_accurate_as_torch(g.cpu().numpy(), t, r, f"({d},{H},{L}) {name}")
+    for name, g, t, r in zip(names, got, t32, ref):
+        sm.assert_as_accurate_as_torch(g.cpu().numpy(), t, r, f"{what} {name}")
+
+
+@pytest.mark.parametrize("d,H,L", [(2, 160, 1), (3, 224, 1)], ids=["d2_H160_L1", "d3_H224_L1"])
+def test_value_only_call_equals_the_full_call_bit_for_bit(gpu, d, H, L):
+    """The value-only kernel (one column per point) with two row tiles per wave and a dropped
+    duplicate: H / 32 = 5 and 7.  The same chains as the full call, so the same bits."""
+    net = _cuda_net(d, H, L)
+    x = torch.from_numpy(sm.points(d, 193, seed=0)).cuda()
+    full = siren.eval(net, x, value=True, jacobian=True, divergence=True)[0]
+    only = siren.eval(net, x, value=True, jacobian=False, divergence=False)
+    assert torch.is_tensor(only) and tuple(only.shape) == (193, d)
+    assert bool(torch.isfinite(only).all()) and bool(only.any())
+    assert np.array_equal(bits(only), bits(full))
+    # and that value is the network's: against float64, with torch's float32 forward as the yardstick
+    u64 = sm.model64(sm.make_net(d, H, L), x.cpu().numpy())[0]
+    with torch.no_grad():
+        u32 = net(x).cpu().numpy()
+    sm.assert_as_accurate_as_torch(only.cpu().numpy(), u32, u64, f"({d},{H},{L}) value only")
 
 
 # ---- 4. C ABI ------------------------------------------------------------------------------------------

@@ -50,7 +50,13 @@ def _dev(a):
 
 
 SHAPES = [(2, 32, 1, None), (2, 128, 2, None), (2, 256, 3, None), (3, 256, 3, None), (3, 96, 2, None), (2, 64, 0, None),
-          (3, 64, 1, 1)]
+          (3, 64, 1, 1),
+          # H / 32 = 5, 6, 7: two row tiles per wave with a dropped duplicate, and a partial second 128-tile of dW
+          (2, 160, 1, None), (3, 192, 2, None), (2, 224, 3, None),
+          # the reference's depth, and L = 8 (12 reduce segments) at the smallest and the largest width
+          (2, 256, 5, None), (3, 32, 8, None), (3, 256, 8, None),
+          # d_out != d_in
+          (2, 64, 1, 3), (3, 64, 1, 2), (2, 64, 1, 1)]
 
 
 @functools.lru_cache(maxsize=None)

@@ -42,13 +42,14 @@ def _tensors(net):
 
 
 # ---- 1. the Adam step against the float32 model, bit for bit -----------------------------------------------
-def _adam_c(params, grads, m, v, step, clip, device, stream=None, want_norm=True):
+def _adam_c(params, grads, m, v, step, clip, device, stream=None, want_norm=True, kw=KW):
     """wos_adam_step through the C ABI on copies of the numpy inputs, with host pointers or device
-    pointers (blocking; on `stream` asynchronously, then synchronised).  Returns (params, m, v, norm)."""
+    pointers (blocking; on `stream` asynchronously, then synchronised) and the hyper-parameters kw.
+    Returns (params, m, v, norm)."""
     lib = _lib.load()
     n = len(params)
     counts = (C.c_int64 * n)(*[a.size for a in params])
-    opt = _lib.AdamParams(KW["lr"], KW["betas"][0], KW["betas"][1], KW["eps"], -1.0 if clip is None else clip)
+    opt = _lib.AdamParams(kw["lr"], kw["betas"][0], kw["betas"][1], kw["eps"], -1.0 if clip is None else clip)
     if device:
         to = lambda a: torch.from_numpy(np.array(a, np.float32)).cuda()  # noqa: E731
         ptr = lambda t: t.data_ptr()  # noqa: E731
@@ -73,8 +74,10 @@ def _adam_c(params, grads, m, v, step, clip, device, stream=None, want_norm=True
     return [host(a) for a in P], host(M), host(V), host(norm)[0]
 
 
-NETS = [(2, 32, 0, 1), (3, 96, 2, 3), (2, 256, 3, 2)]
+NETS = [(2, 32, 0, 1), (3, 96, 2, 3), (2, 256, 3, 2), (3, 32, 8, 3), (2, 160, 1, 2)]
 CLIPS = [None, 0.1, 1e3]
+KW_OTHER = dict(lr=1e-3, betas=(0.5, 0.9), eps=1e-6)
+TINY = np.finfo(np.float32).tiny  # the least normal float32
 
 
 @functools.lru_cache(maxsize=None)
@@ -83,19 +86,18 @@ def _problem(net, step):
     return am.problem(shapes, seed=step + 10 * net[1], state=step > 1, top=0)
 
 
-@pytest.mark.parametrize("clip", CLIPS, ids=["noclip", "clip_active", "clip_inactive"])
-@pytest.mark.parametrize("step", [1, 2, 1000])
-@pytest.mark.parametrize("net", NETS, ids=[f"d{n[0]}_H{n[1]}_L{n[2]}_o{n[3]}" for n in NETS])
-def test_adam_step_equals_the_float32_model_bit_for_bit(gpu, net, step, clip):
+def _step_equals_the_model(net, step, clip, kw):
     params, grads, m, v = _problem(net, step)
     total = sum(a.size for a in params)
     if net == NETS[0]:
         assert total == 129 and params[-1].size == 1 and any(a.size % 4 for a in params)
+    if net == (3, 32, 8, 3):  # the most tensors a call takes, the last one ending off a multiple of 4
+        assert len(params) == 20 and total == 8675
     g = np.concatenate([a.reshape(-1) for a in grads])
     assert np.any(g == 0)
-    want = am.step32(params, grads, m, v, step, max_grad_norm=clip, **KW)
+    want = am.step32(params, grads, m, v, step, max_grad_norm=clip, **kw)
     assert np.any(want[2] == 0), "v' = 0 somewhere: den = eps"
-    got = _adam_c(params, grads, m, v, step, clip, device=True)
+    got = _adam_c(params, grads, m, v, step, clip, device=True, kw=kw)
     for k, (a, b) in enumerate(zip(got[0], want[0])):
         assert a.shape == b.shape and same(a, b), f"parameter tensor {k}: {np.sum(bits(a) != bits(b))} of {a.size} differ"
     assert same(got[1], want[1]), "exp_avg"
@@ -107,6 +109,46 @@ def test_adam_step_equals_the_float32_model_bit_for_bit(gpu, net, step, clip):
         active = am.clip32(want[3], clip) < 1
         assert active == (clip == 0.1)
     assert any(not same(a, b) for a, b in zip(got[0], params)), "the step moved the parameters"
+
+
+@pytest.mark.parametrize("clip", CLIPS, ids=["noclip", "clip_active", "clip_inactive"])
+@pytest.mark.parametrize("step", [1, 2, 1000, 40000])
+@pytest.mark.parametrize("net", NETS, ids=[f"d{n[0]}_H{n[1]}_L{n[2]}_o{n[3]}" for n in NETS])
+def test_adam_step_equals_the_float32_model_bit_for_bit(gpu, net, step, clip):
+    """Step 40000 is the reference's iteration count: sqrt(1 - beta2^step) is exactly 1 and
+    lr / (1 - beta1^step) exactly lr."""
+    if step == 40000:
+        s = am.scalars(step=step, **KW)
+        assert s["bc2"] == 1.0 and s["ss"] == KW["lr"]
+    _step_equals_the_model(net, step, clip, KW)
+
+
+@pytest.mark.parametrize("clip", [None, 0.1], ids=["noclip", "clip_active"])
+@pytest.mark.parametrize("step", [1, 40000])
+@pytest.mark.parametrize("net", [NETS[0], NETS[3]], ids=[f"d{n[0]}_H{n[1]}_L{n[2]}_o{n[3]}" for n in (NETS[0], NETS[3])])
+def test_adam_step_with_other_hyper_parameters_bit_for_bit(gpu, net, step, clip):
+    """lr = 1e-3, betas = (0.5, 0.9), eps = 1e-6: none of the five step scalars is the default's."""
+    _step_equals_the_model(net, step, clip, KW_OTHER)
+
+
+@pytest.mark.parametrize("clip", [None, 0.1], ids=["noclip", "clip_active"])
+def test_adam_step_keeps_subnormals_bit_for_bit(gpu, clip):
+    """Gradual underflow, as numpy's float32 has it: (1 - beta2) g g and v' subnormal or zero from
+    a non-zero gradient, subnormal v and m on input."""
+    net, step = NETS[0], 2
+    params, grads, m, v = am.problem(am.net_shapes(*net), seed=step + 10 * net[1], state=True, top=0, subnormal=True)
+    g = np.concatenate([a.reshape(-1) for a in grads])
+    want = am.step32(params, grads, m, v, step, max_grad_norm=clip, **KW)
+    assert np.any((v > 0) & (v < TINY)) and np.any((m != 0) & (np.abs(m) < TINY)), "subnormal moments on input"
+    assert np.any((want[2] > 0) & (want[2] < TINY)), "a subnormal v'"
+    assert np.any((want[2] == 0) & (g != 0)), "(1 - beta2) g g underflowed to zero"
+    got = _adam_c(params, grads, m, v, step, clip, device=True)
+    for k, (a, b) in enumerate(zip(got[0], want[0])):
+        assert same(a, b), f"parameter tensor {k}: {np.sum(bits(a) != bits(b))} of {a.size} differ"
+    assert same(got[1], want[1]), f"exp_avg: {np.flatnonzero(bits(got[1]) != bits(want[1]))[:8]}"
+    assert same(got[2], want[2]), f"exp_avg_sq: {np.flatnonzero(bits(got[2]) != bits(want[2]))[:8]}"
+    if clip is not None:
+        assert same(got[3], want[3])
 
 
 def test_adam_step_pointers_determinism_and_side_stream(gpu):
@@ -152,11 +194,9 @@ def test_three_consecutive_steps_from_zero_state_through_the_python_layer(gpu, c
 
 
 # ---- 2. against the reference optimiser ------------------------------------------------------------------
-@pytest.mark.parametrize("clip", CLIPS, ids=["noclip", "clip_active", "clip_inactive"])
-def test_adam_step_against_torch_adam_on_the_gpu(gpu, clip):
-    net, step = NETS[2], 7
-    params, grads, m, v = _problem(net, step)
-    got = _adam_c(params, grads, m, v, step, clip, device=True)
+def _torch_adam_on_the_gpu(params, grads, m, v, step, clip):
+    """clip_grad_norm_ and torch.optim.Adam(**KW).step() on the GPU with the state (m, v, step - 1) injected.
+    Returns (the stepped parameter tensors, the optimiser)."""
     ps = [torch.from_numpy(a.copy()).cuda().requires_grad_(True) for a in params]
     opt = torch.optim.Adam(ps, **KW)
     at = 0
@@ -170,6 +210,15 @@ def test_adam_step_against_torch_adam_on_the_gpu(gpu, clip):
     if clip is not None:
         torch.nn.utils.clip_grad_norm_(ps, clip)
     opt.step()
+    return ps, opt
+
+
+@pytest.mark.parametrize("clip", CLIPS, ids=["noclip", "clip_active", "clip_inactive"])
+def test_adam_step_against_torch_adam_on_the_gpu(gpu, clip):
+    net, step = NETS[2], 7
+    params, grads, m, v = _problem(net, step)
+    got = _adam_c(params, grads, m, v, step, clip, device=True)
+    ps, opt = _torch_adam_on_the_gpu(params, grads, m, v, step, clip)
     d = opt.defaults
     print(f"torch.optim.Adam on the GPU: foreach={d.get('foreach')} fused={d.get('fused')} capturable={d.get('capturable')} "
           f"(foreach None: torch's default, the foreach implementation on CUDA tensors)")
@@ -181,6 +230,53 @@ def test_adam_step_against_torch_adam_on_the_gpu(gpu, clip):
     print(f"clip {clip}: bit-equal {np.mean(have == want):.4f}; ours / B {np.max(np.abs(have - ref[4]['p']) / B):.3f}, "
           f"torch / B {np.max(np.abs(want - ref[4]['p']) / B):.3f}, difference / 2B {np.max(diff / (2 * B)):.3f}")
     assert np.all(diff <= 2 * B)
+
+
+def _flat(arrays):
+    return np.concatenate([(a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)).reshape(-1) for a in arrays])
+
+
+def _same_nans_and_bits(a, b, what):
+    """NaN in the same places, and every other element -- an infinity included -- the same bits."""
+    a, b = _flat([a]), _flat([b])
+    assert np.array_equal(np.isnan(a), np.isnan(b)), f"{what}: NaN differs at {np.flatnonzero(np.isnan(a) != np.isnan(b))[:8]}"
+    ok = ~np.isnan(a)
+    assert np.array_equal(bits(a)[ok], bits(b)[ok]), f"{what}: {np.sum(bits(a)[ok] != bits(b)[ok])} finite elements differ"
+
+
+@pytest.mark.parametrize("clip", [None, 0.1], ids=["noclip", "clip"])
+@pytest.mark.parametrize("bad", [float("nan"), float("inf")], ids=["nan", "inf"])
+def test_adam_step_on_a_non_finite_gradient(gpu, bad, clip):
+    """clip_grad_norm_ + Adam.step() on one NaN or +inf gradient element: with clipping a NaN norm
+    gives a NaN coefficient and every element goes NaN; an infinite norm gives a coefficient of 0,
+    NaN at the element and a zero gradient elsewhere; without clipping only the element is touched.
+    The device against the float32 model -- NaN in the same places, every other bit equal -- and
+    against torch's Adam on the GPU, NaN in the same places."""
+    net, step = NETS[1], 2
+    params, grads, m, v = _problem(net, step)
+    grads = [a.copy() for a in grads]
+    grads[1][5, 7] = bad  # the second tensor, past a tensor boundary
+    at = params[0].size + 5 * grads[1].shape[1] + 7
+    with np.errstate(invalid="ignore", over="ignore"):
+        want = am.step32(params, grads, m, v, step, max_grad_norm=clip, **KW)
+    got = _adam_c(params, grads, m, v, step, clip, device=True)
+    _same_nans_and_bits(_flat(got[0]), _flat(want[0]), "parameters")
+    _same_nans_and_bits(got[1], want[1], "exp_avg")
+    _same_nans_and_bits(got[2], want[2], "exp_avg_sq")
+    if clip is not None:
+        _same_nans_and_bits(got[3], want[3], "grad_norm")
+    ps, opt = _torch_adam_on_the_gpu(params, grads, m, v, step, clip)
+    for what, a, b in (("parameters", _flat(got[0]), _flat(ps)), ("exp_avg", got[1], _flat([opt.state[t]["exp_avg"] for t in ps])),
+                       ("exp_avg_sq", got[2], _flat([opt.state[t]["exp_avg_sq"] for t in ps]))):
+        assert np.array_equal(np.isnan(a), np.isnan(b)), f"{what} against torch: NaN differs at {np.flatnonzero(np.isnan(a) != np.isnan(b))[:8]}"
+    nan_p = np.isnan(_flat(got[0]))
+    if clip is not None and np.isnan(bad):
+        assert nan_p.all() and np.isnan(got[1]).all() and np.isnan(got[2]).all() and np.isnan(got[3])
+    else:
+        only = np.zeros(nan_p.size, bool)
+        only[at] = True
+        assert np.array_equal(nan_p, only) and np.array_equal(~np.isfinite(got[1]), only)
+        assert np.array_equal(~np.isfinite(got[2]), only)
 
 
 # ---- 3. run = separate calls, bit for bit ------------------------------------------------------------------
@@ -223,7 +319,9 @@ def _same_run(net_a, state_a, net_b, state_b, what):
 
 
 RUNS = [((2, 64, 1, 2), True, b, 0.1) for b in (1, 32, 65, 545)] + [((3, 96, 2, 3), False, b, None) for b in (1, 32, 65, 545)] + [
-    ((2, 256, 3, 2), True, 65, None)]
+    ((2, 256, 3, 2), True, 65, None),
+    ((3, 32, 8, 3), True, 65, 0.1),      # L = 8: 12 reduce segments in the fit step, 20 tensors in the Adam step
+    ((2, 160, 1, 2), False, 65, None)]   # H / 32 = 5: a dropped row tile and a partial second 128-tile of dW
 
 
 @pytest.mark.parametrize("shape,with_scale,batch,clip", RUNS,
@@ -317,6 +415,62 @@ def test_stop_loss_minus_one_never_stops_through_the_c_abi(gpu):
     state_b.step = K
     assert status.tolist() == [K, 0] and same(losses, want)
     _same_run(net_a, state_a, net_b, state_b, "blocking, check_every 2, stop_loss -1")
+
+
+# ---- 4b. a NaN target ------------------------------------------------------------------------------------------
+def _nan_row_case(idx):
+    """A pool whose target row `row` is NaN, with idx[2, 0] = row and the row drawn nowhere before
+    iteration 2.  Returns (clean pool, poisoned pool, idx)."""
+    pool = _pool(2, 2, True)
+    early = set(idx[:2].reshape(-1).tolist())
+    row = next(r for r in range(1, N_POOL - 1) if r not in early)
+    idx = idx.clone()
+    idx[2, 0] = row
+    target = pool[1].clone()
+    target[row] = float("nan")
+    return pool, (pool[0], target, pool[2]), idx.contiguous()
+
+
+def test_fit_run_with_a_nan_target_poisons_the_network_as_the_separate_calls_do(gpu):
+    """Clipping on: the NaN loss of iteration 2 gives a NaN norm, a NaN clip coefficient and a network
+    that is NaN throughout, as clip_grad_norm_ + Adam.step() leave it -- not a half-poisoned one."""
+    shape, batch, clip = (2, 64, 1, 2), 32, 0.1
+    clean_pool, pool, idx = _nan_row_case(_idx(batch))
+    net_c, net_a, net_b = _cuda_net(*shape), _cuda_net(*shape), _cuda_net(*shape)
+    state_c, state_a, state_b = [siren.AdamState(n, max_grad_norm=clip, **KW) for n in (net_c, net_a, net_b)]
+    clean, status = siren.fit_run(net_c, state_c, *clean_pool, idx)
+    assert status.tolist() == [K, 0] and bool(torch.isfinite(clean).all())
+    want = _loop(net_a, state_a, pool, idx)
+    losses, status = siren.fit_run(net_b, state_b, *pool, idx)
+    assert status.tolist() == [K, 0] and state_b.step == K
+    assert bool(torch.isfinite(losses[:2]).all()) and same(losses[:2], clean[:2]), losses.tolist()
+    assert bool(torch.isnan(losses[2:]).all()), losses.tolist()
+    for k, t in enumerate(_tensors(net_b)):
+        assert bool(torch.isnan(t).all()), f"parameter tensor {k}: {int((~torch.isnan(t)).sum())} of {t.numel()} are not NaN"
+    assert bool(torch.isnan(state_b.exp_avg).all()) and bool(torch.isnan(state_b.exp_avg_sq).all())
+    _same_nans_and_bits(losses, want, "losses")
+    for k, (a, b) in enumerate(zip(_tensors(net_b), _tensors(net_a))):
+        _same_nans_and_bits(a, b, f"parameter tensor {k}")
+    _same_nans_and_bits(state_b.exp_avg, state_a.exp_avg, "exp_avg")
+    _same_nans_and_bits(state_b.exp_avg_sq, state_a.exp_avg_sq, "exp_avg_sq")
+
+
+@pytest.mark.parametrize("check_every", [0, 1])
+def test_a_nan_loss_never_stops_the_run(gpu, check_every):
+    """stop_loss one ulp below the clean run's second loss: not met by iterations 0 and 1, and a NaN
+    loss is not <= stop_loss, as with the Python loop's `loss < threshold`."""
+    shape, batch, clip = (2, 64, 1, 2), 32, 0.1
+    clean_pool, pool, idx = _nan_row_case(_idx(batch)[:1].repeat(K, 1))  # the same batch: the clean loss falls
+    net_c, state_c = _cuda_net(*shape), siren.AdamState(_cuda_net(*shape), max_grad_norm=clip, **KW)
+    clean, _ = siren.fit_run(net_c, state_c, *clean_pool, idx)
+    assert float(clean[0]) > float(clean[1]), f"the test's premise, a falling loss: {clean.tolist()}"
+    stop = float(np.nextafter(np.float32(clean[1].item()), np.float32(0)))
+    assert 0 <= stop < float(clean[1])
+    net, state = _cuda_net(*shape), siren.AdamState(_cuda_net(*shape), max_grad_norm=clip, **KW)
+    losses, status = siren.fit_run(net, state, *pool, idx, stop_loss=stop, check_every=check_every)
+    assert status.tolist() == [K, 0] and state.step == K
+    assert same(losses[:2], clean[:2]) and bool(torch.isnan(losses[2:]).all()), losses.tolist()
+    assert all(bool(torch.isnan(t).all()) for t in _tensors(net))
 
 
 # ---- 5. a bad index ------------------------------------------------------------------------------------------

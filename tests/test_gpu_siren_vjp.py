@@ -43,7 +43,7 @@ def _cuda_net(d, H, L, d_out=None):
 # ---- 1. lane maps, exact -----------------------------------------------------------------------------
 @pytest.mark.parametrize("n_points", [1, 31, 32, 33, 65])
 @pytest.mark.parametrize("d_in", [2, 3])
-@pytest.mark.parametrize("H", [32, 64, 96, 256])
+@pytest.mark.parametrize("H", [32, 64, 96, 128, 160, 192, 224, 256])
 def test_backward_layer_lane_maps_exact(gpu, H, d_in, n_points):
     """Integers of magnitude <= 3: dX sums at most 256 * 9, dW at most 65 * 4 * 9 terms' worth, all exact
     in f32, so a dropped or doubled k, an untransposed W, a tangent in the wrong column or a padding
@@ -65,7 +65,13 @@ def test_backward_layer_lane_maps_exact(gpu, H, d_in, n_points):
 
 # ---- 2. accuracy against float64 -----------------------------------------------------------------------
 SHAPES = [(2, 32, 1, None), (2, 128, 2, None), (2, 256, 3, None), (3, 256, 3, None), (3, 96, 2, None), (2, 64, 0, None),
-          (3, 64, 1, 1)]
+          (3, 64, 1, 1),
+          # H / 32 = 5, 6, 7: two row tiles per wave with a dropped duplicate, and a partial second 128-tile of dW
+          (2, 160, 1, None), (3, 192, 2, None), (2, 224, 3, None),
+          # the reference's depth, and L = 8 (12 reduce segments) at the smallest and the largest width
+          (2, 256, 5, None), (3, 32, 8, None), (3, 256, 8, None),
+          # d_out != d_in
+          (2, 64, 1, 3), (3, 64, 1, 2), (2, 64, 1, 1)]
 
 
 @functools.lru_cache(maxsize=None)

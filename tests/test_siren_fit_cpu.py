@@ -130,7 +130,8 @@ def test_python_layer_names_what_it_refuses():
 
 
 # ---- the model ---------------------------------------------------------------------------------------
-MODEL_SHAPES = [(2, 32, 1, None), (3, 64, 2, None), (2, 64, 0, None), (3, 32, 1, 1)]
+MODEL_SHAPES = [(2, 32, 1, None), (3, 64, 2, None), (2, 64, 0, None), (3, 32, 1, 1),
+                (3, 32, 8, 3), (2, 160, 1, 2), (2, 64, 1, 3)]  # the deepest net, H / 32 = 5, and d_out > d_in
 
 
 @pytest.mark.parametrize("with_scale", [False, True], ids=["plain", "scale"])

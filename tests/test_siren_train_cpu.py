@@ -239,6 +239,50 @@ def test_float32_model_against_torch_float32_within_two_bounds(step, clip):
         assert abs(float(norm) - ref[3]) <= (len(diff) / 2 + 4) * am.U * ref[3]
 
 
+def _non_finite_problem(bad):
+    """am.problem(SHAPES, step 2) with one gradient element, in the middle tensor, set to `bad`.
+    Returns (params, grads, m, v, the element's flat index)."""
+    params, grads, m, v = am.problem(SHAPES, seed=2, state=True)
+    grads[1][5] = bad
+    return params, grads, m, v, params[0].size + 5
+
+
+@pytest.mark.parametrize("clip", [None, 0.1], ids=["noclip", "clip"])
+@pytest.mark.parametrize("bad", [float("nan"), float("inf")], ids=["nan", "inf"])
+def test_float32_model_follows_torch_float32_on_a_non_finite_gradient(bad, clip):
+    """clip_grad_norm_ clamps its coefficient with torch.clamp(max=1), which keeps a NaN: with a NaN
+    gradient and clipping on, every parameter and both moments go NaN.  An infinite gradient gives a
+    norm of inf and a coefficient of 0: NaN at that element, a zero gradient everywhere else.
+    Without clipping only the element itself is touched."""
+    kw = dict(lr=1e-4, betas=(0.9, 0.999), eps=1e-8)
+    params, grads, m, v, at = _non_finite_problem(bad)
+    with np.errstate(invalid="ignore", over="ignore"):
+        p32, m32, v32, norm = am.step32(params, grads, m, v, 2, max_grad_norm=clip, **kw)
+        ref = am.step64(params, grads, m, v, 2, max_grad_norm=clip, **kw)
+        B = am.bound(ref[4])
+    want = _torch_step(np.float32, params, grads, m, v, 2, clip, **kw)
+    total = m.size
+    for name, a, b in (("parameters", _flat(p32), _flat(want[0])), ("exp_avg", m32, want[1]), ("exp_avg_sq", v32, want[2])):
+        assert np.array_equal(np.isnan(a), np.isnan(b)), f"{name}: NaN at {np.flatnonzero(np.isnan(a) != np.isnan(b))[:8]}"
+        assert np.array_equal(np.isinf(a), np.isinf(b)) and np.array_equal(a[np.isinf(a)], b[np.isinf(b)]), name
+    ok = np.isfinite(_flat(p32))
+    diff = np.abs(_flat(p32).astype(np.float64) - _flat(want[0]).astype(np.float64))
+    assert np.all(B[ok] > 0) and np.all(diff[ok] <= 2 * B[ok])
+    # what reading torch says must happen
+    nan_p = np.isnan(_flat(p32))
+    if clip is not None and np.isnan(bad):
+        assert nan_p.all() and np.isnan(m32).all() and np.isnan(v32).all() and np.isnan(norm)
+    else:
+        only = np.zeros(total, bool)
+        only[at] = True
+        assert np.array_equal(nan_p, only) and np.array_equal(~np.isfinite(m32), only) and np.array_equal(~np.isfinite(v32), only)
+        if clip is not None:  # inf: the coefficient is 0, the step is that of a zero gradient
+            assert np.isinf(norm) and am.clip32(norm, clip) == 0
+            with np.errstate(invalid="ignore"):
+                zero = am.step32(params, [np.zeros_like(g) for g in grads], m, v, 2, **kw)
+            assert np.array_equal(_flat(zero[0])[~only], _flat(p32)[~only])
+
+
 def test_norm32_is_the_chain_then_pairwise_order():
     """Against a literal scalar restatement of the kernel's loops, at a size below, at and above 256."""
     rng = np.random.default_rng(3)

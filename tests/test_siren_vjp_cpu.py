@@ -22,7 +22,8 @@ HEADER = os.path.join(REPO, "include", "wos.h")
 
 
 # ---- the model ---------------------------------------------------------------------------------------
-MODEL_SHAPES = [(2, 32, 1, None), (3, 64, 2, None), (2, 64, 0, None), (3, 32, 1, 1)]
+MODEL_SHAPES = [(2, 32, 1, None), (3, 64, 2, None), (2, 64, 0, None), (3, 32, 1, 1),
+                (3, 32, 8, 3), (2, 160, 1, 2), (2, 64, 1, 3)]  # the deepest net, H / 32 = 5, and d_out > d_in
 
 
 @pytest.mark.parametrize("which", ["u", "J", "div", "all"])
