@@ -145,6 +145,33 @@ int wos_release_caches(int32_t device);
  * clamped to [2^16, 2^30].  Returns the previous value.  Results do not depend on it. */
 int64_t wos_set_max_batch_tasks(int64_t max_tasks);
 
+/* Length hints (additive, ABI 10).  A solve's walks do not depend on the source, so a time-stepper
+ * that solves the same points on the same boundary every step repeats them step for step.  A plain
+ * 2D one-channel solve that runs in one batch lists its walks of >= hint_min steps in the per-device
+ * workspace; the next such solve with the same walks (same geometry content, absorption, point count
+ * and coordinates, index_base / index_stride, seed and walk-relevant solver parameters; a fresh
+ * wos_scene on the same geometry qualifies) starts those of >= express_min steps first, longest
+ * first, express_per_wave to a wave that takes nothing else until they have ended, at issue priority
+ * `priority` (0..3).  Scheduling only: results are bit-identical with and without, a stale or foreign
+ * list is never used, and the first solve of a point set runs as it always did.  capacity: entries
+ * of the list (at most 65536; walks beyond it are counted, not listed, and a list that overflowed
+ * is not used at all: where that many walks are long they are the bulk, not the tail).  The express
+ * list holds at most express_per_wave walks per workgroup of the walk kernel's grid, the longest.
+ * Hinted are the plain solves (wos_solve, wos_solve_var) of 2D one-channel scenes whose Neumann term
+ * is provably inert (watertight, single-sided, no Neumann image; not WOS_SCHED_FULL_NEUMANN); robust_float,
+ * several channels, 3D, solves that split into batches, the tape and wos_bvc run as they always did.
+ * A negative argument selects that value's default.  Takes effect with the next solve.  WOS_SCHED_NO_LENGTH_HINTS switches both the
+ * listing and the use off for a solve; wos_release_caches drops the list.
+ * wos_length_hint_stats: of the last solve on `device`, after waiting for it: out[0] express walks
+ * started, out[1] walks the list had no room for, out[2] walks listed, out[3] entries of the express
+ * list it ran with (all 0 if that solve ran without hints).
+ * wos_selftest_hint_key: host only.  1 if two hint keys that differ in field `field` alone compare
+ * unequal, 0 if they compare equal, -1 past the last field. */
+void wos_set_length_hints(int32_t hint_min, int32_t express_min, int32_t express_per_wave, int32_t capacity,
+                          int32_t priority);
+int wos_length_hint_stats(int32_t device, int64_t *out);
+int32_t wos_selftest_hint_key(int32_t field);
+
 typedef struct wos_scene_info {
     int32_t dim, n_prims, n_silhouettes, n_dprims, device;
     float bbox_min[3], bbox_max[3];
@@ -223,6 +250,8 @@ typedef struct wos_solver_params {
 #define WOS_SCHED_NO_TAIL_SPREAD 0x10u /* no hand-over of walks to idle sibling waves once the queue is dry */
 #define WOS_SCHED_NO_GRID_SPREAD 0x20u /* reserved, no effect: grid-wide hand-over was measured slower than the
                                           in-workgroup one and removed (the bit stays defined so callers still build) */
+#define WOS_SCHED_NO_LENGTH_HINTS (0x40u) /* neither list this solve's long walks nor start known-long walks first
+                                           (wos_set_length_hints) */
 
 void wos_default_params(wos_solver_params *p);
 

@@ -126,6 +126,26 @@ struct TaskWs {
 };
 constexpr int kSideWs = 2;
 
+// Everything that decides a solve's walks (not its values): the length hints a solve leaves are used
+// by the next one only if the keys are equal field for field (Length hints).  The point
+// coordinates are guarded on the device (the point-setup checksum).
+struct HintKey {
+  int32_t dim = 0, wpp = 0, n_walks = 0, n_anti = 0;
+  int64_t n = 0, index_base = 0, index_stride = 0;
+  uint64_t seed = 0, geometry = 0;  // Geom::content_id
+  int32_t max_walk_length = 0, steps_before_tikhonov = 0, steps_before_maximal_spheres = 0;
+  int32_t use_cosine = 0, ignore_dirichlet = 0, ignore_neumann = 0, ignore_source = 0, force_estimate = 0;
+  int32_t watertight = 0, double_sided = 0;
+  float epsilon_shell = 0, min_star_radius = 0, silhouette_precision = 0, rr_threshold = 0, absorption = 0;
+  bool operator==(const HintKey& o) const;
+};
+// the tunables of the length hints (wos_set_length_hints)
+struct HintTuning {
+  int32_t hint_min, express_min, express_per_wave, capacity, priority;
+};
+extern std::mutex g_hint_mu;
+extern HintTuning g_hint_tuning;
+
 struct DevCtx {
   std::mutex mu;  // one solve at a time per device (the workspace is shared)
   bool ready = false;
@@ -154,6 +174,14 @@ struct DevCtx {
   float* d_rejtab = nullptr;   // rejection bound table, 2D then 3D (DevParams::rej_tab)
   int stat_waiters = 0;        // wos_solve_stats calls waiting on a slot's event without the lock
   std::condition_variable no_waiters;
+  // length hints: the device lists behind d_counters' control block, and what the list in it belongs to
+  void* d_hint_list = nullptr;        // uint2 [kHintListMax]
+  uint32_t* d_hint_express = nullptr; // [kHintListMax]
+  uint32_t* d_hint_bits = nullptr;    // one bit per task of the workspace
+  int64_t hint_bits_tasks = 0;
+  HintKey hint_key;
+  bool hint_key_valid = false;
+  bool hint_last = false;             // the last solve on the workspace ran with hints (collecting at least)
   TaskWs side[kSideWs];        // boundary value caching's side-stream workspaces (lazy)
   hipStream_t bvc_dir = nullptr;  // boundary value caching: the Dirichlet samples' solve (lazy)
   hipEvent_t bvc_dir_done = nullptr;
@@ -182,6 +210,8 @@ wos::DevTasks task_view_in(float* d_tasks, int32_t* d_pstate, int64_t pstate_cap
 wos::DevTasks task_view(DevCtx& c, int dim, int64_t T, int32_t wpp, int channels = 1);
 // state_k = A_k * state_0 + C_k for the PCG32 LCG (multiplier kPcgMult, increment kPcgInc)
 int ensure_jump(DevCtx& c, int k_needed);
+// the length hints' lists for a batch of `tasks` tasks; *hc: the control block
+int ensure_hints(DevCtx& c, int64_t tasks, uint32_t** hc);
 // the rejection bound tables [2D | 3D] of DevParams::rej_tab (host, computed once per process)
 const std::vector<float>& rejection_tables();
 
@@ -228,6 +258,7 @@ struct Geom {
   int device = 0;
   int dim = 2, double_sided = 0;
   std::vector<float> v, dv;  // the key: exactly the inputs of prepare_scene
+  uint64_t content_id = 0;   // a hash of the key (length hints: the geometry's identity across Geom objects)
   std::vector<int32_t> ix, dix;
   wos::HostScene host;
   float *d_prim = nullptr, *d_paux = nullptr, *d_sil = nullptr, *d_dprim = nullptr, *d_dpaux = nullptr;
@@ -337,8 +368,9 @@ Batches batches(int64_t n, int64_t wpp);
 // The head of batch `k`, nb points at d_pts: one launch zeroes the counters (first batch: all of
 // them; later ones: the queues) and the bucket histogram -- instead of two or three memset
 // dispatches; after_zero (or null) is recorded; then the point setup and the LPT order.
+// cksum (or null): the point setup adds the points' checksum there (length hints).
 int batch_head(DevCtx& c, int dim, const SolvePlan& P, int64_t k, const float* d_pts, int64_t nb,
-               const wos::DevTasks& tk, hipEvent_t after_zero, hipStream_t st);
+               const wos::DevTasks& tk, hipEvent_t after_zero, hipStream_t st, unsigned long long* cksum = nullptr);
 // One fold per channel of the batch of nb points at b0 of n: only total and first ([C][T] in tk) differ,
 // code / bdir / sdir are the walks'.  Outputs channel-major; n_est and steps from channel 0 alone.
 int fold_channels(int dim, const wos::DevParams& dp, const wos::DevTasks& tk, int C, int64_t nb, int64_t b0,

@@ -20,6 +20,23 @@ static_assert(WOS_BATCH_LOG2 <= 30, "task indices carry a flag in bit 31 (wos_wa
 constexpr int64_t kDefaultBatchTasks = (int64_t)1 << WOS_BATCH_LOG2;
 std::atomic<int64_t> g_max_batch_tasks{kDefaultBatchTasks};
 
+// Length hints (Length hints): walks of >= hint_min steps are listed, those of >=
+// express_min steps start first in the next solve, express_per_wave to a wave at issue priority `priority`.
+constexpr HintTuning kDefaultHintTuning = {24, 40, 4, (int32_t)wos::kHintListMax, 0};
+std::mutex g_hint_mu;
+HintTuning g_hint_tuning = kDefaultHintTuning;
+
+bool HintKey::operator==(const HintKey& o) const {
+  return dim == o.dim && wpp == o.wpp && n_walks == o.n_walks && n_anti == o.n_anti && n == o.n &&
+         index_base == o.index_base && index_stride == o.index_stride && seed == o.seed && geometry == o.geometry &&
+         max_walk_length == o.max_walk_length && steps_before_tikhonov == o.steps_before_tikhonov &&
+         steps_before_maximal_spheres == o.steps_before_maximal_spheres && use_cosine == o.use_cosine &&
+         ignore_dirichlet == o.ignore_dirichlet && ignore_neumann == o.ignore_neumann &&
+         ignore_source == o.ignore_source && force_estimate == o.force_estimate && watertight == o.watertight &&
+         double_sided == o.double_sided && epsilon_shell == o.epsilon_shell && min_star_radius == o.min_star_radius &&
+         silhouette_precision == o.silhouette_precision && rr_threshold == o.rr_threshold && absorption == o.absorption;
+}
+
 static void ctx_free(DevCtx& c) {
   hipFree(c.d_pts); hipFree(c.d_p); hipFree(c.d_g); hipFree(c.d_nest); hipFree(c.d_steps);
   hipFree(c.d_pvar); hipFree(c.d_gvar);
@@ -27,6 +44,11 @@ static void ctx_free(DevCtx& c) {
   c.ws_var_points = 0;
   hipFree(c.d_jump); hipFree(c.d_tasks); hipFree(c.d_pstate); hipFree(c.d_counters); hipFree(c.d_rejtab);
   c.d_rejtab = nullptr;
+  hipFree(c.d_hint_list); hipFree(c.d_hint_express); hipFree(c.d_hint_bits);
+  c.d_hint_list = nullptr; c.d_hint_express = nullptr; c.d_hint_bits = nullptr;
+  c.hint_bits_tasks = 0;
+  c.hint_key_valid = false;
+  c.hint_last = false;
   for (StatSlot& q : c.slot) {
     if (q.ev0) hipEventDestroy(q.ev0);
     if (q.ev1) hipEventDestroy(q.ev1);
@@ -80,6 +102,7 @@ int ctx_ready(DevCtx& c, int device) {
   }
   HIP_TRY(hipDeviceGetAttribute(&c.num_cus, hipDeviceAttributeMultiprocessorCount, device));
   HIP_TRY(hipMalloc((void**)&c.d_counters, wos::kMainCounterSlots * sizeof(unsigned long long)));
+  HIP_TRY(hipMemset(c.d_counters, 0, wos::kMainCounterSlots * sizeof(unsigned long long)));
   for (StatSlot& q : c.slot) {
     HIP_TRY(hipHostMalloc((void**)&q.h_cnt, wos::kNumCounters * sizeof(unsigned long long)));
     HIP_TRY(hipEventCreate(&q.ev0));
@@ -182,6 +205,31 @@ wos::DevTasks task_view_in(float* d_tasks, int32_t* d_pstate, int64_t pstate_cap
 
 wos::DevTasks task_view(DevCtx& c, int dim, int64_t T, int32_t wpp, int channels) {
   return task_view_in(c.d_tasks, c.d_pstate, c.pstate_cap, dim, T, wpp, channels);
+}
+
+int ensure_hints(DevCtx& c, int64_t tasks, uint32_t** hc_out) {
+  uint32_t* const hc = (uint32_t*)(c.d_counters + wos::kNumCounterSlots);
+  *hc_out = hc;
+  if (c.d_hint_list && tasks <= c.hint_bits_tasks) return WOS_OK;
+  // (re)built from nothing: the lists, a zeroed bitmap and control block, no key.  Blocking, like
+  // every growth of the workspace (hipFree waits for the device).
+  hipFree(c.d_hint_list); hipFree(c.d_hint_express); hipFree(c.d_hint_bits);
+  c.d_hint_list = nullptr; c.d_hint_express = nullptr; c.d_hint_bits = nullptr;
+  c.hint_bits_tasks = 0;
+  c.hint_key_valid = false;
+  const size_t words = (size_t)((tasks + 31) / 32);
+  HIP_TRY(hipMalloc(&c.d_hint_list, (size_t)wos::kHintListMax * 2 * sizeof(uint32_t)));
+  HIP_TRY(hipMalloc((void**)&c.d_hint_express, (size_t)wos::kHintListMax * sizeof(uint32_t)));
+  HIP_TRY(hipMalloc((void**)&c.d_hint_bits, words * sizeof(uint32_t)));
+  HIP_TRY(hipMemset(c.d_hint_bits, 0, words * sizeof(uint32_t)));
+  uint32_t h[wos::H_WORDS] = {};
+  const auto put = [&](int at, const void* p) { std::memcpy(h + at, &p, sizeof(p)); };
+  put(wos::H_LIST, c.d_hint_list);
+  put(wos::H_EXPRESS, c.d_hint_express);
+  put(wos::H_BITS, c.d_hint_bits);
+  HIP_TRY(hipMemcpy(hc, h, sizeof(h), hipMemcpyHostToDevice));
+  c.hint_bits_tasks = tasks;
+  return WOS_OK;
 }
 
 int ensure_jump(DevCtx& c, int k_needed) {
@@ -341,6 +389,53 @@ int64_t wos_set_max_batch_tasks(int64_t max_tasks) {
   const int64_t v = max_tasks <= 0 ? kDefaultBatchTasks
                                    : std::min<int64_t>(std::max<int64_t>(max_tasks, (int64_t)1 << 16), (int64_t)1 << 30);
   return g_max_batch_tasks.exchange(v);
+}
+
+void wos_set_length_hints(int32_t hint_min, int32_t express_min, int32_t express_per_wave, int32_t capacity,
+                          int32_t priority) {
+  std::lock_guard<std::mutex> lk(g_hint_mu);
+  const HintTuning& d = kDefaultHintTuning;
+  HintTuning& t = g_hint_tuning;
+  t.hint_min = hint_min < 0 ? d.hint_min : std::min(std::max(hint_min, 1), (int32_t)wos::kHintMinMask);
+  t.express_min = express_min < 0 ? d.express_min : std::max(express_min, 1);
+  t.express_per_wave = express_per_wave < 0 ? d.express_per_wave : std::min(std::max(express_per_wave, 1), 64);
+  t.capacity = capacity < 0 ? d.capacity : std::min(std::max(capacity, 1), (int32_t)wos::kHintListMax);
+  t.priority = priority < 0 ? d.priority : std::min(priority, 3);
+}
+
+int32_t wos_selftest_hint_key(int32_t field) {
+  HintKey a, b;
+  int k = 0;
+  bool hit = false;
+  const auto bump = [&](auto& v) {
+    if (k++ == field) { v = v + 1; hit = true; }
+  };
+  bump(b.dim); bump(b.wpp); bump(b.n_walks); bump(b.n_anti); bump(b.n); bump(b.index_base); bump(b.index_stride);
+  bump(b.seed); bump(b.geometry); bump(b.max_walk_length); bump(b.steps_before_tikhonov);
+  bump(b.steps_before_maximal_spheres); bump(b.use_cosine); bump(b.ignore_dirichlet); bump(b.ignore_neumann);
+  bump(b.ignore_source); bump(b.force_estimate); bump(b.watertight); bump(b.double_sided); bump(b.epsilon_shell);
+  bump(b.min_star_radius); bump(b.silhouette_precision); bump(b.rr_threshold); bump(b.absorption);
+  static_assert(sizeof(HintKey) == 4 * 4 + 3 * 8 + 2 * 8 + 10 * 4 + 5 * 4 + 4, "a new HintKey field: compare it, bump it here");
+  if (field < 0 || !hit) return -1;
+  return a == b ? 0 : 1;
+}
+
+int wos_length_hint_stats(int32_t device, int64_t* out) {
+  if (!out) return fail(WOS_E_INVALID, "wos_length_hint_stats: null output");
+  for (int k = 0; k < 4; k++) out[k] = 0;
+  if (device < 0 || device >= kMaxDevices) return fail(WOS_E_INVALID, "wos_length_hint_stats: no such device");
+  DevCtx& c = g_ctx[device];
+  std::lock_guard<std::mutex> lk(c.mu);
+  if (!c.ready || !c.hint_last || !c.d_hint_list) return WOS_OK;
+  HIP_TRY(hipSetDevice(device));
+  if (c.inflight) HIP_TRY(hipEventSynchronize(c.done));
+  uint32_t h[wos::H_WORDS];
+  HIP_TRY(hipMemcpy(h, c.d_counters + wos::kNumCounterSlots, sizeof(h), hipMemcpyDeviceToHost));
+  out[0] = h[wos::H_CLAIMED];
+  out[1] = h[wos::H_NLIST] > h[wos::H_CAP] ? h[wos::H_NLIST] - h[wos::H_CAP] : 0;
+  out[2] = std::min(h[wos::H_NLIST], h[wos::H_CAP]);
+  out[3] = h[wos::H_NEXPRESS];
+  return WOS_OK;
 }
 
 int wos_release_caches(int32_t device) {

@@ -55,6 +55,21 @@ static int geom_get(const wos_scene_desc* d, int device, std::shared_ptr<Geom>& 
   if (d->n_prims > 0) g->ix.assign(d->prims, d->prims + (size_t)d->n_prims * dim);
   if (d->n_dvertices > 0) g->dv.assign(d->dvertices, d->dvertices + (size_t)d->n_dvertices * dim);
   if (d->n_dprims > 0) g->dix.assign(d->dprims, d->dprims + (size_t)d->n_dprims * dim);
+  {
+    // FNV-1a over the key
+    uint64_t h = 0xCBF29CE484222325ull;
+    const auto mix = [&](const void* p, size_t bytes) {
+      const unsigned char* b = (const unsigned char*)p;
+      for (size_t i = 0; i < bytes; i++) h = (h ^ b[i]) * 0x100000001B3ull;
+    };
+    const int32_t head[2] = {dim, d->is_double_sided};
+    mix(head, sizeof(head));
+    mix(g->v.data(), g->v.size() * sizeof(float));
+    mix(g->ix.data(), g->ix.size() * sizeof(int32_t));
+    mix(g->dv.data(), g->dv.size() * sizeof(float));
+    mix(g->dix.data(), g->dix.size() * sizeof(int32_t));
+    g->content_id = h;
+  }
   wos::HostSceneInput in;
   in.dim = dim;
   in.vertices = d->vertices; in.prims = d->prims; in.n_vertices = d->n_vertices; in.n_prims = d->n_prims;

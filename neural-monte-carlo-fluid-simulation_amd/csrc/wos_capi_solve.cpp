@@ -221,12 +221,12 @@ Batches batches(int64_t n, int64_t wpp) {
 }
 
 int batch_head(DevCtx& c, int dim, const SolvePlan& P, int64_t k, const float* d_pts, int64_t nb,
-               const wos::DevTasks& tk, hipEvent_t after_zero, hipStream_t st) {
+               const wos::DevTasks& tk, hipEvent_t after_zero, hipStream_t st, unsigned long long* cksum) {
   HIP_TRY(wos::launch_zero(k == 0 ? c.d_counters : c.d_counters + wos::kNumCounters,
                            k == 0 ? wos::kNumCounterSlots : wos::kNumCounterSlots - wos::kNumCounters,
                            tk.hist, 2 * wos::kCostBuckets, st));
   if (after_zero) HIP_TRY(hipEventRecord(after_zero, st));
-  HIP_TRY(wos::launch_point_setup(dim, P.dfb, P.dp, d_pts, nb, tk, st));
+  HIP_TRY(wos::launch_point_setup(dim, P.dfb, P.dp, d_pts, nb, tk, st, cksum));
   HIP_TRY(wos::launch_lpt_order(tk, nb, st));
   return WOS_OK;
 }
@@ -278,10 +278,46 @@ int solve_locked(wos_scene* s, const wos_solver_params* prm, const float* pts, i
     WOS_TRY(ensure_tasks(c, dim, bt.chunk * wpp, bt.chunk, C));
     WOS_TRY(solve_grids(c, dim, bt.chunk, false, plan));
   }
+  // Length hints: the plain 2D one-channel solve in one batch (the other kernels carry none of it).
+  // The list this solve's walk kernel leaves serves the next solve of the same key; the one in the
+  // workspace is used if it was left under this solve's key.
+  const bool hinted = dim == 2 && !dp.robust && dp.neumann_inert && C == 1 && bt.n_chunks == 1 && !ex.ddir &&
+                      !ex.deriv && !(prm->schedule & WOS_SCHED_NO_LENGTH_HINTS);
+  uint32_t* hc = nullptr;
+  uint32_t hint_word = 0;
+  bool hint_use = false;
+  HintTuning ht{};
+  HintKey hint_key;
+  if (hinted) {
+    {
+      std::lock_guard<std::mutex> lk(g_hint_mu);
+      ht = g_hint_tuning;
+    }
+    WOS_TRY(ensure_hints(c, bt.chunk * wpp, &hc));
+    HintKey& key = hint_key;
+    key.dim = dim; key.wpp = (int32_t)wpp; key.n_walks = dp.n_walks; key.n_anti = dp.n_anti;
+    key.n = n; key.index_base = index_base; key.index_stride = index_stride;
+    key.seed = dp.seed; key.geometry = s->geom->content_id;
+    key.max_walk_length = dp.max_walk_length; key.steps_before_tikhonov = dp.steps_before_tikhonov;
+    key.steps_before_maximal_spheres = dp.steps_before_maximal_spheres;
+    key.use_cosine = dp.use_cosine; key.ignore_dirichlet = dp.ignore_dirichlet;
+    key.ignore_neumann = dp.ignore_neumann; key.ignore_source = dp.ignore_source;
+    key.force_estimate = dp.force_estimate;
+    key.watertight = s->dev.watertight; key.double_sided = s->dev.double_sided;
+    key.epsilon_shell = dp.epsilon_shell; key.min_star_radius = dp.min_star_radius;
+    key.silhouette_precision = dp.silhouette_precision; key.rr_threshold = dp.rr_threshold;
+    key.absorption = s->dev.absorption;
+    hint_use = c.hint_key_valid && key == c.hint_key;
+    // the list belongs to nobody until this solve's walk kernel, which refills it, is enqueued
+    c.hint_key_valid = false;
+    hint_word = wos::kHintCollect | (hint_use ? wos::kHintUse : 0u) | ((uint32_t)ht.priority << wos::kHintPrioShift) |
+                ((uint32_t)ht.hint_min << wos::kHintMinShift);
+  }
+  if (n > 0) c.hint_last = hinted;
   StatSlot* slot = nullptr;
   WOS_TRY(slot_open(c, st, 4 * bt.n_chunks, bt.n_chunks, plan.shape(), &slot));
   StatSlot& q = *slot;
-  if (bt.n_chunks == 0) HIP_TRY(wos::launch_zero(c.d_counters, wos::kMainCounterSlots, nullptr, 0, st));
+  if (bt.n_chunks == 0) HIP_TRY(wos::launch_zero(c.d_counters, wos::kNumCounterSlots, nullptr, 0, st));
   for (int64_t k = 0; k < bt.n_chunks; k++) {
     const int64_t b0 = k * bt.chunk;
     hipEvent_t* ev = &q.bev[4 * k];
@@ -293,12 +329,24 @@ int solve_locked(wos_scene* s, const wos_solver_params* prm, const float* pts, i
     unsigned int* q_points = (unsigned int*)(c.d_counters + wos::kNumCounters);
     unsigned int* q_tasks = (unsigned int*)(c.d_counters + wos::kTaskQueueSlot0);
     const int walk_grid = (int)std::min<int64_t>(plan.grid_walk, (tk.T + 63) / 64);
-    WOS_TRY(batch_head(c, dim, plan, k, d_pts + b0 * dim, nb, tk, ev[0], st));
+    tk.hint = hint_word;
+    WOS_TRY(batch_head(c, dim, plan, k, d_pts + b0 * dim, nb, tk, ev[0], st,
+                       hinted ? (unsigned long long*)(hc + wos::H_CK_CUR) : nullptr));
+    // at most one express wave's worth per workgroup of the walk grid: where more walks than that are
+    // "long", they are the bulk, and sparse waves would only cost throughput
+    if (hinted)
+      HIP_TRY(wos::launch_hint_build(hc, hint_use ? 1 : 0, (uint32_t)ht.express_min, (uint32_t)ht.express_per_wave,
+                                     (uint32_t)ht.capacity, (uint32_t)walk_grid * (uint32_t)ht.express_per_wave, tk,
+                                     st));
     HIP_TRY(wos::launch_first_balls(plan.kv, plan.dfb, dp, d_pts + b0 * dim, nb, bbase, index_stride, tk,
                                     c.d_counters, q_points, plan.grid_fb, plan.shmem_fb_run, plan.lhs_floats, st));
     HIP_TRY(hipEventRecord(ev[1], st));
     HIP_TRY(wos::launch_walks(plan.kv, plan.dsc, dp, tk, bbase, index_stride, c.d_counters, q_tasks, walk_grid,
                               plan.shmem_walk, plan.geom_floats_walk, st));
+    if (hinted) {
+      c.hint_key = hint_key;
+      c.hint_key_valid = true;
+    }
     HIP_TRY(hipEventRecord(ev[2], st));
     WOS_TRY(fold_channels(dim, dp, tk, C, nb, b0, n, out.dev, st));
     HIP_TRY(hipEventRecord(ev[3], st));

@@ -175,7 +175,7 @@ int wos_tape_record(wos_scene* s, const wos_solver_params* prm, const float* pts
   struct EvGuard { hipEvent_t& a; hipEvent_t& b; ~EvGuard() { if (a) hipEventDestroy(a); if (b) hipEventDestroy(b); } } evg{ev0, ev1};
   HIP_TRY(hipEventCreate(&ev1));
   HIP_TRY(hipEventRecord(ev0, st));
-  if (bt.n_chunks == 0) HIP_TRY(wos::launch_zero(c.d_counters, wos::kMainCounterSlots, nullptr, 0, st));
+  if (bt.n_chunks == 0) HIP_TRY(wos::launch_zero(c.d_counters, wos::kNumCounterSlots, nullptr, 0, st));
   tape->seg.reserve((size_t)bt.n_chunks);
   for (int64_t k = 0; k < bt.n_chunks; k++) {
     const int64_t b0 = k * bt.chunk;

@@ -53,7 +53,11 @@ enum { D_ITERS = 0, D_LANES, D_STAR, D_RAY, D_SAMPLE, D_STEP, D_LOOP, D_RAYOVF, 
        D_L_ITERS, D_L_STEP, D_L_STAR, D_L_MID, D_L_RAY, D_L_END, D_L_SAMPLE, D_L_TAIL, D_L_LOOP,
        D_L_S_CELL, D_L_S_PFX, D_L_S_WIN, D_L_S_FIN, D_L_S_BUILD, D_L_S_PRE, D_L_S_POST,
        // first-ball parts: ball update, member a's source sample, the rest of member a, member b, task stores
-       D_FB_UPD, D_FB_SMP, D_FB_MA, D_FB_MB, D_FB_ST, D_FB_ITSUM, D_FB_ITMAX, D_NUM };  // X: iterations after the wave's task queue ran dry
+       D_FB_UPD, D_FB_SMP, D_FB_MA, D_FB_MB, D_FB_ST, D_FB_ITSUM, D_FB_ITMAX,
+#if WOS_DIAG
+       D_E_ITERS, D_E_LANES, D_E_LOOP,  // iterations of waves that hold express walks (length hints)
+#endif
+       D_NUM };  // X: iterations after the wave's task queue ran dry
 // slots holding maxima (folded with atomicMax)
 __host__ __device__ constexpr bool diag_is_max(int k) { return k == D_FB_MAX || k == D_WMAXLEN || k == D_WAVEMAX; }
 static __device__ unsigned long long g_diag[D_NUM];
@@ -3748,11 +3752,14 @@ static_assert((kSetupLanes & (kSetupLanes - 1)) == 0 && kSetupLanes <= kWave, "k
 // first-ball radius per point, the cost-bucket histogram of the walk queue and (2D Yukawa,
 // reference float semantics) the first ball's Bessel members at mu R.  The first-ball kernel
 // then takes the points in plain point order from an atomic queue.
+// cksum (length hints; null otherwise): += a 64-bit checksum of the point coordinates, one atomic per block.
 template <int DIM>
 __global__ __launch_bounds__(256) void wos_point_setup_kernel(const DevScene sc, const DevParams prm,
                                                              const float* __restrict__ pts, int64_t n,
-                                                             const DevTasks tk) {
+                                                             const DevTasks tk, unsigned long long* cksum) {
   __shared__ uint32_t s_hist[kCostBuckets];
+  __shared__ unsigned long long s_ck;
+  if (threadIdx.x == 0) s_ck = 0ull;
   // small boundaries staged in LDS: every lane scans every record (broadcast reads)
   // instead of one global round trip per primitive
   __shared__ __attribute__((aligned(16))) float s_prim[kSetupLdsFloats];
@@ -3810,10 +3817,22 @@ __global__ __launch_bounds__(256) void wos_point_setup_kernel(const DevScene sc,
         }
       }
       atomicAdd(&s_hist[bucket], 1u);
+      if (DIM == 2 && cksum != nullptr) {  // (length hints are 2D)
+        // order-independent sum of a mix of (index, coordinate bits): splitmix64's finaliser
+        unsigned long long h = (unsigned long long)i * 0x9E3779B97F4A7C15ull;
+        for (int k = 0; k < DIM; k++) {
+          h ^= (unsigned long long)__float_as_uint(x[k]) << (k & 1 ? 32 : 0);
+          h = (h ^ (h >> 30)) * 0xBF58476D1CE4E5B9ull;
+          h = (h ^ (h >> 27)) * 0x94D049BB133111EBull;
+          h ^= h >> 31;
+        }
+        atomicAdd(&s_ck, h);
+      }
     }
   }
   __syncthreads();
   if (threadIdx.x < kCostBuckets && s_hist[threadIdx.x]) atomicAdd(&tk.hist[threadIdx.x], s_hist[threadIdx.x]);
+  if (DIM == 2 && cksum != nullptr && threadIdx.x == 0) atomicAdd(cksum, s_ck);
 }
 
 // RB: robust float semantics (DevParams::robust; Gfn::scaled) -- separate instantiations
@@ -3837,6 +3856,12 @@ __device__ __forceinline__ void wave_priority(int level) {
   if (level == 1) __builtin_amdgcn_s_setprio(1);
   else if (level == 2) __builtin_amdgcn_s_setprio(2);
   else if (level >= 3) __builtin_amdgcn_s_setprio(3);
+}
+
+// ... back down too (wave_priority leaves level 0 alone)
+__device__ __forceinline__ void wave_priority_set(int level) {
+  if (level <= 0) __builtin_amdgcn_s_setprio(0);
+  else wave_priority(level);
 }
 
 // ---- kernel 2: walks ---------------------------------------------------------
@@ -3952,9 +3977,11 @@ __device__ __forceinline__ int walk_iteration(const DevScene& sc, const DevParam
 }
 
 // the record of a finished walk (walk_on_stars.h:583-585: escaped and over-length walks are dropped)
-template <int DIM, int NC, bool REC>
+// HINT (the plain 2D walk kernels): a walk of >= hint_min steps is offered to the length-hint list at hc
+template <bool HINT = false, int DIM, int NC, bool REC>
 __device__ __forceinline__ void walk_finish(const DevScene& sc, const DevParams& prm, const DevTasks& tk, int64_t t,
-                                            int code, WalkState<DIM, NC, REC>& st, uint32_t wsteps, unsigned int* s_ctr) {
+                                            int code, WalkState<DIM, NC, REC>& st, uint32_t wsteps, unsigned int* s_ctr,
+                                            unsigned int* hc = nullptr) {
   flush_source<DIM>(st);
   const bool recorded = code == WC_DIRICHLET || code == WC_RR;
   if (recorded) {
@@ -3981,6 +4008,17 @@ __device__ __forceinline__ void walk_finish(const DevScene& sc, const DevParams&
     }
   }
   if (!WOS_ACCT_NOREC) tk.code[t] = (wsteps << 1) | (recorded ? 1u : 0u);
+  if constexpr (HINT) {
+    if ((tk.hint & kHintCollect) && wsteps >= ((tk.hint >> kHintMinShift) & kHintMinMask)) {
+      // one device-scope atomic per listed walk; once the list is full the walks are only counted, in
+      // the workgroup (s_ctr[C_PTS], which the walk kernel does not use otherwise; added to H_NLIST at its end)
+      const uint32_t cap = hc[H_CAP];
+      uint32_t i = __hip_atomic_load(&hc[H_NLIST], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (i < cap) i = atomicAdd(&hc[H_NLIST], 1u);
+      else atomicAdd(&s_ctr[C_PTS], 1u);
+      if (i < cap) (*reinterpret_cast<uint2* const*>(hc + H_LIST))[i] = make_uint2((uint32_t)t, wsteps);
+    }
+  }
   DIAG_MAX(D_WMAXLEN, wsteps);
   atomicAdd(&s_ctr[recorded ? C_STEPS : C_WASTED], wsteps);
   atomicAdd(&s_ctr[code == WC_DIRICHLET ? C_DIR : code == WC_RR ? C_RR : code == WC_ESCAPED ? C_ESC : C_MAXL], 1u);

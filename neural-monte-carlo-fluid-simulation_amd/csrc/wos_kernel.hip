@@ -64,9 +64,9 @@ __global__ __launch_bounds__(256) void wos_lpt_scatter_kernel(const DevTasks tk,
   X(3, true, false, false, false, false, 1)
 UNIT_FIRST_BALLS(WOS_FIRST_BALL_INSTANTIATE)
 template __global__ void wos_point_setup_kernel<2>(const DevScene, const DevParams, const float*, int64_t,
-                                                   const DevTasks);
+                                                   const DevTasks, unsigned long long*);
 template __global__ void wos_point_setup_kernel<3>(const DevScene, const DevParams, const float*, int64_t,
-                                                   const DevTasks);
+                                                   const DevTasks, unsigned long long*);
 UNIT_WALKS(WOS_WALK_INSTANTIATE)
 UnitKernels unit_kernels_plain(const KernelVariant& v) {
   UnitKernels k;
@@ -155,11 +155,101 @@ hipError_t launch_first_balls(const KernelVariant& v, const DevScene& sc, const 
 }
 
 hipError_t launch_point_setup(int dim, const DevScene& sc, const DevParams& prm, const float* pts, int64_t n,
-                              const DevTasks& tk, hipStream_t s) {
+                              const DevTasks& tk, hipStream_t s, unsigned long long* cksum) {
   const int grid = (int)((n * kSetupLanes + 255) / 256);
   if (grid < 1) return hipSuccess;
-  if (dim == 2) hipLaunchKernelGGL(wos_point_setup_kernel<2>, dim3(grid), dim3(256), 0, s, sc, prm, pts, n, tk);
-  else hipLaunchKernelGGL(wos_point_setup_kernel<3>, dim3(grid), dim3(256), 0, s, sc, prm, pts, n, tk);
+  if (dim == 2) hipLaunchKernelGGL(wos_point_setup_kernel<2>, dim3(grid), dim3(256), 0, s, sc, prm, pts, n, tk, cksum);
+  else hipLaunchKernelGGL(wos_point_setup_kernel<3>, dim3(grid), dim3(256), 0, s, sc, prm, pts, n, tk, cksum);
+  return hipGetLastError();
+}
+
+// ---- length hints: the express list (wos_scene.h H_*; DESIGN.md, Length hints) ----
+// One block.  The list the last hinted walk kernel left holds (task, steps) of its long walks.  If the
+// host's key matched (use) and the points are the ones the list was collected on (the point-setup
+// checksums agree), the entries of >= express_min steps become the express list, longest first (a
+// counting sort by steps; the order inside a step count is immaterial), each with its bit in the
+// task bitmap and its point flagged in pstate (after point setup rewrote it).  The bits of the
+// previous express list are cleared first, so the bitmap is never swept.  Then the list, the claim
+// counters and the checksum are reset for the walk kernel that follows.
+constexpr int kHintBins = 1024;
+__global__ __launch_bounds__(kHintBins) void wos_hint_build_kernel(uint32_t* __restrict__ hc, int use,
+                                                                   uint32_t express_min, uint32_t epw, uint32_t cap,
+                                                                   uint32_t max_express, const DevTasks tk) {
+  __shared__ uint32_t s_bin[kHintBins], s_wave[kHintBins / kWave];
+  const int tid = threadIdx.x;
+  uint32_t* const express = *reinterpret_cast<uint32_t* const*>(hc + H_EXPRESS);
+  uint32_t* const bits = *reinterpret_cast<uint32_t* const*>(hc + H_BITS);
+  const uint2* const list = *reinterpret_cast<const uint2* const*>(hc + H_LIST);
+  const unsigned long long ck_cur = *reinterpret_cast<const unsigned long long*>(hc + H_CK_CUR);
+  const unsigned long long ck_list = *reinterpret_cast<const unsigned long long*>(hc + H_CK_LIST);
+  const uint32_t n_old = hc[H_NEXPRESS];
+  const uint32_t n = hc[H_NLIST] < hc[H_CAP] ? hc[H_NLIST] : hc[H_CAP];
+  // (a list that overflowed is a sample of walks that are the bulk, not the tail: no express list)
+  const bool ok = use != 0 && ck_cur == ck_list && hc[H_NLIST] <= hc[H_CAP];
+  const uint32_t T = (uint32_t)tk.T, wpp = (uint32_t)tk.wpp;
+  for (uint32_t i = tid; i < n_old; i += kHintBins) {
+    const uint32_t t = express[i];
+    atomicAnd(&bits[t >> 5], ~(1u << (t & 31u)));
+  }
+  s_bin[tid] = 0u;
+  __syncthreads();
+  // an entry goes express: long enough, a task of this batch, its point estimated; bin 0: the longest
+  const auto bin_of = [&](const uint2 e) -> int {
+    if (e.y < express_min || e.x >= T || !(tk.pstate[e.x / wpp] & kPtEstimate)) return -1;
+    return kHintBins - 1 - (int)(e.y < (uint32_t)kHintBins - 1u ? e.y : (uint32_t)kHintBins - 1u);
+  };
+  if (ok)
+    for (uint32_t i = tid; i < n; i += kHintBins) {
+      const int b = bin_of(list[i]);
+      if (b >= 0) atomicAdd(&s_bin[b], 1u);
+    }
+  __syncthreads();
+  // exclusive scan of the bins: inside each wave by shuffles, then the waves' totals
+  const int lane = tid & (kWave - 1), wv = tid / kWave;
+  const uint32_t mine = s_bin[tid];
+  uint32_t inc = mine;
+  for (int off = 1; off < kWave; off <<= 1) {
+    const uint32_t v = (uint32_t)__shfl_up((int)inc, off);
+    if (lane >= off) inc += v;
+  }
+  if (lane == kWave - 1) s_wave[wv] = inc;
+  __syncthreads();
+  uint32_t before = 0, total = 0;
+  for (int w = 0; w < kHintBins / kWave; w++) {
+    if (w < wv) before += s_wave[w];
+    total += s_wave[w];
+  }
+  s_bin[tid] = before + inc - mine;  // the bin's fill cursor
+  __syncthreads();
+  if (ok)
+    for (uint32_t i = tid; i < n; i += kHintBins) {
+      const uint2 e = list[i];
+      const int b = bin_of(e);
+      if (b < 0) continue;
+      // (the longest max_express of them: express waves are for the few walks that outlast the bulk)
+      const uint32_t pos = atomicAdd(&s_bin[b], 1u);
+      if (pos >= max_express) continue;
+      express[pos] = e.x;
+      atomicOr(&bits[e.x >> 5], 1u << (e.x & 31u));
+      atomicOr(&tk.pstate[e.x / wpp], kPtExpress);
+    }
+  __syncthreads();
+  if (tid == 0) {
+    hc[H_NEXPRESS] = ok ? (total < max_express ? total : max_express) : 0u;
+    hc[H_EPW] = epw;
+    hc[H_CAP] = cap;
+    hc[H_CLAIMED] = 0u;
+    hc[H_NLIST] = 0u;
+    hc[H_XCLAIM] = 0u;
+    *reinterpret_cast<unsigned long long*>(hc + H_CK_LIST) = ck_cur;
+    *reinterpret_cast<unsigned long long*>(hc + H_CK_CUR) = 0ull;
+  }
+}
+
+hipError_t launch_hint_build(uint32_t* hc, int use, uint32_t express_min, uint32_t express_per_wave, uint32_t cap,
+                             uint32_t max_express, const DevTasks& tk, hipStream_t s) {
+  hipLaunchKernelGGL(wos_hint_build_kernel, dim3(1), dim3(kHintBins), 0, s, hc, use, express_min, express_per_wave, cap,
+                     max_express, tk);
   return hipGetLastError();
 }
 
@@ -293,6 +383,8 @@ void diag_print(const char* tag, const void* sym) {
   fprintf(stderr, "[diag %s] after the queue ran dry: %llu iterations (%.1f%%), lanes/iter %.2f, %.1f%% of loop cycles\n",
           tag, d[D_XITERS], 100.0 * d[D_XITERS] / (d[D_ITERS] ? d[D_ITERS] : 1),
           (double)d[D_XLANES] / (d[D_XITERS] ? d[D_XITERS] : 1), 100.0 * d[D_XLOOP] / (d[D_LOOP] ? d[D_LOOP] : 1));
+  fprintf(stderr, "[diag %s] express waves: %llu iterations, lanes/iter %.2f, cycles/iter (loop) %.0f\n", tag, d[D_E_ITERS],
+          (double)d[D_E_LANES] / (d[D_E_ITERS] ? d[D_E_ITERS] : 1), (double)d[D_E_LOOP] / (d[D_E_ITERS] ? d[D_E_ITERS] : 1));
   const double li = (double)(d[D_L_ITERS] ? d[D_L_ITERS] : 1);
   fprintf(stderr, "[diag %s] <=2 live lanes: %llu iterations, cycles/iter: loop %.0f step %.0f star %.0f (cell %.0f prefix %.0f "
                   "window %.0f final %.0f) mid %.0f ray %.0f end %.0f sample %.0f tail %.0f\n",

@@ -15,7 +15,9 @@ constexpr int kNumCounters = 9;
 // task queues from slot kNumCounters + 8 on, one per 64-byte line (wos_walk_kernel)
 constexpr int kTaskQueueSlot0 = kNumCounters + 8;
 constexpr int kNumCounterSlots = kTaskQueueSlot0 + kMaxTaskQueues * 8;
-constexpr int kMainCounterSlots = kNumCounterSlots;  // the main solve's counter buffer
+// the main solve's counter buffer: + the length hints' control block (wos_scene.h H_*)
+constexpr int kMainCounterSlots = kNumCounterSlots + H_WORDS / 2;
+static_assert(2 * (kNumCounterSlots - kTaskQueueSlot0) == kHintBlockWord, "the control block follows the task queues");
 
 // the first balls of every estimated point (after launch_point_setup)
 hipError_t launch_first_balls(const KernelVariant& v, const DevScene& sc, const DevParams& prm, const float* pts,
@@ -23,8 +25,15 @@ hipError_t launch_first_balls(const KernelVariant& v, const DevScene& sc, const 
                               unsigned long long* counters, unsigned int* work, int grid, size_t shmem, int lhs_floats,
                               hipStream_t s);
 // per-point setup: pstate + first-ball radius + bucket histogram, before launch_lpt_order
+// cksum (or null): += a checksum of the point coordinates (length hints)
 hipError_t launch_point_setup(int dim, const DevScene& sc, const DevParams& prm, const float* pts, int64_t n,
-                              const DevTasks& tk, hipStream_t s);
+                              const DevTasks& tk, hipStream_t s, unsigned long long* cksum = nullptr);
+// length hints: the express list of the walk kernel about to run from the list its predecessor left
+// (use 0, or another point checksum: none; at most max_express entries, the longest), then the list
+// and the claim counters reset.  hc: the control block; after launch_point_setup(..., cksum = hc +
+// H_CK_CUR), before launch_walks.
+hipError_t launch_hint_build(uint32_t* hc, int use, uint32_t express_min, uint32_t express_per_wave, uint32_t cap,
+                             uint32_t max_express, const DevTasks& tk, hipStream_t s);
 // geometry queries (wos_query.hip; include/wos.h wos_scene_query): per point the distance, signed
 // distance and closest point [n][dim] of boundary `which` (0 Neumann, 1 Dirichlet) and the state
 // word for `mask` (pstate's bits 0-2, bit 3 inside); every output may be null

@@ -180,6 +180,9 @@ struct DevTasks {
   float* prad;      // [n] first-ball radius 0.99 min(dDist, nDist) (point-setup kernel -> presorted first balls)
   int64_t T;
   int32_t wpp;      // walks per point = n_pairs * n_anti
+  // length hints of the plain 2D walk kernels (kHint*, below), in the padding that followed wpp, so the
+  // layout every other kernel sees is unchanged; 0: neither collect nor use
+  uint32_t hint;
   // Boundary-start walks (estimateSolution, walk_on_stars.h:353-464; boundary value
   // caching): per task the start normal [DIM][T], the first sphere radius [T] and
   // bit 0 "starts on the Neumann boundary" [T].  They alias the first-ball record
@@ -197,6 +200,37 @@ struct DevTasks {
   // (getEstimatedDerivative, :843-846; nullptr: not computed) -- BVC's Dirichlet samples
   const float* ddir;
   float* deriv;
+};
+
+// ---- length hints (Length hints) ----
+// The walks of a solve do not depend on the source, so a time-stepper's next projection repeats
+// them step for step.  The plain 2D walk kernel lists the walks that took >= hint_min steps; the
+// next solve of the same walks starts those of >= express_min steps first, longest first, in
+// waves that hold nothing else ("express").  A scheduling hint only: results do not depend on it.
+// DevTasks::hint: bit 0 collect, bit 1 use the express list, bits 2-3 the express waves' issue
+// priority, bits 8-23 hint_min.
+constexpr uint32_t kHintCollect = 1u, kHintUse = 2u;
+constexpr int kHintPrioShift = 2, kHintMinShift = 8;
+constexpr uint32_t kHintMinMask = 0xFFFFu;
+constexpr int32_t kPtExpress = 1 << 16;    // pstate: some walk of the point is express-owned
+constexpr uint32_t kHintListMax = 1u << 16;  // entries of the collection list (and of the express list)
+// the control block's first word, counted from the walk kernel's task queues (its `tqueue`)
+constexpr int kHintBlockWord = kMaxTaskQueues * (int)kTaskQueueStride;
+// The control block: u32 words that follow the main solve's counter slots (kNumCounterSlots u64 after
+// `counters`).  The two atomics of the walk kernel sit on lines of their own.
+enum {
+  H_NLIST = 0,      // walks offered to the list by the running walk kernel (may exceed H_CAP)
+  H_XCLAIM = 16,    // express entries handed out
+  H_NEXPRESS = 32,  // entries of the express list
+  H_EPW,            // express walks a wave claims at once
+  H_CAP,            // capacity of the list in use (<= kHintListMax)
+  H_CLAIMED,        // express walks started by the last hinted walk kernel
+  H_CK_CUR = 48,    // u64: checksum of the points of the running solve (point setup)
+  H_CK_LIST = 50,   // u64: ... of the solve that filled the list
+  H_LIST = 52,      // u64: uint2* (task, steps)
+  H_EXPRESS = 54,   // u64: uint32_t* tasks, longest first
+  H_BITS = 56,      // u64: uint32_t* one bit per task: express-owned
+  H_WORDS = 64
 };
 
 // What a recording pass (wos_tape.hip) keeps of a batch's walks instead of their source-dependent

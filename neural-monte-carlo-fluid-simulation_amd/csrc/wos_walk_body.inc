@@ -12,6 +12,10 @@
   static_assert(walk_pack_words<DIM, NC>() * kSpreadMax * 4 <= (int)walk_scratch_bytes<DIM>(), "mailbox fits the scratch");
   static_assert(!(BSTART && NC != 1), "boundary-start walks carry one channel");
   constexpr bool kSpread = SPR;
+  // length hints (wos_scene.h): the plain solve's 2D walks alone
+  // (the Neumann-inert instantiations, where they cost neither registers nor scratch: with the Neumann term's
+  // live state the claim and skip code pushed the tail-spreading kernel from 12 to 36 B/lane of scratch)
+  constexpr bool HINT = DIM == 2 && !BSTART && !RB && !REC && NC == 1 && !NEU;
   const int lane = threadIdx.x & (kWave - 1);
   stage_geometry<DIM, GG>(sc, smem, true);
   stage_rej_jump(prm);
@@ -76,9 +80,38 @@
   const uint32_t qhome = blockIdx.x & (kTaskQueues - 1u);
   uint32_t qdone = 0u;  // queues found exhausted (wave-uniform)
   int head = 0, S = 0;
-  uint32_t s_t = 0, s_ok = 0;  // staged task index, its point is estimated
+  uint32_t s_t = 0, s_ok = 0;  // staged task index, its point is estimated (HINT: | 2 it has express-owned walks)
+  // HINT: the control block follows the counter slots (tqueue starts at slot kTaskQueueSlot0)
+  unsigned int* const hc = tqueue + kHintBlockWord;
+  bool xhold = false;  // this wave holds express walks: nothing from the bulk queue until they have ended
+  // up to H_EPW tasks off the express list into the (empty) ring; false once the list is handed out
+  auto claim_express = [&]() -> bool {
+    if constexpr (HINT) {
+      uint32_t i0 = 0, n = 0;
+      if (lane == 0) {
+        const uint32_t nx = hc[H_NEXPRESS], epw = hc[H_EPW];
+        if (__hip_atomic_load(&hc[H_XCLAIM], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < nx) {
+          i0 = atomicAdd(&hc[H_XCLAIM], epw);
+          n = i0 < nx ? (nx - i0 < epw ? nx - i0 : epw) : 0u;
+          if (n) atomicAdd(&hc[H_CLAIMED], n);
+        }
+      }
+      i0 = (uint32_t)__builtin_amdgcn_readlane((int)i0, 0);
+      n = (uint32_t)__builtin_amdgcn_readlane((int)n, 0);
+      if (n == 0u) return false;
+      const uint32_t pos = (uint32_t)((lane - head) & (kWave - 1));
+      if (pos < n) {
+        s_t = (*reinterpret_cast<const uint32_t* const*>(hc + H_EXPRESS))[i0 + pos];
+        s_ok = kPtEstimate;
+      }
+      S = (int)n;
+      return true;
+    } else {
+      return false;
+    }
+  };
   auto refill = [&](const DevTasks& tk) {
-    while (S < kWave && !exhausted) {
+    while (S < kWave && !exhausted && !(HINT && xhold)) {
       if (wq >= we) {
         unsigned int c = 0xFFFFFFFFu, len = 0u;
         if (lane == 0) {
@@ -116,12 +149,25 @@
       const uint32_t pidx = (uint32_t)__shfl((int)wperm, (int)(qp - wp0));  // queue position -> permuted point
       if (mine) {
         s_t = pidx * wpp + (q - qp * wpp);
-        s_ok = tk.pstate[pidx] & kPtEstimate;
+        if constexpr (HINT) {
+          const uint32_t ps = (uint32_t)tk.pstate[pidx];
+          s_ok = (ps & kPtEstimate) | ((ps & (uint32_t)kPtExpress) ? 2u : 0u);
+        } else {
+          s_ok = tk.pstate[pidx] & kPtEstimate;
+        }
       }
       S += take;
       wq += (uint32_t)take;
     }
   };
+  if constexpr (HINT) {
+    // express waves: one wave per workgroup (rotating over the SIMDs), which claims until the list is
+    // dry -- the host caps the list at gridDim.x claims, so the first round spreads it over the grid
+    if ((tk.hint & kHintUse) && (uint32_t)wave_u == (blockIdx.x & (kBlock / kWave - 1u)) && hc[H_NEXPRESS] > 0u) {
+      xhold = claim_express();
+      if (xhold) wave_priority((int)((tk.hint >> kHintPrioShift) & 3u));
+    }
+  }
   refill(tk);
   int64_t t = -1;           // this lane's task
   WalkState<DIM, NC, REC> st;
@@ -153,9 +199,19 @@
         const int take = k < S ? k : S;
         const int src = (head + (rank < take ? rank : 0)) & (kWave - 1);
         // the staged task index with its point's estimate bit on top (tasks < 2^31): one shuffle
-        const uint32_t v_pk = (uint32_t)__shfl((int)(s_t | (s_ok ? 0x80000000u : 0u)), src);
-        const uint32_t v_t = v_pk & 0x7FFFFFFFu;
-        const uint32_t v_ok = v_pk >> 31;
+        // (HINT: s_ok's two bits in bits 30 and 31; tasks < 2^30, WOS_BATCH_LOG2)
+        const uint32_t v_pk =
+            (uint32_t)__shfl((int)(HINT ? s_t | (s_ok << 30) : s_t | (s_ok ? 0x80000000u : 0u)), src);
+        const uint32_t v_t = v_pk & (HINT ? 0x3FFFFFFFu : 0x7FFFFFFFu);
+        const uint32_t v_ok = HINT ? (v_pk >> 30) & 1u : v_pk >> 31;
+        // HINT: a task an express wave owns is skipped, its record untouched: the lane sits this
+        // hand-out out (t >= 0 for the length of it)
+        bool v_own = false;
+        if constexpr (HINT) {
+          if (t < 0 && rank < take && (v_pk >> 31))
+            v_own = ((*reinterpret_cast<const uint32_t* const*>(hc + H_BITS))[v_t >> 5] >> (v_t & 31u)) & 1u;
+          if (v_own) t = 0;
+        }
         float v_pt[DIM], v_thr = 0.0f, v_tsrc[NC], v_dd = 0.0f;
         for (int c = 0; c < NC; c++) v_tsrc[c] = 0.0f;
         if (t < 0 && rank < take && v_ok) {  // the task record from memory, at hand-out
@@ -186,6 +242,9 @@
                                         g, ws, ddist, wsteps, firstR);
           }
         }
+        if constexpr (HINT) {
+          if (v_own) t = -1;
+        }
         head = (head + take) & (kWave - 1);
         S -= take;
 #if WOS_TIMELINE
@@ -194,6 +253,11 @@
       }
     }
     if (__ballot(t >= 0) == 0) {
+      if (HINT && xhold && S == 0) {  // its express walks have ended: more of them, or the bulk
+        xhold = claim_express();
+        if (xhold) continue;
+        wave_priority_set(prm.wave_prio);
+      }
       if (S == 0 && exhausted) {  // queue drained and every lane idle
         if (!kSpread) break;
         // idle: announce, then take a sibling's hand-over or leave once no wave holds walks
@@ -244,10 +308,14 @@
     }
 #endif
     if (t >= 0 && code >= 0) {
-      walk_finish<DIM>(sc, prm, tk, t, code, st, wsteps, s_ctr);
+      walk_finish<HINT>(sc, prm, tk, t, code, st, wsteps, s_ctr, hc);
       t = -1;
     }
-    if (kSpread && exhausted && S == 0) {
+    // (HINT: an express wave never draws from the queue, so it never sees it dry; a sibling that has
+    // announced itself idle has, and the express walks spread like any others from then on)
+    bool dry = exhausted;
+    if constexpr (HINT) dry = dry || xhold;
+    if (kSpread && dry && S == 0) {
       const uint64_t live = __ballot(t >= 0);
       const int k = __popcll(live);
       if (k >= 2 && __builtin_amdgcn_readfirstlane(
@@ -292,6 +360,11 @@
     DIAG_ADD_LONE(D_LOOP, D_L_LOOP, t_loop, lone_it);
 #endif
 #if WOS_DIAG
+    if (HINT && xhold && !exhausted) {  // an express wave (it never sees the queue dry itself)
+      DIAG_COUNT(D_E_ITERS, 1);
+      DIAG_COUNT(D_E_LANES, __popcll(__ballot(t >= 0)));
+      DIAG_ADD(D_E_LOOP, t_loop);
+    }
     if (exhausted) {
       DIAG_COUNT(D_XITERS, 1);
       DIAG_COUNT(D_XLANES, __popcll(__ballot(t >= 0)));
@@ -308,4 +381,7 @@
     else atomicAdd(&g_diag[threadIdx.x], s_diag[threadIdx.x]);
   }
 #endif
+  if constexpr (HINT) {
+    if (threadIdx.x == 0 && s_ctr[C_PTS]) atomicAdd(&hc[H_NLIST], s_ctr[C_PTS]);
+  }
   flush_walk_counters(counters, s_ctr);

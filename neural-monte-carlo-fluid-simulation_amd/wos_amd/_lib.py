@@ -75,6 +75,7 @@ SCHED_NO_STAR_GRID = 0x4
 SCHED_NO_DIR_GRID = 0x8
 SCHED_NO_TAIL_SPREAD = 0x10
 SCHED_NO_GRID_SPREAD = 0x20  # reserved: no effect (include/wos.h)
+SCHED_NO_LENGTH_HINTS = 0x40
 
 
 class BvcParams(C.Structure):
@@ -136,6 +137,7 @@ EXPORTS = (
     "wos_siren_vjp", "wos_selftest_siren_vjp_layer",
     "wos_siren_fit",
     "wos_adam_step", "wos_siren_fit_run",
+    "wos_set_length_hints", "wos_length_hint_stats", "wos_selftest_hint_key",
 )
 
 # include/wos.h WOS_QUERY_*: the boundary wos_scene_query's dist / signed_dist / closest describe
@@ -181,6 +183,14 @@ def load():
     L.wos_release_caches.argtypes = [C.c_int32]
     L.wos_set_max_batch_tasks.restype = C.c_int64
     L.wos_set_max_batch_tasks.argtypes = [C.c_int64]
+    # additive within ABI 10: a library built before the length hints (an A/B against WOS_LIB_PATH) lacks them
+    if hasattr(L, "wos_set_length_hints"):
+        L.wos_set_length_hints.restype = None
+        L.wos_set_length_hints.argtypes = [C.c_int32] * 5
+        L.wos_length_hint_stats.restype = C.c_int
+        L.wos_length_hint_stats.argtypes = [C.c_int32, C.POINTER(C.c_int64)]
+        L.wos_selftest_hint_key.restype = C.c_int32
+        L.wos_selftest_hint_key.argtypes = [C.c_int32]
     L.wos_default_params.restype = None
     L.wos_default_params.argtypes = [C.POINTER(SolverParams)]
     L.wos_solve.restype = C.c_int

@@ -746,6 +746,31 @@ def set_max_batch_tasks(n):
     return int(_lib.load().wos_set_max_batch_tasks(int(n)))
 
 
+def set_length_hints(hint_min=-1, express_min=-1, express_per_wave=-1, capacity=-1, priority=-1):
+    """Tunables of the length hints (wos_set_length_hints; a negative value: that one's default).  Scheduling
+    only: results never depend on them."""
+    _lib.load().wos_set_length_hints(int(hint_min), int(express_min), int(express_per_wave), int(capacity),
+                                     int(priority))
+
+
+def length_hint_stats(device=0):
+    """Of the last solve on `device` (waits for it): express walks started, walks the list had no room for,
+    walks listed, entries of the express list it ran with (wos_length_hint_stats)."""
+    out = (C.c_int64 * 4)()
+    check(_lib.load().wos_length_hint_stats(int(device), out), "wos_length_hint_stats")
+    return {"claimed": int(out[0]), "overflow": int(out[1]), "listed": int(out[2]), "express": int(out[3])}
+
+
+def selftest_hint_key():
+    """Per field of the hint key (host only): does a difference in it alone make two keys unequal?"""
+    res = []
+    while True:
+        r = int(_lib.load().wos_selftest_hint_key(len(res)))
+        if r < 0:
+            return res
+        res.append(bool(r))
+
+
 def selftest_math(which, x, device=0):
     x = np.ascontiguousarray(x, dtype=np.float64)
     out = np.empty_like(x)
