@@ -729,8 +729,8 @@ int wos_adam_step(int32_t n_tensors, const int64_t *counts,
  * step = step0 + i + 1 over weights[0..], biases[0..] -- exp_avg and exp_avg_sq are flat in that
  * order.  Bit for bit, in the loss, every parameter and both moments, iteration i is those calls
  * made separately.
- * THIS IS THE ONE ENTRY POINT THAT WRITES THROUGH net->weights[l] AND net->biases[l]: the network
- * is updated in place.
+ * THIS ENTRY POINT WRITES THROUGH net->weights[l] AND net->biases[l]: the network is updated in
+ * place (wos_siren_fit_run_batches below is the only other one that does).
  * Device pointers only: without WOS_PTRS_DEVICE the call is WOS_E_INVALID.  One stream-ordered
  * temporary per call holds the packed weights, the batch, the gradients and the fit step's work.
  * An index outside [0, n_pool) is clamped (no out-of-bounds read) and counted in status[1]; a
@@ -756,6 +756,38 @@ int wos_siren_fit_run(const wos_siren_net *net,
                       float stop_loss, int32_t check_every,
                       float *losses, int64_t *status,
                       size_t workspace_bytes, uint32_t flags, int32_t device, void *stream);
+
+/* ---- Device-resident fit loop over ragged batches read in place -------------------------------
+ * The advection fit's training loop (_advect_velocity, model_split.py:88-120, in _training_loop,
+ * base.py:130-152), whose points are new every iteration and, where samples inside an obstacle are
+ * dropped (base.py:239-241), of another count every iteration (added within ABI 10: a new entry point
+ * only; DESIGN.md "Device-resident advection fit").  pts[total*d_in], target[total*d_out] and
+ * scale[total*d_out] or NULL hold the rows of all iterations one after the other; offsets is a HOST
+ * array of n_iters + 1 row offsets, offsets[0] >= 0 (it need not be 0) and strictly increasing.
+ * Iteration i is wos_siren_fit's step on the n_i = offsets[i+1] - offsets[i] rows from offsets[i] on,
+ * read in place (no gather, no copy; a batch's first row needs no more than a float's alignment),
+ * with wos_siren_fit's own chunking for n = n_i and the same workspace_bytes, the loss, a mean over
+ * n_i d_out, to losses[i]; then wos_adam_step with step = step0 + i + 1.  Bit for bit, in the loss,
+ * every parameter and both moments, iteration i is
+ *   wos_siren_fit(net, pts + offsets[i]*d_in, n_i, target + offsets[i]*d_out,
+ *                 scale ? scale + offsets[i]*d_out : NULL, ...) and wos_adam_step(...)
+ * made separately.  THE NETWORK IS UPDATED IN PLACE through net->weights[l] and net->biases[l], as
+ * in wos_siren_fit_run.  Device pointers only (offsets excepted).  One stream-ordered temporary per
+ * call holds the packed weights, the gradients and the fit step's work, sized for the largest n_i.
+ * Early stop, losses (NaN from the stop on), check_every and status[0] are wos_siren_fit_run's;
+ * status[1] is always 0: there is no index to clamp.
+ * WOS_E_INVALID, naming the field, before any device work: n_iters <= 0, step0 < 0, a NULL pts,
+ * target, offsets, losses, status, exp_avg or exp_avg_sq, offsets[0] < 0, an iteration without rows
+ * (offsets[i+1] <= offsets[i]: a mean over nothing; the iteration is named), a NaN stop_loss,
+ * check_every < 0 or check_every > 0 with WOS_ASYNC, wos_adam_step's parameter rules,
+ * wos_siren_eval's envelope.  A non-zero workspace_bytes below one tile is WOS_E_CAPACITY. */
+int wos_siren_fit_run_batches(const wos_siren_net *net,
+                              const float *pts, const float *target, const float *scale,
+                              const int64_t *offsets, int64_t n_iters,
+                              float *exp_avg, float *exp_avg_sq, int64_t step0, const wos_adam_params *opt,
+                              float stop_loss, int32_t check_every,
+                              float *losses, int64_t *status,
+                              size_t workspace_bytes, uint32_t flags, int32_t device, void *stream);
 
 const char *wos_last_error(void);
 int32_t wos_abi_version(void);

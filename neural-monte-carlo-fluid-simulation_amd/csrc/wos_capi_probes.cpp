@@ -1,7 +1,7 @@
 // wos_capi_probes.cpp -- entry points that need neither a scene's workspace nor the device context:
 // the self-test probes (wos_selftest_*, kernels in wos_selftest.hip) and the fused SIREN
 // (wos_siren_eval, wos_siren.hip; wos_siren_vjp, wos_siren_vjp.hip; wos_siren_fit, wos_siren_fit.hip;
-// wos_adam_step and wos_siren_fit_run, wos_siren_train.hip).  Each call owns what it allocates.
+// wos_adam_step, wos_siren_fit_run and wos_siren_fit_run_batches, wos_siren_train.hip).  Each call owns what it allocates.
 #include "wos_capi.h"
 
 using namespace wos::capi;
@@ -750,6 +750,47 @@ int wos_adam_step(int32_t n_tensors, const int64_t* counts, float* const* params
   return WOS_OK;
 }
 
+// The two fit loops' tensors: the network's own weights and biases for the fit step, and for the Adam
+// step the same tensors, weights, then biases, with their gradients in one flat buffer `g` in that order.
+static void fit_run_bind(const wos_siren_net* net, float* g, wos::SirenNet& dn, wos::AdamSegs& segs, wos::SirenGrads& dg) {
+  const int D = net->d_in, DO = net->d_out, H = net->hidden, NL = net->n_hidden_layers + 2;
+  segs.n = 2 * NL;
+  size_t at = 0;
+  for (int k = 0; k < 2 * NL; k++) {
+    const int l = k < NL ? k : k - NL;
+    const size_t rows = l == NL - 1 ? (size_t)DO : (size_t)H, count = k < NL ? rows * (l == 0 ? (size_t)D : (size_t)H) : rows;
+    segs.p[k] = const_cast<float*>(k < NL ? net->weights[l] : net->biases[l]);
+    segs.g[k] = g + at;
+    (k < NL ? dg.w[l] : dg.b[l]) = g + at;
+    at += count;
+    segs.end[k] = (int64_t)at;
+  }
+  for (int l = 0; l < NL; l++) {
+    dn.w[l] = net->weights[l];
+    dn.b[l] = net->biases[l];
+  }
+}
+
+// One iteration of either loop on n contiguous rows: wos_siren_fit's launches (both packs, the zero
+// fill, the fit step with `plan`; the loss to state[1]) and wos_adam_step's (the norm to state[2] when
+// clipping; the update, a no-op once state[0] is set).
+static hipError_t fit_run_step(const wos::SirenNet& dn, float* tmp, size_t o_packT, size_t o_zero, size_t o_work,
+                               const float* pts, int64_t n, const float* target, const float* scale,
+                               const wos::SirenFitPlan& plan, const wos::SirenGrads& dg, const wos::AdamSegs& segs,
+                               float* exp_avg, float* exp_avg_sq, const wos::AdamScalars& sc, bool clip, int* state,
+                               hipStream_t st) {
+  float *loss = (float*)state + 1, *norm = (float*)state + 2;
+  hipError_t e;
+  if ((e = wos::launch_siren_pack(dn, tmp, st)) != hipSuccess) return e;
+  if ((e = hipMemsetAsync(tmp + o_zero, 0, (size_t)dn.H * sizeof(float), st)) != hipSuccess) return e;
+  if ((e = wos::launch_siren_pack_transposed(dn, tmp + o_packT, st)) != hipSuccess) return e;
+  if ((e = wos::launch_siren_fit(dn, tmp, tmp + o_packT, tmp + o_zero, pts, n, target, scale, loss, &dg, plan, tmp + o_work,
+                                 st)) != hipSuccess)
+    return e;
+  if (clip && (e = wos::launch_adam_norm(segs, norm, st)) != hipSuccess) return e;
+  return wos::launch_adam_update(segs, exp_avg, exp_avg_sq, sc, clip ? norm : nullptr, state, st);
+}
+
 // One stream-ordered temporary per run: packed | packedT | H zeros | the plan's work (wos_siren_fit's
 // layout), then the batch's points, target and scale, the flat gradients (weights, then biases: the
 // order of exp_avg) and the state words [stop flag, loss, norm], each on a 256-byte boundary.
@@ -804,31 +845,14 @@ int wos_siren_fit_run(const wos_siren_net* net, const float* pool_pts, const flo
   const size_t o_packT = pack_n, o_zero = 2 * pack_n, o_work = o_zero + (size_t)H, o_pts = pad(o_work + plan.total(true)),
                o_t = o_pts + pad(B * D), o_s = o_t + pad(B * DO), o_g = o_s + (pool_scale ? pad(B * DO) : 0),
                o_state = o_g + pad(n_par), total = o_state + 64;
-  // the Adam step's tensors and the fit step's gradient pointers: weights, then biases, one flat buffer
   wos::AdamSegs segs{};
   wos::SirenGrads dg{};
-  segs.n = 2 * NL;
   float* tmp = nullptr;
   if (hipMallocAsync((void**)&tmp, total * sizeof(float), st) != hipSuccess)
     return fail(WOS_E_NOMEM, fn + ": cannot allocate " + std::to_string(total * sizeof(float)) + " bytes of workspace");
-  size_t at = 0;
-  for (int k = 0; k < 2 * NL; k++) {
-    const int l = k < NL ? k : k - NL;
-    const size_t rows = l == NL - 1 ? (size_t)DO : (size_t)H, count = k < NL ? rows * (l == 0 ? (size_t)D : (size_t)H) : rows;
-    float* g = tmp + o_g + at;
-    segs.p[k] = const_cast<float*>(k < NL ? net->weights[l] : net->biases[l]);
-    segs.g[k] = g;
-    (k < NL ? dg.w[l] : dg.b[l]) = g;
-    at += count;
-    segs.end[k] = (int64_t)at;
-  }
-  for (int l = 0; l < NL; l++) {
-    dn.w[l] = net->weights[l];
-    dn.b[l] = net->biases[l];
-  }
+  fit_run_bind(net, tmp + o_g, dn, segs, dg);
   int* state = (int*)(tmp + o_state);
-  float *loss = tmp + o_state + 1, *norm = tmp + o_state + 2;
-  float *b_pts = tmp + o_pts, *b_t = tmp + o_t, *b_s = pool_scale ? tmp + o_s : nullptr;
+  float *b_pts = tmp + o_pts,*b_t = tmp + o_t, *b_s = pool_scale ? tmp + o_s : nullptr;
   const bool clip = opt->max_grad_norm > 0.0;
   int stopped = 0;  // the flag as last read on the host (check_every > 0)
   const auto run = [&]() -> hipError_t {
@@ -841,15 +865,8 @@ int wos_siren_fit_run(const wos_siren_net* net, const float* pool_pts, const flo
       if ((e = wos::launch_fit_run_gather(D, DO, pool_pts, pool_target, pool_scale, n_pool, idx + i * batch, batch, b_pts,
                                           b_t, b_s, state, pending, stop_loss, losses, status, st)) != hipSuccess)
         return e;
-      if ((e = wos::launch_siren_pack(dn, tmp, st)) != hipSuccess) return e;
-      if ((e = hipMemsetAsync(tmp + o_zero, 0, (size_t)H * sizeof(float), st)) != hipSuccess) return e;
-      if ((e = wos::launch_siren_pack_transposed(dn, tmp + o_packT, st)) != hipSuccess) return e;
-      if ((e = wos::launch_siren_fit(dn, tmp, tmp + o_packT, tmp + o_zero, b_pts, batch, b_t, b_s, loss, &dg, plan,
-                                     tmp + o_work, st)) != hipSuccess)
-        return e;
-      if (clip && (e = wos::launch_adam_norm(segs, norm, st)) != hipSuccess) return e;
-      if ((e = wos::launch_adam_update(segs, exp_avg, exp_avg_sq, adam_scalars(*opt, step0 + i + 1), clip ? norm : nullptr,
-                                       state, st)) != hipSuccess)
+      if ((e = fit_run_step(dn, tmp, o_packT, o_zero, o_work, b_pts, batch, b_t, b_s, plan, dg, segs, exp_avg, exp_avg_sq,
+                            adam_scalars(*opt, step0 + i + 1), clip, state, st)) != hipSuccess)
         return e;
       pending = i;
       if (check_every > 0 && (i + 1) % check_every == 0 && i + 1 < n_iters) {
@@ -874,6 +891,112 @@ int wos_siren_fit_run(const wos_siren_net* net, const float* pool_pts, const flo
   if (e != hipSuccess) return fail(WOS_E_DEVICE, fn + ": " + hipGetErrorString(e));
   if (bad != 0)
     return fail(WOS_E_INVALID, fn + ": idx: " + std::to_string(bad) + " indices outside [0, n_pool) were clamped (status[1])");
+  return WOS_OK;
+}
+
+// wos_siren_fit_run without a pool: iteration i's rows offsets[i] .. offsets[i + 1] - 1 are read in
+// place, with wos_siren_fit's plan for that many rows.  One stream-ordered temporary per run: packed |
+// packedT | H zeros | the largest plan's work, then the flat gradients and the state words.  The
+// commit that the gather carries there is a launch of its own here, between two iterations.
+int wos_siren_fit_run_batches(const wos_siren_net* net, const float* pts, const float* target, const float* scale,
+                              const int64_t* offsets, int64_t n_iters, float* exp_avg, float* exp_avg_sq, int64_t step0,
+                              const wos_adam_params* opt, float stop_loss, int32_t check_every, float* losses,
+                              int64_t* status, size_t workspace_bytes, uint32_t flags, int32_t device, void* stream) {
+  const std::string fn = "wos_siren_fit_run_batches";
+  if (int rc = siren_net_check(fn, net)) return rc;
+  const int D = net->d_in, DO = net->d_out, H = net->hidden, L = net->n_hidden_layers, NL = L + 2;
+  if (!(flags & WOS_PTRS_DEVICE)) return fail(WOS_E_INVALID, fn + ": flags: device pointers only (WOS_PTRS_DEVICE)");
+  if (check_every < 0) return fail(WOS_E_INVALID, fn + ": check_every must be >= 0, got " + std::to_string(check_every));
+  if ((flags & WOS_ASYNC) && check_every > 0)
+    return fail(WOS_E_INVALID, fn + ": check_every > 0 synchronises with the host and cannot be WOS_ASYNC");
+  if (n_iters <= 0) return fail(WOS_E_INVALID, fn + ": n_iters must be positive, got " + std::to_string(n_iters));
+  if (n_iters > (int64_t)1 << 40) return fail(WOS_E_INVALID, fn + ": n_iters: too many iterations for one call");
+  if (step0 < 0) return fail(WOS_E_INVALID, fn + ": step0 must be >= 0, got " + std::to_string(step0));
+  if (!pts) return fail(WOS_E_INVALID, fn + ": null pts");
+  if (!target) return fail(WOS_E_INVALID, fn + ": null target");
+  if (!offsets) return fail(WOS_E_INVALID, fn + ": null offsets");
+  if (!losses) return fail(WOS_E_INVALID, fn + ": null losses");
+  if (!status) return fail(WOS_E_INVALID, fn + ": null status");
+  if (!exp_avg) return fail(WOS_E_INVALID, fn + ": null exp_avg");
+  if (!exp_avg_sq) return fail(WOS_E_INVALID, fn + ": null exp_avg_sq");
+  if (std::isnan(stop_loss)) return fail(WOS_E_INVALID, fn + ": stop_loss is NaN (negative: never stop)");
+  if (int rc = adam_params_check(fn, opt)) return rc;
+  if (offsets[0] < 0) return fail(WOS_E_INVALID, fn + ": offsets[0] must be >= 0, got " + std::to_string(offsets[0]));
+  for (int64_t i = 0; i < n_iters; i++) {
+    if (offsets[i + 1] <= offsets[i])
+      return fail(WOS_E_INVALID, fn + ": offsets must be strictly increasing: iteration " + std::to_string(i) + " has no rows (" +
+                                     std::to_string(offsets[i]) + " to " + std::to_string(offsets[i + 1]) +
+                                     "), and its loss is a mean over nothing");
+    if (offsets[i + 1] - offsets[i] > (int64_t)0x7FFFFFFF * wos::kSirenTile)
+      return fail(WOS_E_INVALID, fn + ": offsets: too many points for one step in iteration " + std::to_string(i));
+  }
+  const size_t tile_bytes = wos::siren_fit_stash_floats_per_tile(H, L) * sizeof(float);
+  if (workspace_bytes != 0 && workspace_bytes < tile_bytes)
+    return fail(WOS_E_CAPACITY, fn + ": workspace_bytes " + std::to_string(workspace_bytes) +
+                                    " cannot hold one tile's stash of " + std::to_string(tile_bytes) + " bytes");
+  HIP_TRY(hipSetDevice(device));
+  hipStream_t st = (hipStream_t)stream;
+  wos::SirenNet dn{};
+  dn.d_in = D;
+  dn.d_out = DO;
+  dn.H = H;
+  dn.L = L;
+  dn.omega = net->omega;
+  int cus = 0;
+  HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
+  const int per_cu = std::max<int>(1, (int)(kLdsDynamicMax / wos::siren_fit_tile_lds_bytes(D, H)));
+  const auto plan_of = [&](int64_t i) {  // wos_siren_fit's plan for iteration i's rows
+    return wos::siren_fit_plan(dn, offsets[i + 1] - offsets[i], workspace_bytes ? workspace_bytes : kSirenVjpDefaultStash,
+                               cus * per_cu);
+  };
+  size_t work = 0;
+  for (int64_t i = 0; i < n_iters; i++) work = std::max(work, plan_of(i).total(true));
+  const auto pad = [](size_t floats) { return (floats + 63) / 64 * 64; };
+  const size_t pack_n = wos::siren_pack_floats(H, L);
+  size_t n_par = 0;
+  for (int l = 0; l < NL; l++) n_par += (l == NL - 1 ? (size_t)DO : (size_t)H) * ((l == 0 ? (size_t)D : (size_t)H) + 1);
+  const size_t o_packT = pack_n, o_zero = 2 * pack_n, o_work = o_zero + (size_t)H, o_g = pad(o_work + work),
+               o_state = o_g + pad(n_par), total = o_state + 64;
+  wos::AdamSegs segs{};
+  wos::SirenGrads dg{};
+  float* tmp = nullptr;
+  if (hipMallocAsync((void**)&tmp, total * sizeof(float), st) != hipSuccess)
+    return fail(WOS_E_NOMEM, fn + ": cannot allocate " + std::to_string(total * sizeof(float)) + " bytes of workspace");
+  fit_run_bind(net, tmp + o_g, dn, segs, dg);
+  int* state = (int*)(tmp + o_state);
+  const bool clip = opt->max_grad_norm > 0.0;
+  int stopped = 0;  // the flag as last read on the host (check_every > 0)
+  const auto run = [&]() -> hipError_t {
+    hipError_t e;
+    if ((e = hipMemsetAsync(state, 0, 64 * sizeof(float), st)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(status, 0, 2 * sizeof(int64_t), st)) != hipSuccess) return e;
+    if ((e = hipMemsetD32Async((hipDeviceptr_t)losses, 0x7FC00000, (size_t)n_iters, st)) != hipSuccess) return e;
+    int64_t pending = -1;  // the iteration whose commit has not been enqueued yet
+    for (int64_t i = 0; i < n_iters; i++) {
+      if (pending >= 0 && (e = wos::launch_fit_run_commit(state, pending, stop_loss, losses, status, st)) != hipSuccess)
+        return e;
+      const int64_t row = offsets[i];
+      if ((e = fit_run_step(dn, tmp, o_packT, o_zero, o_work, pts + row * D, offsets[i + 1] - row, target + row * DO,
+                            scale ? scale + row * DO : nullptr, plan_of(i), dg, segs, exp_avg, exp_avg_sq,
+                            adam_scalars(*opt, step0 + i + 1), clip, state, st)) != hipSuccess)
+        return e;
+      pending = i;
+      if (check_every > 0 && (i + 1) % check_every == 0 && i + 1 < n_iters) {
+        if ((e = wos::launch_fit_run_commit(state, i, stop_loss, losses, status, st)) != hipSuccess) return e;
+        pending = -1;
+        if ((e = hipMemcpyAsync(&stopped, state, sizeof(int), hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
+        if ((e = hipStreamSynchronize(st)) != hipSuccess) return e;
+        if (stopped) break;
+      }
+    }
+    if (pending >= 0) return wos::launch_fit_run_commit(state, pending, stop_loss, losses, status, st);
+    return hipSuccess;
+  };
+  hipError_t e = run();
+  const hipError_t e2 = hipFreeAsync(tmp, st);
+  if (e == hipSuccess) e = e2;
+  if (e == hipSuccess && !(flags & WOS_ASYNC)) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) return fail(WOS_E_DEVICE, fn + ": " + hipGetErrorString(e));
   return WOS_OK;
 }
 

@@ -136,7 +136,7 @@ EXPORTS = (
     "wos_siren_eval", "wos_selftest_siren_layer",
     "wos_siren_vjp", "wos_selftest_siren_vjp_layer",
     "wos_siren_fit",
-    "wos_adam_step", "wos_siren_fit_run",
+    "wos_adam_step", "wos_siren_fit_run", "wos_siren_fit_run_batches",
     "wos_set_length_hints", "wos_length_hint_stats", "wos_selftest_hint_key",
 )
 
@@ -261,6 +261,12 @@ def load():
                                     C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(AdamParams),
                                     C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_int32,
                                     C.c_void_p]
+    if hasattr(L, "wos_siren_fit_run_batches"):  # additive within ABI 10, as the length hints above
+        L.wos_siren_fit_run_batches.restype = C.c_int
+        L.wos_siren_fit_run_batches.argtypes = [C.POINTER(SirenNet), C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.POINTER(C.c_int64), C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
+                                                C.POINTER(AdamParams), C.c_float, C.c_int32, C.c_void_p, C.c_void_p,
+                                                C.c_size_t, C.c_uint32, C.c_int32, C.c_void_p]
     L.wos_selftest_siren_vjp_layer.restype = C.c_int
     L.wos_selftest_siren_vjp_layer.argtypes = [C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                                C.c_void_p, C.c_void_p, C.c_int32]

@@ -475,6 +475,16 @@ def advection_fit_loss(network, network_prev, samples, dt, size, network_tilde=N
     attached to network's parameters (wos_amd.siren.fit_loss).  Every no-grad evaluation runs in
     wos_amd.siren.eval.  wrap as in PressureProjector.projection_fit_loss."""
     x = samples.detach()
+    target, scale = _advection_target(network_prev, x, dt, size, network_tilde, wrap)
+    return _siren.fit_loss(network, x, target, scale)
+
+
+def _advection_target(network_prev, x, dt, size, network_tilde, wrap):
+    """The no-grad part of the advection fit at the points x [..., d_in]: (target, scale) as
+    wos_amd.siren.fit takes them (scale None without a wrap).  Every operation is pointwise --
+    siren.eval gives a point the same bits in any batch -- so the rows of one call over the points of
+    many iterations are, bit for bit, the rows of one call per iteration: advection_fit_loss and
+    fit_advection both go through here."""
     with torch.no_grad():
         def query(net, pts):
             u = _siren.eval(net, pts)
@@ -488,4 +498,96 @@ def advection_fit_loss(network, network_prev, samples, dt, size, network_tilde=N
         if wrap is not None:
             scale, offset = _diagonal(wrap, x, target.shape[-1])
             target = target - offset
-    return _siren.fit_loss(network, x, target, scale)
+    return target, scale
+
+
+def fit_advection(network, network_prev, dt, size, n_iters, *, n_samples=None, samples=None, network_tilde=None,
+                  wrap=None, keep=None, state=None, generator=None, early_stop=None, iters_per_call=256, lr=1e-4):
+    """The whole training loop of _advect_velocity (n_iters iterations of advection_fit_loss, backward
+    and Adam: src/2d/models/model_split.py:88-120 in _training_loop, base.py:130-152; the 3D twin
+    src/3d/models/model_split.py:89-122) on the device, through wos_amd.siren.fit_run_batches.
+    network_prev and network_tilde are frozen for the loop, so the points, backtracked positions,
+    targets and wrap factors of a block of k <= iters_per_call iterations are computed together, all
+    rows at once, exactly as advection_fit_loss computes them per iteration; an iteration is then fit
+    step and Adam step on its own rows.  Iteration i is, bit for bit in the loss, every parameter and
+    both moments, advection_fit_loss's target for that iteration's points followed by siren.fit and
+    siren.adam_step.  `network` IS UPDATED IN PLACE.
+    Points: with n_samples, one torch.rand(n_samples, d_in) per iteration on the network's device,
+    component c scaled as sample_random_2D does, x_c * (size[2c+1] - size[2c]) + size[2c] -- the
+    generator consumption of the Python loop, so a generator seeded alike yields the same points;
+    otherwise `samples` is a callable samples(k) -> [k, n, d_in] (the `uniform` and `random+uniform`
+    patterns).  Exactly one of the two.
+    keep: None, or a function of points [m, d_in] returning a bool mask [m] -- for karman
+    lambda x: sdf(x) > 0 with a MeshSDF or an analytic circle, the reference's
+    samples = samples[dist > 0] (base.py:239-241).  It is applied to the flattened block; rows keep
+    their order, so an iteration's points stay contiguous and in draw order, and its loss is the mean
+    over its own count.  The counts are read on the host: the one synchronisation per block.  An
+    iteration left without a point raises ValueError, naming the iteration, before the block is
+    enqueued: network and state are then as the previous block left them.
+    wrap(x, u_net) -> u as in advection_fit_loss: pointwise and diagonal-affine in u_net.  A wrap whose
+    value at a point depends on the rest of the batch (the 3D smoke branch's per-call np.random draw,
+    the jpipe branch's norm over the batch) is not covered by the block form: a block hands it the
+    points of k iterations at once.  iters_per_call=1 hands such a wrap exactly one iteration's points.
+    state: a wos_amd.siren.AdamState to continue (None: a fresh one with `lr`).  early_stop as in
+    PressureProjector.fit_projection: None, or the loss at or below which the loop stops after that
+    iteration's update (True: the reference's 1.1e-10); one host read per block, the losses from the
+    stop on are NaN, no further block is drawn.  A block of 256 iterations of 16384 points holds its
+    points, backtracked points, two or three network values, target and scale: about 0.3 GB at its peak.
+    Returns (losses [n_iters], state)."""
+    n_iters, per_call = int(n_iters), int(iters_per_call)
+    if n_iters < 1 or per_call < 1:
+        raise ValueError(f"fit_advection: n_iters and iters_per_call must be positive, got {n_iters}, {per_call}")
+    if (n_samples is None) == (samples is None):
+        raise ValueError("fit_advection: give exactly one of n_samples (torch.rand points per iteration) and samples "
+                         "(a callable samples(k) -> [k, n, d_in])")
+    if n_samples is not None and int(n_samples) < 1:
+        raise ValueError(f"fit_advection: n_samples must be positive, got {n_samples}")
+    p = _siren.pack(network)
+    d, dev = p.d_in, p.weights[0].device
+    if len(size) != 2 * d:
+        raise ValueError(f"fit_advection: size must hold {2 * d} bounds for {d} coordinates, got {len(size)}")
+    if state is None:
+        state = _siren.AdamState(network, lr=lr)
+    stop = None if early_stop is None or early_stop is False else (1.1e-10 if early_stop is True else float(early_stop))
+    losses = []
+    for first in range(0, n_iters, per_call):
+        k = min(per_call, n_iters - first)
+        if samples is None:
+            x = torch.stack([torch.rand(int(n_samples), d, device=dev, generator=generator) for _ in range(k)])
+            for c in range(d):
+                x[..., c] = x[..., c] * (size[2 * c + 1] - size[2 * c]) + size[2 * c]
+        else:
+            x = samples(k)
+            if x.dim() != 3 or x.shape[0] != k or x.shape[1] < 1 or x.shape[2] != d:
+                raise ValueError(f"fit_advection: samples({k}) must return [{k}, n, {d}], got shape {tuple(x.shape)}")
+            x = x.detach()
+        n = int(x.shape[1])
+        x = x.reshape(k * n, d)
+        if keep is None:
+            counts = [n] * k
+        else:
+            mask = keep(x)
+            if mask.dtype != torch.bool or tuple(mask.shape) != (k * n,):
+                raise ValueError(f"fit_advection: keep must return a bool mask of shape {(k * n,)}, got {mask.dtype} "
+                                 f"{tuple(mask.shape)}")
+            counts = mask.reshape(k, n).sum(dim=1).tolist()  # the block's one host synchronisation
+            for i, c in enumerate(counts):
+                if c < 1:
+                    raise ValueError(f"fit_advection: keep left iteration {first + i} without a point (its loss is a mean "
+                                     f"over nothing); the network and the state are as the {first} iterations before this "
+                                     f"block left them")
+            # the kept rows in their order; the size is known, so this does not wait for the device again
+            x = x[torch.nonzero_static(mask, size=sum(counts)).squeeze(1)]
+        target, scale = _advection_target(network_prev, x, dt, size, network_tilde, wrap)
+        block, status = _siren.fit_run_batches(network, state, x, target, scale, counts, stop_loss=stop)
+        losses.append(block)
+        if stop is None:
+            continue
+        # as in fit_projection: a stop at the block's last iteration leaves status[0] == k, and the last applied
+        # loss tells, by the device's own test
+        applied = int(status[0])
+        if applied < k or float(block[applied - 1]) <= float(np.float32(stop)):
+            if first + k < n_iters:
+                losses.append(torch.full((n_iters - first - k,), float("nan"), dtype=block.dtype, device=block.device))
+            break
+    return torch.cat(losses), state

@@ -13,7 +13,9 @@ one value-only pass (wos_siren_fit, csrc/wos_siren_fit.hip) -- fit_loss() the sa
 scalar, diagonal_wrap() the (scale, offset) form of query_velocity's masks that fit() takes.
 adam_step() is the loop's optimiser -- clip_grad_norm_ and torch.optim.Adam.step() in one call on an
 AdamState (wos_adam_step, csrc/wos_siren_train.hip) -- and fit_run() K iterations of gather, fit()
-and adam_step() on a fixed pool from one call (wos_siren_fit_run).
+and adam_step() on a fixed pool from one call (wos_siren_fit_run); fit_run_batches() K iterations of
+fit() and adam_step() on fresh rows of another count every iteration, read in place
+(wos_siren_fit_run_batches).
 """
 import collections
 import ctypes as C
@@ -740,6 +742,92 @@ def fit_run(net, state, pool_x, pool_target, pool_scale, idx, *, stop_loss=None,
             torch.cuda.current_stream(dev).wait_stream(ts)
         state.step += int(status[0].item())
     return losses, status
+
+
+def fit_run_batches(net, state, x, target, scale, counts, *, stop_loss=None, check_every=0, stream=None,
+                    workspace_bytes=None):
+    """K iterations of fit() -> adam_step() in one call (wos_siren_fit_run_batches) for a fit whose
+    points are new every iteration and of another count every iteration (the advection fit, with the
+    samples inside an obstacle dropped): x [total, d_in], target and scale [total, d_out] (scale may be
+    None) hold the rows of all iterations one after the other, counts the K positive row counts, which
+    sum to total.  Iteration i reads its counts[i] rows in place, as the slice x[o:o + counts[i]] with
+    o = sum(counts[:i]), and equals, bit for bit in the loss, every parameter and both moments,
+    fit(net, x[o:o + n], target[o:o + n], scale[o:o + n]) and adam_step(net, grads, state): the loss is
+    the mean over that iteration's own rows.  THE NETWORK'S OWN TENSORS ARE UPDATED IN PLACE, as are
+    the state's moments.  CUDA tensors only; the offsets are built on the host.  Returns
+    (losses [K] float32, status [2] int64) as device tensors: status[0] the iterations applied,
+    status[1] always 0.  stop_loss, check_every, `stream`, workspace_bytes and state.step as in
+    fit_run()."""
+    import torch
+    p = net if isinstance(net, PackedSiren) else pack(net)
+    if len(x.shape) != 2 or x.shape[1] != p.d_in or x.shape[0] < 1:
+        raise ValueError(f"siren.fit_run_batches: x must be [total, {p.d_in}], got shape {tuple(x.shape)}")
+    total = int(x.shape[0])
+    offsets = _batch_offsets("siren.fit_run_batches", counts, total)
+    if not (_is_torch(x) and x.is_cuda):
+        raise ValueError("siren.fit_run_batches: x must be a CUDA tensor (device pointers only)")
+    dev = x.device
+
+    def operand(name, a):
+        if not _is_torch(a) or a.device != dev:
+            raise ValueError(f"siren.fit_run_batches: {name} must be a tensor on {dev}, like x")
+        if tuple(a.shape) != (total, p.d_out):
+            raise ValueError(f"siren.fit_run_batches: {name} must have shape {(total, p.d_out)}, got {tuple(a.shape)}")
+        return a.detach().to(torch.float32).contiguous()
+    xs = x.detach().to(torch.float32).contiguous()
+    t = operand("target", target)
+    sc = None if scale is None else operand("scale", scale)
+    K = len(offsets) - 1
+    tensors = p.weights + p.biases
+    if any(w.device != dev for w in tensors) or state.exp_avg.device != dev:
+        raise ValueError(f"siren.fit_run_batches: the points are on {dev}, the network on {tensors[0].device}, the state on "
+                         f"{state.exp_avg.device}")
+    if state.counts != [int(w.numel()) for w in tensors]:
+        raise ValueError("siren.fit_run_batches: state was made for a network of another shape")
+    ws = 0 if workspace_bytes is None else int(workspace_bytes)
+    if ws < 0:
+        raise ValueError(f"siren.fit_run_batches: workspace_bytes must be >= 0, got {workspace_bytes}")
+    check_every = int(check_every)
+    if check_every < 0:
+        raise ValueError(f"siren.fit_run_batches: check_every must be >= 0, got {check_every}")
+    if stop_loss is not None and not float(stop_loss) >= 0.0:
+        raise ValueError(f"siren.fit_run_batches: stop_loss must be None or >= 0, got {stop_loss}")
+    losses = torch.empty(K, dtype=torch.float32, device=dev)
+    status = torch.zeros(2, dtype=torch.int64, device=dev)  # zeros: a call refused before any device work applied nothing
+    held = [xs, t, losses, status, state.exp_avg, state.exp_avg_sq] + ([] if sc is None else [sc]) + tensors
+    s = _stream_of(stream, held, dev)
+    st, keep = _net_struct(p, [w.data_ptr() for w in p.weights], [b.data_ptr() for b in p.biases])
+    opt = state.params()
+    flags = _lib.WOS_PTRS_DEVICE | (0 if check_every > 0 else _lib.WOS_ASYNC)
+    rc = _lib.load().wos_siren_fit_run_batches(C.byref(st), xs.data_ptr(), t.data_ptr(), None if sc is None else sc.data_ptr(),
+                                               (C.c_int64 * (K + 1))(*offsets), K, state.exp_avg.data_ptr(),
+                                               state.exp_avg_sq.data_ptr(), state.step, C.byref(opt),
+                                               -1.0 if stop_loss is None else float(stop_loss), check_every,
+                                               losses.data_ptr(), status.data_ptr(), ws, flags, dev.index or 0, s)
+    del keep, held
+    check(rc, "wos_siren_fit_run_batches")
+    if stop_loss is None:
+        state.step += K
+    else:
+        if stream is not None:  # status was written on `stream`: torch's current stream must see it
+            ts = stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.ExternalStream(int(stream), device=dev)
+            torch.cuda.current_stream(dev).wait_stream(ts)
+        state.step += int(status[0].item())
+    return losses, status
+
+
+def _batch_offsets(who, counts, total):
+    """The K + 1 row offsets of K positive counts that sum to `total`, as Python ints."""
+    offsets = [0]
+    for i, c in enumerate(counts):
+        if int(c) != c or int(c) <= 0:
+            raise ValueError(f"{who}: counts[{i}] must be a positive int (a mean over nothing), got {c!r}")
+        offsets.append(offsets[-1] + int(c))
+    if len(offsets) < 2:
+        raise ValueError(f"{who}: counts is empty (at least one iteration)")
+    if offsets[-1] != total:
+        raise ValueError(f"{who}: counts sum to {offsets[-1]}, the tensors hold {total} rows")
+    return offsets
 
 
 _probes = {}  # diagonal_wrap's probe of the last (shape, dtype, device)
