@@ -4,7 +4,8 @@
 //   wos_capi_solve.cpp   the solve pipeline (wos_solve*)
 //   wos_capi_tape.cpp    the walk tape, its index, replay and adjoint
 //   wos_capi_bvc.cpp     boundary value caching
-//   wos_capi_probes.cpp  the self-test probes and the fused SIREN entry point
+//   wos_capi_probes.cpp  the self-test probes of the solve's kernels
+//   wos_capi_siren.cpp   the fused SIREN: forward, backward, fit step, Adam step, the two fit loops, its probes
 //
 // Device memory lives at three levels, sized for a time-stepper that builds a
 // new Scene(sceneConfig, div) for every projection (model_split.py:191):

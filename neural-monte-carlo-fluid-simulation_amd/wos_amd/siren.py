@@ -91,11 +91,41 @@ def pack(net, omega=30.0):
     return PackedSiren(d_in, d_out, hidden, n_hidden, float(omega), weights, biases)
 
 
-def _net_struct(p, ptrs_w, ptrs_b):
+def _ptr_array(arrays):
+    """The addresses of torch tensors or numpy arrays as a C array of pointers."""
+    return (C.c_void_p * len(arrays))(*[a.data_ptr() if _is_torch(a) else a.ctypes.data for a in arrays])
+
+
+def _net_struct(p, host=None):
+    """(wos_siren_net, what keeps its pointers alive) over the network's own tensors, or over `host`,
+    numpy arrays in their place."""
     n = p.n_hidden_layers + 2
-    w = (C.c_void_p * n)(*ptrs_w)
-    b = (C.c_void_p * n)(*ptrs_b)
-    return _lib.SirenNet(p.d_in, p.d_out, p.hidden, p.n_hidden_layers, p.omega, w, b), (w, b)
+    arrays = p.weights + p.biases if host is None else host
+    w, b = _ptr_array(arrays[:n]), _ptr_array(arrays[n:])
+    return _lib.SirenNet(p.d_in, p.d_out, p.hidden, p.n_hidden_layers, p.omega, w, b), (w, b, host)
+
+
+def _host_call(p, stream):
+    """What a host-pointer call takes: (host, device, stream), the network's tensors staged as numpy
+    arrays from wherever they live, the device ordinal to run on and the raw stream."""
+    host = [np.ascontiguousarray(t.cpu().numpy()) for t in p.weights + p.biases]
+    dev = p.weights[0].device.index or 0 if p.weights[0].is_cuda else 0
+    return host, dev, stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
+
+
+def _operand(who, name, a, shape, on_gpu, device, like="the points"):
+    """One array operand of `who` as a contiguous float32 array of `shape` and of the points' kind: a
+    tensor on `device` (on_gpu), else numpy."""
+    if tuple(np.shape(a)) != shape:
+        raise ValueError(f"siren.{who}: {name} must have shape {shape}, got {tuple(np.shape(a))}")
+    if on_gpu:
+        import torch
+        if not _is_torch(a) or a.device != device:
+            raise ValueError(f"siren.{who}: {name} must be a tensor on {device}, like {like}")
+        return a.detach().to(torch.float32).contiguous()
+    if _is_torch(a):
+        a = a.detach().cpu().numpy()
+    return np.ascontiguousarray(a, dtype=np.float32)
 
 
 def eval(net, x, *, value=True, jacobian=False, divergence=False, stream=None):  # noqa: A001 (the module's verb)
@@ -128,18 +158,8 @@ def eval(net, x, *, value=True, jacobian=False, divergence=False, stream=None): 
         out = [torch.empty((n,) + tails[k], dtype=torch.float32, device=xs.device) if want[k] else None
                for k in range(3)]
         if n > 0:
-            cur = torch.cuda.current_stream(xs.device)
-            held = [xs] + [t for t in out if t is not None] + p.weights + p.biases
-            if stream is None:
-                s = cur.cuda_stream
-            else:
-                ts = stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.ExternalStream(int(stream),
-                                                                                                    device=xs.device)
-                s = ts.cuda_stream
-                ts.wait_stream(cur)  # points, weights and fresh outputs belong to torch's current stream
-                for t in held:
-                    t.record_stream(ts)  # ... and are used on `stream`: the allocator must wait for it
-            st, keep = _net_struct(p, [t.data_ptr() for t in p.weights], [t.data_ptr() for t in p.biases])
+            s = _stream_of(stream, [xs] + [t for t in out if t is not None] + p.weights + p.biases, xs.device)
+            st, keep = _net_struct(p)
             ptr = [t.data_ptr() if t is not None else None for t in out]
             check(L.wos_siren_eval(C.byref(st), xs.data_ptr(), n, *ptr, _lib.WOS_PTRS_DEVICE | _lib.WOS_ASYNC,
                                    xs.device.index or 0, s), "wos_siren_eval")
@@ -156,14 +176,11 @@ def eval(net, x, *, value=True, jacobian=False, divergence=False, stream=None): 
         n = xs.shape[0]
         out = [np.empty((n,) + tails[k], np.float32) if want[k] else None for k in range(3)]
         if n > 0:
-            host = [np.ascontiguousarray(t.cpu().numpy()) for t in p.weights + p.biases]
-            nl = p.n_hidden_layers + 2
-            st, keep = _net_struct(p, [a.ctypes.data for a in host[:nl]], [a.ctypes.data for a in host[nl:]])
+            host, dev, s = _host_call(p, stream)
+            st, keep = _net_struct(p, host)
             ptr = [a.ctypes.data if a is not None else None for a in out]
-            dev = p.weights[0].device.index or 0 if p.weights[0].is_cuda else 0
-            s = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
             check(L.wos_siren_eval(C.byref(st), xs.ctypes.data, n, *ptr, 0, dev, s), "wos_siren_eval")
-            del keep, host
+            del keep
         res = [a.reshape(lead + tails[k]) for k, a in enumerate(out) if a is not None]
     return res[0] if len(res) == 1 else tuple(res)
 
@@ -181,22 +198,6 @@ def selftest_layer(W, b, X, device=0):
     check(_lib.load().wos_selftest_siren_layer(W.shape[0], X.shape[1] - 1, X.shape[0], W.ctypes.data, b.ctypes.data,
                                                X.ctypes.data, Z.ctypes.data, device), "wos_selftest_siren_layer")
     return Z
-
-
-def _cotangent(name, g, shape, like_torch, device):
-    """One cotangent as a contiguous float32 [n, ...] array of the points' kind, or None."""
-    if g is None:
-        return None
-    if tuple(g.shape) != shape:
-        raise ValueError(f"siren.vjp: {name} must have shape {shape}, got {tuple(g.shape)}")
-    if like_torch:
-        import torch
-        if not _is_torch(g) or g.device != device:
-            raise ValueError(f"siren.vjp: {name} must be a tensor on {device}, like the points")
-        return g.detach().to(torch.float32).contiguous()
-    if _is_torch(g):
-        g = g.detach().cpu().numpy()
-    return np.ascontiguousarray(g, dtype=np.float32)
 
 
 def vjp(net, x, *, grad_value=None, grad_jacobian=None, grad_divergence=None, stream=None, workspace_bytes=None):
@@ -219,7 +220,7 @@ def vjp(net, x, *, grad_value=None, grad_jacobian=None, grad_divergence=None, st
     tails = ((p.d_out,), (p.d_out, p.d_in), ())
     names = ("grad_value", "grad_jacobian", "grad_divergence")
     on_gpu = _is_torch(x) and x.is_cuda
-    g = [_cotangent(names[k], c, lead + tails[k], on_gpu, x.device if on_gpu else None)
+    g = [None if c is None else _operand("vjp", names[k], c, lead + tails[k], on_gpu, x.device if on_gpu else None)
          for k, c in enumerate((grad_value, grad_jacobian, grad_divergence))]
     ws = 0 if workspace_bytes is None else int(workspace_bytes)
     if ws < 0:
@@ -231,43 +232,25 @@ def vjp(net, x, *, grad_value=None, grad_jacobian=None, grad_divergence=None, st
         if any(t.device != x.device for t in p.weights + p.biases):
             raise ValueError(f"siren.vjp: the points are on {x.device}, the network on {p.weights[0].device}")
         xs = x.detach().to(torch.float32).contiguous().reshape(-1, p.d_in)
-        n = xs.shape[0]
         gw = [torch.empty_like(t) for t in p.weights]
         gb = [torch.empty_like(t) for t in p.biases]
-        cur = torch.cuda.current_stream(xs.device)
-        held = [xs] + [t for t in g if t is not None] + gw + gb + p.weights + p.biases
-        if stream is None:
-            s = cur.cuda_stream
-        else:
-            ts = stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.ExternalStream(int(stream),
-                                                                                                device=xs.device)
-            s = ts.cuda_stream
-            ts.wait_stream(cur)  # points, cotangents, weights and fresh outputs belong to torch's current stream
-            for t in held:
-                t.record_stream(ts)  # ... and are used on `stream`: the allocator must wait for it
-        st, keep = _net_struct(p, [t.data_ptr() for t in p.weights], [t.data_ptr() for t in p.biases])
-        pw = (C.c_void_p * nl)(*[t.data_ptr() for t in gw])
-        pb = (C.c_void_p * nl)(*[t.data_ptr() for t in gb])
-        check(L.wos_siren_vjp(C.byref(st), xs.data_ptr(), n, *[None if t is None else t.data_ptr() for t in g],
-                              pw, pb, ws, _lib.WOS_PTRS_DEVICE | _lib.WOS_ASYNC, xs.device.index or 0, s),
-              "wos_siren_vjp")
-        del keep, held
+        s = _stream_of(stream, [xs] + [t for t in g if t is not None] + gw + gb + p.weights + p.biases, xs.device)
+        st, keep = _net_struct(p)
+        check(L.wos_siren_vjp(C.byref(st), xs.data_ptr(), xs.shape[0], *[None if t is None else t.data_ptr() for t in g],
+                              _ptr_array(gw), _ptr_array(gb), ws, _lib.WOS_PTRS_DEVICE | _lib.WOS_ASYNC,
+                              xs.device.index or 0, s), "wos_siren_vjp")
+        del keep
         return gw, gb
     if _is_torch(x):
         x = x.detach().cpu().numpy()
     xs = np.ascontiguousarray(x, dtype=np.float32).reshape(-1, p.d_in)
-    n = xs.shape[0]
-    host = [np.ascontiguousarray(t.cpu().numpy()) for t in p.weights + p.biases]
-    st, keep = _net_struct(p, [a.ctypes.data for a in host[:nl]], [a.ctypes.data for a in host[nl:]])
+    host, dev, s = _host_call(p, stream)
+    st, keep = _net_struct(p, host)
     gw = [np.empty(a.shape, np.float32) for a in host[:nl]]
     gb = [np.empty(a.shape, np.float32) for a in host[nl:]]
-    pw = (C.c_void_p * nl)(*[a.ctypes.data for a in gw])
-    pb = (C.c_void_p * nl)(*[a.ctypes.data for a in gb])
-    dev = p.weights[0].device.index or 0 if p.weights[0].is_cuda else 0
-    s = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
-    check(L.wos_siren_vjp(C.byref(st), xs.ctypes.data, n, *[None if a is None else a.ctypes.data for a in g],
-                          pw, pb, ws, 0, dev, s), "wos_siren_vjp")
-    del keep, host
+    check(L.wos_siren_vjp(C.byref(st), xs.ctypes.data, xs.shape[0], *[None if a is None else a.ctypes.data for a in g],
+                          _ptr_array(gw), _ptr_array(gb), ws, 0, dev, s), "wos_siren_vjp")
+    del keep
     return gw, gb
 
 
@@ -389,20 +372,6 @@ def divergence_with_wrap(x, u_net, J, wrap, create_graph=False):
     return div if create_graph else div.detach()
 
 
-def _fit_operand(name, a, shape, like_torch, device):
-    """target / scale as a contiguous float32 [n, d_out] array of the points' kind."""
-    if tuple(a.shape) != shape:
-        raise ValueError(f"siren.fit: {name} must have shape {shape}, got {tuple(a.shape)}")
-    if like_torch:
-        import torch
-        if not _is_torch(a) or a.device != device:
-            raise ValueError(f"siren.fit: {name} must be a tensor on {device}, like the points")
-        return a.detach().to(torch.float32).contiguous()
-    if _is_torch(a):
-        a = a.detach().cpu().numpy()
-    return np.ascontiguousarray(a, dtype=np.float32)
-
-
 fit_calls = collections.Counter()  # "loss_only" / "grads": how many times fit() went down either path
 
 
@@ -425,8 +394,8 @@ def fit(net, x, target, scale=None, *, grads=True, stream=None, workspace_bytes=
     dev = x.device if on_gpu else None
     if target is None:
         raise ValueError("siren.fit: target is None")
-    t = _fit_operand("target", target, lead + (p.d_out,), on_gpu, dev)
-    sc = None if scale is None else _fit_operand("scale", scale, lead + (p.d_out,), on_gpu, dev)
+    t = _operand("fit", "target", target, lead + (p.d_out,), on_gpu, dev)
+    sc = None if scale is None else _operand("fit", "scale", scale, lead + (p.d_out,), on_gpu, dev)
     n = 1
     for k in lead:
         n *= int(k)
@@ -452,40 +421,26 @@ def fit(net, x, target, scale=None, *, grads=True, stream=None, workspace_bytes=
                 views.append(flat[at:at + a.numel()].view(a.shape))
                 at += a.numel()
             gw, gb = views[:nl], views[nl:]
-        cur = torch.cuda.current_stream(xs.device)
         held = [xs, t, loss] + ([] if sc is None else [sc]) + ([] if flat is None else [flat]) + p.weights + p.biases
-        if stream is None:
-            s = cur.cuda_stream
-        else:
-            ts = stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.ExternalStream(int(stream),
-                                                                                                device=xs.device)
-            s = ts.cuda_stream
-            ts.wait_stream(cur)  # points, target, weights and fresh outputs belong to torch's current stream
-            for a in held:
-                a.record_stream(ts)  # ... and are used on `stream`: the allocator must wait for it
-        st, keep = _net_struct(p, [w.data_ptr() for w in p.weights], [b.data_ptr() for b in p.biases])
-        pw = (C.c_void_p * nl)(*[a.data_ptr() for a in gw]) if grads else None
-        pb = (C.c_void_p * nl)(*[a.data_ptr() for a in gb]) if grads else None
+        s = _stream_of(stream, held, xs.device)
+        st, keep = _net_struct(p)
         check(L.wos_siren_fit(C.byref(st), xs.data_ptr(), n, t.data_ptr(), None if sc is None else sc.data_ptr(),
-                              loss.data_ptr(), pw, pb, ws, _lib.WOS_PTRS_DEVICE | _lib.WOS_ASYNC,
-                              xs.device.index or 0, s), "wos_siren_fit")
-        del keep, held
+                              loss.data_ptr(), _ptr_array(gw) if grads else None, _ptr_array(gb) if grads else None, ws,
+                              _lib.WOS_PTRS_DEVICE | _lib.WOS_ASYNC, xs.device.index or 0, s), "wos_siren_fit")
+        del keep
         return (loss, gw, gb) if grads else loss
     if _is_torch(x):
         x = x.detach().cpu().numpy()
     xs = np.ascontiguousarray(x, dtype=np.float32).reshape(-1, p.d_in)
-    host = [np.ascontiguousarray(w.cpu().numpy()) for w in p.weights + p.biases]
-    st, keep = _net_struct(p, [a.ctypes.data for a in host[:nl]], [a.ctypes.data for a in host[nl:]])
+    host, dev, s = _host_call(p, stream)
+    st, keep = _net_struct(p, host)
     loss = np.empty((), np.float32)
     gw = [np.empty(a.shape, np.float32) for a in host[:nl]] if grads else []
     gb = [np.empty(a.shape, np.float32) for a in host[nl:]] if grads else []
-    pw = (C.c_void_p * nl)(*[a.ctypes.data for a in gw]) if grads else None
-    pb = (C.c_void_p * nl)(*[a.ctypes.data for a in gb]) if grads else None
-    dev = p.weights[0].device.index or 0 if p.weights[0].is_cuda else 0
-    s = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
     check(L.wos_siren_fit(C.byref(st), xs.ctypes.data, n, t.ctypes.data, None if sc is None else sc.ctypes.data,
-                          loss.ctypes.data, pw, pb, ws, 0, dev, s), "wos_siren_fit")
-    del keep, host
+                          loss.ctypes.data, _ptr_array(gw) if grads else None, _ptr_array(gb) if grads else None, ws, 0,
+                          dev, s), "wos_siren_fit")
+    del keep
     return (loss[()], gw, gb) if grads else loss[()]
 
 
@@ -634,24 +589,20 @@ def adam_step(net, grads, state, *, stream=None):
         norm = torch.empty((), dtype=torch.float32, device=dev) if state.clips else None
         held = g + tensors + [state.exp_avg, state.exp_avg_sq] + ([] if norm is None else [norm])
         s = _stream_of(stream, held, dev)
-        pp = (C.c_void_p * n)(*[t.data_ptr() for t in tensors])
-        pg = (C.c_void_p * n)(*[a.data_ptr() for a in g])
-        check(L.wos_adam_step(n, counts, pp, pg, state.exp_avg.data_ptr(), state.exp_avg_sq.data_ptr(), state.step + 1,
-                              C.byref(opt), None if norm is None else norm.data_ptr(),
-                              _lib.WOS_PTRS_DEVICE | _lib.WOS_ASYNC, dev.index or 0, s), "wos_adam_step")
-        del held
+        check(L.wos_adam_step(n, counts, _ptr_array(tensors), _ptr_array(g), state.exp_avg.data_ptr(),
+                              state.exp_avg_sq.data_ptr(), state.step + 1, C.byref(opt),
+                              None if norm is None else norm.data_ptr(), _lib.WOS_PTRS_DEVICE | _lib.WOS_ASYNC,
+                              dev.index or 0, s), "wos_adam_step")
         state.step += 1
         return norm
     g = [np.ascontiguousarray(a.detach().cpu().numpy() if _is_torch(a) else a, dtype=np.float32) for a in g]
     host = [np.array(t.cpu().numpy(), dtype=np.float32, order="C") for t in tensors]  # copies: the net is left alone
     m, v = state.exp_avg.cpu().numpy().copy(), state.exp_avg_sq.cpu().numpy().copy()
     norm = np.empty((), np.float32) if state.clips else None
-    pp = (C.c_void_p * n)(*[a.ctypes.data for a in host])
-    pg = (C.c_void_p * n)(*[a.ctypes.data for a in g])
     dev = tensors[0].device.index or 0 if tensors[0].is_cuda else 0
     s = stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
-    check(L.wos_adam_step(n, counts, pp, pg, m.ctypes.data, v.ctypes.data, state.step + 1, C.byref(opt),
-                          None if norm is None else norm.ctypes.data, 0, dev, s), "wos_adam_step")
+    check(L.wos_adam_step(n, counts, _ptr_array(host), _ptr_array(g), m.ctypes.data, v.ctypes.data, state.step + 1,
+                          C.byref(opt), None if norm is None else norm.ctypes.data, 0, dev, s), "wos_adam_step")
     import torch
     state.exp_avg.copy_(torch.from_numpy(m))
     state.exp_avg_sq.copy_(torch.from_numpy(v))
@@ -687,61 +638,70 @@ def fit_run(net, state, pool_x, pool_target, pool_scale, idx, *, stop_loss=None,
     if pool_x.dim() != 2 or pool_x.shape[1] != p.d_in or pool_x.shape[0] < 1:
         raise ValueError(f"siren.fit_run: pool_x must be [n_pool, {p.d_in}], got shape {tuple(pool_x.shape)}")
     n_pool = int(pool_x.shape[0])
-
-    def operand(name, a):
-        if not _is_torch(a) or a.device != dev:
-            raise ValueError(f"siren.fit_run: {name} must be a tensor on {dev}, like pool_x")
-        if tuple(a.shape) != (n_pool, p.d_out):
-            raise ValueError(f"siren.fit_run: {name} must have shape {(n_pool, p.d_out)}, got {tuple(a.shape)}")
-        return a.detach().to(torch.float32).contiguous()
     xs = pool_x.detach().to(torch.float32).contiguous()
-    t = operand("pool_target", pool_target)
-    sc = None if pool_scale is None else operand("pool_scale", pool_scale)
+    t = _operand("fit_run", "pool_target", pool_target, (n_pool, p.d_out), True, dev, "pool_x")
+    sc = None if pool_scale is None else _operand("fit_run", "pool_scale", pool_scale, (n_pool, p.d_out), True, dev, "pool_x")
     if not _is_torch(idx) or idx.device != dev or idx.dtype != torch.int64 or idx.dim() != 2 or not idx.is_contiguous() \
             or idx.shape[0] < 1 or idx.shape[1] < 1:
         raise ValueError(f"siren.fit_run: idx must be a contiguous int64 tensor [K, batch] on {dev}")
+    K, batch = int(idx.shape[0]), int(idx.shape[1])
+
+    def call(L, net, *rest):
+        return L.wos_siren_fit_run(net, xs.data_ptr(), t.data_ptr(), None if sc is None else sc.data_ptr(), n_pool,
+                                   idx.data_ptr(), K, batch, *rest)
+    return _run_loop("fit_run", "pool is", p, state, dev, [xs, t, idx] + ([] if sc is None else [sc]), K, call, stop_loss,
+                     check_every, stream, workspace_bytes, clamps=True)
+
+
+def _run_loop(who, what, p, state, dev, inputs, K, call, stop_loss, check_every, stream, workspace_bytes, clamps=False):
+    """What fit_run() and fit_run_batches() share once their inputs are device tensors on `dev`: the
+    checks of the network, the state and the loop's settings, the outputs, the stream discipline, the
+    call -- call(library, net, *the arguments from exp_avg on) -- and the state's step after it."""
+    import torch
     tensors = p.weights + p.biases
     if any(w.device != dev for w in tensors) or state.exp_avg.device != dev:
-        raise ValueError(f"siren.fit_run: the pool is on {dev}, the network on {tensors[0].device}, the state on "
+        raise ValueError(f"siren.{who}: the {what} on {dev}, the network on {tensors[0].device}, the state on "
                          f"{state.exp_avg.device}")
     if state.counts != [int(w.numel()) for w in tensors]:
-        raise ValueError("siren.fit_run: state was made for a network of another shape")
+        raise ValueError(f"siren.{who}: state was made for a network of another shape")
     ws = 0 if workspace_bytes is None else int(workspace_bytes)
     if ws < 0:
-        raise ValueError(f"siren.fit_run: workspace_bytes must be >= 0, got {workspace_bytes}")
+        raise ValueError(f"siren.{who}: workspace_bytes must be >= 0, got {workspace_bytes}")
     check_every = int(check_every)
     if check_every < 0:
-        raise ValueError(f"siren.fit_run: check_every must be >= 0, got {check_every}")
+        raise ValueError(f"siren.{who}: check_every must be >= 0, got {check_every}")
     if stop_loss is not None and not float(stop_loss) >= 0.0:
-        raise ValueError(f"siren.fit_run: stop_loss must be None or >= 0, got {stop_loss}")
-    K, batch = int(idx.shape[0]), int(idx.shape[1])
+        raise ValueError(f"siren.{who}: stop_loss must be None or >= 0, got {stop_loss}")
     losses = torch.empty(K, dtype=torch.float32, device=dev)
     status = torch.zeros(2, dtype=torch.int64, device=dev)  # zeros: a call refused before any device work applied nothing
-    held = [xs, t, idx, losses, status, state.exp_avg, state.exp_avg_sq] + ([] if sc is None else [sc]) + tensors
-    s = _stream_of(stream, held, dev)
-    st, keep = _net_struct(p, [w.data_ptr() for w in p.weights], [b.data_ptr() for b in p.biases])
+    s = _stream_of(stream, inputs + [losses, status, state.exp_avg, state.exp_avg_sq] + tensors, dev)
+    st, keep = _net_struct(p)
     opt = state.params()
     flags = _lib.WOS_PTRS_DEVICE | (0 if check_every > 0 else _lib.WOS_ASYNC)
-    rc = _lib.load().wos_siren_fit_run(C.byref(st), xs.data_ptr(), t.data_ptr(), None if sc is None else sc.data_ptr(),
-                                       n_pool, idx.data_ptr(), K, batch, state.exp_avg.data_ptr(),
-                                       state.exp_avg_sq.data_ptr(), state.step, C.byref(opt),
-                                       -1.0 if stop_loss is None else float(stop_loss), check_every, losses.data_ptr(),
-                                       status.data_ptr(), ws, flags, dev.index or 0, s)
-    del keep, held
-    if rc == -1 and check_every > 0:
+    rc = call(_lib.load(), C.byref(st), state.exp_avg.data_ptr(), state.exp_avg_sq.data_ptr(), state.step, C.byref(opt),
+              -1.0 if stop_loss is None else float(stop_loss), check_every, losses.data_ptr(), status.data_ptr(), ws, flags,
+              dev.index or 0, s)
+    del keep
+    if clamps and rc == -1 and check_every > 0:
         # The blocking call refuses a clamped index only after the run: its iterations are applied to the
         # network and the moments, so the state's step follows them before the error is raised.
         torch.cuda.synchronize(dev)
         state.step += int(status[0].item())
-    check(rc, "wos_siren_fit_run")
+    check(rc, f"wos_siren_{who}")
     if stop_loss is None:
         state.step += K
     else:
-        if stream is not None:  # status was written on `stream`: torch's current stream must see it
-            ts = stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.ExternalStream(int(stream), device=dev)
-            torch.cuda.current_stream(dev).wait_stream(ts)
+        _current_waits_for(stream, dev)
         state.step += int(status[0].item())
     return losses, status
+
+
+def _current_waits_for(stream, device):
+    """Torch's current stream waits for `stream`, on which the loop's status was written (None: it is the current one)."""
+    import torch
+    if stream is not None:
+        ts = stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.ExternalStream(int(stream), device=device)
+        torch.cuda.current_stream(device).wait_stream(ts)
 
 
 def fit_run_batches(net, state, x, target, scale, counts, *, stop_loss=None, check_every=0, stream=None,
@@ -767,53 +727,16 @@ def fit_run_batches(net, state, x, target, scale, counts, *, stop_loss=None, che
     if not (_is_torch(x) and x.is_cuda):
         raise ValueError("siren.fit_run_batches: x must be a CUDA tensor (device pointers only)")
     dev = x.device
-
-    def operand(name, a):
-        if not _is_torch(a) or a.device != dev:
-            raise ValueError(f"siren.fit_run_batches: {name} must be a tensor on {dev}, like x")
-        if tuple(a.shape) != (total, p.d_out):
-            raise ValueError(f"siren.fit_run_batches: {name} must have shape {(total, p.d_out)}, got {tuple(a.shape)}")
-        return a.detach().to(torch.float32).contiguous()
     xs = x.detach().to(torch.float32).contiguous()
-    t = operand("target", target)
-    sc = None if scale is None else operand("scale", scale)
+    t = _operand("fit_run_batches", "target", target, (total, p.d_out), True, dev, "x")
+    sc = None if scale is None else _operand("fit_run_batches", "scale", scale, (total, p.d_out), True, dev, "x")
     K = len(offsets) - 1
-    tensors = p.weights + p.biases
-    if any(w.device != dev for w in tensors) or state.exp_avg.device != dev:
-        raise ValueError(f"siren.fit_run_batches: the points are on {dev}, the network on {tensors[0].device}, the state on "
-                         f"{state.exp_avg.device}")
-    if state.counts != [int(w.numel()) for w in tensors]:
-        raise ValueError("siren.fit_run_batches: state was made for a network of another shape")
-    ws = 0 if workspace_bytes is None else int(workspace_bytes)
-    if ws < 0:
-        raise ValueError(f"siren.fit_run_batches: workspace_bytes must be >= 0, got {workspace_bytes}")
-    check_every = int(check_every)
-    if check_every < 0:
-        raise ValueError(f"siren.fit_run_batches: check_every must be >= 0, got {check_every}")
-    if stop_loss is not None and not float(stop_loss) >= 0.0:
-        raise ValueError(f"siren.fit_run_batches: stop_loss must be None or >= 0, got {stop_loss}")
-    losses = torch.empty(K, dtype=torch.float32, device=dev)
-    status = torch.zeros(2, dtype=torch.int64, device=dev)  # zeros: a call refused before any device work applied nothing
-    held = [xs, t, losses, status, state.exp_avg, state.exp_avg_sq] + ([] if sc is None else [sc]) + tensors
-    s = _stream_of(stream, held, dev)
-    st, keep = _net_struct(p, [w.data_ptr() for w in p.weights], [b.data_ptr() for b in p.biases])
-    opt = state.params()
-    flags = _lib.WOS_PTRS_DEVICE | (0 if check_every > 0 else _lib.WOS_ASYNC)
-    rc = _lib.load().wos_siren_fit_run_batches(C.byref(st), xs.data_ptr(), t.data_ptr(), None if sc is None else sc.data_ptr(),
-                                               (C.c_int64 * (K + 1))(*offsets), K, state.exp_avg.data_ptr(),
-                                               state.exp_avg_sq.data_ptr(), state.step, C.byref(opt),
-                                               -1.0 if stop_loss is None else float(stop_loss), check_every,
-                                               losses.data_ptr(), status.data_ptr(), ws, flags, dev.index or 0, s)
-    del keep, held
-    check(rc, "wos_siren_fit_run_batches")
-    if stop_loss is None:
-        state.step += K
-    else:
-        if stream is not None:  # status was written on `stream`: torch's current stream must see it
-            ts = stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.ExternalStream(int(stream), device=dev)
-            torch.cuda.current_stream(dev).wait_stream(ts)
-        state.step += int(status[0].item())
-    return losses, status
+
+    def call(L, net, *rest):
+        return L.wos_siren_fit_run_batches(net, xs.data_ptr(), t.data_ptr(), None if sc is None else sc.data_ptr(),
+                                           (C.c_int64 * (K + 1))(*offsets), K, *rest)
+    return _run_loop("fit_run_batches", "points are", p, state, dev, [xs, t] + ([] if sc is None else [sc]), K, call,
+                     stop_loss, check_every, stream, workspace_bytes)
 
 
 def _batch_offsets(who, counts, total):

@@ -223,6 +223,17 @@ def test_c_abi_pointers_and_refusals(gpu):
     assert np.abs(u.cpu().numpy() - ref[0]).max() < 1e-5 and np.abs(jac.cpu().numpy() - ref[1]).max() < 1e-4
 
 
+def test_no_hidden_layer_host_pointers_equal_device_pointers(gpu):
+    """L = 0: no packed weights, so the device-pointer call allocates nothing and the host-pointer call only its staging."""
+    net = _cuda_net(2, 32, 0)
+    x = sm.points(2, 33)  # one full tile and one point
+    dev = siren.eval(net, torch.from_numpy(x).cuda(), value=True, jacobian=True, divergence=True)
+    host = siren.eval(net, x, value=True, jacobian=True, divergence=True)
+    for what, a, b in zip(("u", "J", "div"), host, dev):  # (accuracy at L = 0: SHAPES above)
+        assert isinstance(a, np.ndarray) and np.array_equal(bits(a), bits(b)), what
+        assert np.isfinite(a).all() and np.abs(a).max() > 0, what
+
+
 # ---- 5. projector --------------------------------------------------------------------------------------
 def test_projector_source_from_network(gpu):
     cfg = workloads.karman_config(n_walks=16, n_points=200)

@@ -1,5 +1,5 @@
 """The device-resident advection fit on the GPU (wos_siren_fit_run_batches,
-csrc/wos_capi_probes.cpp; wos_amd.siren.fit_run_batches, wos_amd.projection.fit_advection):
+csrc/wos_capi_siren.cpp; wos_amd.siren.fit_run_batches, wos_amd.projection.fit_advection):
 fit_run_batches bit for bit against siren.fit and siren.adam_step on the row slices -- ragged counts,
 chunked, continued, from a first offset that is not zero, stopped early -- and fit_advection bit for
 bit against the reference's loop restated here in plain torch (src/2d/models/model_split.py:88-110),
@@ -92,6 +92,20 @@ def test_fit_run_batches_equals_the_separate_calls(gpu, shape, with_scale, clip)
     assert same(losses, want), f"losses {losses.tolist()} separate calls {want.tolist()}"
     assert bool(torch.isfinite(losses).all()) and state_b.step == K
     _same_run(net_a, state_a, net_b, state_b, "fit_run_batches")
+    assert any(not same(a, b) for a, b in zip(_tensors(net_b), _tensors(_cuda_net(*shape)))), "the run moved the network"
+
+
+def test_fit_run_batches_without_a_hidden_layer_equals_the_separate_calls(gpu):
+    """L = 0: no packed copies in the run's temporary, which starts with the H zeros."""
+    shape, counts = (2, 32, 0, 2), [33, 33]  # one full tile and one point, twice
+    rows = _rows(2, 2, True, n=sum(counts))
+    net_a, net_b = _cuda_net(*shape), _cuda_net(*shape)
+    state_a, state_b = siren.AdamState(net_a, max_grad_norm=0.1, **KW), siren.AdamState(net_b, max_grad_norm=0.1, **KW)
+    want = _loop(net_a, state_a, rows, counts)
+    losses, status = siren.fit_run_batches(net_b, state_b, *rows, counts)
+    assert status.tolist() == [2, 0] and same(losses, want), f"losses {losses.tolist()} separate calls {want.tolist()}"
+    assert bool(torch.isfinite(losses).all()) and state_b.step == 2
+    _same_run(net_a, state_a, net_b, state_b, "fit_run_batches, L = 0")
     assert any(not same(a, b) for a, b in zip(_tensors(net_b), _tensors(_cuda_net(*shape)))), "the run moved the network"
 
 

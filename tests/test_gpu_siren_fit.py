@@ -143,6 +143,25 @@ def test_point_counts(gpu, n):
     _check(got, case, f"n = {n}")
 
 
+def test_no_hidden_layer_host_pointers_equal_device_pointers(gpu):
+    """L = 0: no packed copies, the temporary is the H zeros and the plan's work, for the loss alone the tiles'
+    sums (accuracy at L = 0: SHAPES above)."""
+    net, n = _cuda_net(2, 32, 0), 33  # one full tile and one point
+    x = sm.points(2, n)
+    target, scale = fm.problem(n, 2, True, seed=3)
+    dev = siren.fit(net, *[torch.from_numpy(a).cuda() for a in (x, target, scale)])
+    host = siren.fit(net, x, target, scale)
+    assert np.array_equal(bits(host[0]), bits(dev[0])) and np.isfinite(host[0]) and host[0] > 0
+    for kind in (1, 2):
+        assert len(host[kind]) == 2
+        for l, (a, b) in enumerate(zip(host[kind], dev[kind])):
+            assert isinstance(a, np.ndarray) and np.array_equal(bits(a), bits(b)), (kind, l)
+            assert np.isfinite(a).all() and np.abs(a).max() > 0, (kind, l)
+    only_dev = siren.fit(net, *[torch.from_numpy(a).cuda() for a in (x, target, scale)], grads=False)
+    only_host = siren.fit(net, x, target, scale, grads=False)
+    assert np.array_equal(bits(only_dev), bits(host[0])) and np.array_equal(bits(only_host), bits(host[0]))
+
+
 # ---- 3. chunks ---------------------------------------------------------------------------------------------
 def _tile_bytes(H, L):
     return (2 * L + 1) * H * 4 * 32

@@ -340,6 +340,20 @@ def test_fit_run_equals_the_separate_calls(gpu, shape, with_scale, batch, clip):
     assert any(not same(a, b) for a, b in zip(_tensors(net_b), _tensors(_cuda_net(*shape)))), "the run moved the network"
 
 
+def test_fit_run_without_a_hidden_layer_equals_the_separate_calls(gpu):
+    """L = 0: no packed copies in the run's temporary, which starts with the H zeros."""
+    shape, k = (2, 32, 0, 2), 2
+    pool, idx = _pool(2, 2, True), _idx(33, k=k)  # one full tile and one point
+    net_a, net_b = _cuda_net(*shape), _cuda_net(*shape)
+    state_a, state_b = siren.AdamState(net_a, max_grad_norm=0.1, **KW), siren.AdamState(net_b, max_grad_norm=0.1, **KW)
+    want = _loop(net_a, state_a, pool, idx)
+    losses, status = siren.fit_run(net_b, state_b, *pool, idx)
+    assert status.tolist() == [k, 0] and same(losses, want), f"losses {losses.tolist()} separate calls {want.tolist()}"
+    assert bool(torch.isfinite(losses).all()) and state_b.step == k
+    _same_run(net_a, state_a, net_b, state_b, "fit_run, L = 0")
+    assert any(not same(a, b) for a, b in zip(_tensors(net_b), _tensors(_cuda_net(*shape)))), "the run moved the network"
+
+
 def test_fit_run_chunked_and_continued(gpu):
     shape, batch = (2, 64, 1, 2), 65
     pool, idx = _pool(2, 2, True), _idx(batch)

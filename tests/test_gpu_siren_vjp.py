@@ -140,6 +140,20 @@ def test_workspace_below_one_tile_is_refused(gpu):
     assert b"cannot hold one tile" in _lib.load().wos_last_error()
 
 
+def test_no_hidden_layer_host_pointers_equal_device_pointers(gpu):
+    """L = 0: no packed copies, the temporary is the H zeros and the plan's work (accuracy at L = 0: SHAPES above)."""
+    net, n = _cuda_net(2, 32, 0), 33  # one full tile and one point
+    x, g = sm.points(2, n), vm.cotangents(n, 2, 2)
+    dev = siren.vjp(net, torch.from_numpy(x).cuda(), grad_value=torch.from_numpy(g[0]).cuda(),
+                    grad_jacobian=torch.from_numpy(g[1]).cuda(), grad_divergence=torch.from_numpy(g[2]).cuda())
+    host = siren.vjp(net, x, grad_value=g[0], grad_jacobian=g[1], grad_divergence=g[2])
+    for kind in (0, 1):
+        assert len(host[kind]) == 2
+        for l, (a, b) in enumerate(zip(host[kind], dev[kind])):
+            assert isinstance(a, np.ndarray) and np.array_equal(bits(a), bits(b)), (kind, l)
+            assert np.isfinite(a).all() and np.abs(a).max() > 0, (kind, l)
+
+
 # ---- 4. determinism and zeros ----------------------------------------------------------------------------
 @pytest.mark.parametrize("side", [False, True], ids=["current_stream", "side_stream"])
 def test_determinism_zeros_and_written_not_accumulated(gpu, side):

@@ -15,7 +15,7 @@ co() {  # object -> "hash bytes"
 }
 echo "| object | parent | this | bytes parent / this |"
 echo "|---|---|---|---|"
-for u in wos_kernel wos_channels wos_channels_rb wos_robust wos_bvc wos_tape wos_tape_index wos_query wos_siren wos_selftest; do
+for u in wos_kernel wos_channels wos_channels_rb wos_robust wos_bvc wos_tape wos_tape_index wos_query wos_siren wos_siren_vjp wos_siren_fit wos_siren_train wos_selftest; do
   read -r hp bp <<<"$(co "$1/$u.o")"
   read -r ht bt <<<"$(co "$2/$u.o")"
   echo "| build/$u.o | $hp | $ht | $bp / $bt |"

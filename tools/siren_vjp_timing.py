@@ -33,7 +33,7 @@ DEFAULT_STASH = 256 << 20  # wos_siren_vjp's stash cap with workspace_bytes = 0
 
 
 def workspace_bytes(points, d_in, d_out, hidden, n_hidden, compute_units):
-    """The temporary one wos_siren_vjp call takes (csrc/wos_siren.h siren_vjp_plan, wos_capi_probes.cpp)."""
+    """The temporary one wos_siren_vjp call takes (csrc/wos_siren.h siren_vjp_plan, wos_capi_siren.cpp)."""
     c = 1 + d_in
     tile = (2 * n_hidden + 1) * hidden * c * 32 * 4
     tiles_all = (points + 31) // 32
