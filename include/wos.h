@@ -789,6 +789,45 @@ int wos_siren_fit_run_batches(const wos_siren_net *net,
                               float *losses, int64_t *status,
                               size_t workspace_bytes, uint32_t flags, int32_t device, void *stream);
 
+/* ---- Ensemble fit loops: up to WOS_MAX_CHANNELS networks trained in one device loop ------------
+ * The two loops above for n_members = 1..WOS_MAX_CHANNELS networks of one shape, the members of an
+ * ensemble on one obstacle mesh after a multi-channel solve (added within ABI 10: new entry points
+ * only; DESIGN.md "Ensemble fit loops").  nets[n_members]; pool_target / target, pool_scale / scale,
+ * exp_avg and exp_avg_sq are HOST arrays of n_members device pointers (pool_scale / scale may be
+ * NULL, or hold NULL entries: that member has no scale); losses[n_members][n_iters] and
+ * status[n_members][2] are device arrays, member-major.
+ * Shared by the members: the points, the index draw `idx` or the row offsets, opt and step0 -- common
+ * random numbers, as the walks of the multi-channel solve are.  A member's own: its network, targets
+ * and scales, both moments, its row of losses and its status pair.
+ * Every launch of an iteration covers all members (an iteration stays eleven launches).  Bit for bit,
+ * member e's losses, every parameter and both moments are those of wos_siren_fit_run /
+ * wos_siren_fit_run_batches called on member e's arguments alone; workspace_bytes counts per member,
+ * and the call's one stream-ordered temporary is n_members times as large.
+ * Early stop: the stop flag is sticky per member; a stopped member's later updates and loss writes
+ * are no-ops while the others go on, and check_every = c stops enqueuing once every member's flag is
+ * set.  status[e][1] counts the clamped indices of the shared draw (the same number for every e).
+ * WOS_E_INVALID, naming the field and the member, before any device work and writing nothing:
+ * n_members outside 1..WOS_MAX_CHANNELS, members that differ in d_in, d_out, hidden,
+ * n_hidden_layers or omega, two members sharing a weights or biases pointer or a moment buffer, a
+ * NULL entry of nets' arrays, pool_target / target, exp_avg or exp_avg_sq, and every refusal of the
+ * single-network entry points. */
+int wos_siren_fit_run_ensemble(int32_t n_members, const wos_siren_net *nets,
+                               const float *pool_pts, const float *const *pool_target,
+                               const float *const *pool_scale, int64_t n_pool,
+                               const int64_t *idx, int64_t n_iters, int64_t batch,
+                               float *const *exp_avg, float *const *exp_avg_sq, int64_t step0,
+                               const wos_adam_params *opt, float stop_loss, int32_t check_every,
+                               float *losses, int64_t *status,
+                               size_t workspace_bytes, uint32_t flags, int32_t device, void *stream);
+
+int wos_siren_fit_run_batches_ensemble(int32_t n_members, const wos_siren_net *nets,
+                                       const float *pts, const float *const *target, const float *const *scale,
+                                       const int64_t *offsets, int64_t n_iters,
+                                       float *const *exp_avg, float *const *exp_avg_sq, int64_t step0,
+                                       const wos_adam_params *opt, float stop_loss, int32_t check_every,
+                                       float *losses, int64_t *status,
+                                       size_t workspace_bytes, uint32_t flags, int32_t device, void *stream);
+
 const char *wos_last_error(void);
 int32_t wos_abi_version(void);
 int32_t wos_device_count(void);

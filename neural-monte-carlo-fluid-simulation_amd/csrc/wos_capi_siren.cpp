@@ -111,12 +111,20 @@ struct DevTmp {
   }
 };
 
-// the fragment-ordered copy of the hidden weights and, for a backward, the H zeros and the copy of W^T
-static hipError_t enqueue_packs(const wos::SirenNet& dn, float* tmp, const DevTmp& lay, bool transposed, hipStream_t st) {
+// the fragment-ordered copy of the hidden weights and, for a backward, the H zeros and the copy of W^T:
+// for E members in the same three launches, member e's copies e * member_stride floats further on
+// (the zeros are member 0's, and every member reads them)
+static hipError_t enqueue_packs(const wos::SirenNets& nets, int E, float* tmp, const DevTmp& lay, size_t member_stride,
+                                bool transposed, hipStream_t st) {
   hipError_t e;
-  if ((e = wos::launch_siren_pack(dn, tmp, st)) != hipSuccess || !transposed) return e;
-  if ((e = hipMemsetAsync(tmp + lay.o_zero, 0, (size_t)dn.H * sizeof(float), st)) != hipSuccess) return e;
-  return wos::launch_siren_pack_transposed(dn, tmp + lay.o_packT, st);
+  if ((e = wos::launch_siren_pack_members(nets, E, tmp, member_stride, st)) != hipSuccess || !transposed) return e;
+  if ((e = hipMemsetAsync(tmp + lay.o_zero, 0, (size_t)nets.v[0].H * sizeof(float), st)) != hipSuccess) return e;
+  return wos::launch_siren_pack_transposed_members(nets, E, tmp + lay.o_packT, member_stride, st);
+}
+static hipError_t enqueue_packs(const wos::SirenNet& dn, float* tmp, const DevTmp& lay, bool transposed, hipStream_t st) {
+  wos::SirenNets nets{};
+  nets.v[0] = dn;
+  return enqueue_packs(nets, 1, tmp, lay, 0, transposed, st);
 }
 
 // ---- the call protocol ---------------------------------------------------------------------------
@@ -426,8 +434,11 @@ int wos_selftest_siren_vjp_layer(int32_t hidden, int32_t d_in, int64_t n_points,
 // ---- fused Adam step and the device-resident fit loops (wos_siren_train.hip) ---------------------
 static_assert(wos::kAdamMaxTensors == 20, "include/wos.h documents n_tensors as 1..20");
 static_assert(sizeof(wos_adam_params) == 5 * sizeof(double), "wos_adam_params is five doubles (wos_amd/_lib.py AdamParams)");
-static_assert(sizeof(wos::AdamSegs) + sizeof(wos::AdamScalars) + 4 * sizeof(void*) <= 4096,
-              "adam_update_kernel's arguments, the segment table included, fit the kernel argument segment");
+static_assert(sizeof(wos::AdamMembers) + sizeof(wos::AdamScalars) + 2 * sizeof(void*) <= 4096,
+              "adam_update_kernel's arguments, every member's segment table included, fit the kernel argument segment");
+static_assert(sizeof(wos::SirenNets) + sizeof(wos::SirenMemberRows) + 16 * sizeof(void*) <= 4096,
+              "siren_fit_tile_kernel's arguments, every member's network included, fit the kernel argument segment");
+static_assert(wos::kSirenMaxMembers == WOS_MAX_CHANNELS, "an ensemble is as wide as a multi-channel solve");
 static int adam_params_check(const std::string& fn, const wos_adam_params* opt) {
   if (!opt) return fail(WOS_E_INVALID, fn + ": null opt");
   if (!std::isfinite(opt->lr)) return fail(WOS_E_INVALID, fn + ": lr must be finite");
@@ -531,33 +542,49 @@ static void fit_run_bind(const wos_siren_net* net, float* g, wos::SirenNet& dn, 
   bind_layers(net, nullptr, nullptr, dn, dg);
 }
 
-// the rows of one iteration, contiguous on the device
+// the rows of one iteration, contiguous on the device: the points, which the members share, and each
+// member's target and scale
 struct FitRows {
-  const float *pts, *target, *scale;
+  const float* pts;
+  wos::SirenMemberRows m;
 };
 
-// One iteration of either loop on n contiguous rows: wos_siren_fit's launches (both packs, the zero
-// fill, the fit step with `plan`; the loss to state[1]) and wos_adam_step's (the norm to state[2] when
-// clipping; the update, a no-op once state[0] is set).
-static hipError_t fit_run_step(const wos::SirenNet& dn, float* tmp, const DevTmp& lay, const FitRows& r, int64_t n,
-                               const wos::SirenFitPlan& plan, const wos::SirenGrads& dg, const wos::AdamSegs& segs,
-                               float* exp_avg, float* exp_avg_sq, const wos::AdamScalars& sc, bool clip, int* state,
+// What a loop's members keep in its temporary, member e at + e * stride: the device half of a fit step
+// (`member`: packed | packedT | H zeros | work), the flat gradients (`grad`) and, kFitStateWords apart,
+// the state words.
+struct FitStrides {
+  size_t member, grad;
+};
+
+// One iteration of either loop on n contiguous rows, every launch covering the E members:
+// wos_siren_fit's launches (both packs, the zero fill, the fit step with `plan`; the loss to state[1])
+// and wos_adam_step's (the norm to state[2] when clipping; the update, a no-op for a member whose
+// state[0] is set).  dg: member 0's gradients.
+static hipError_t fit_run_step(const wos::SirenNets& nets, int E, float* tmp, const DevTmp& lay, const FitStrides& stride,
+                               const FitRows& r, int64_t n, const wos::SirenFitPlan& plan, const wos::SirenGrads& dg,
+                               const wos::AdamMembers& adam, const wos::AdamScalars& sc, bool clip, int* state,
                                hipStream_t st) {
   float *loss = (float*)state + 1, *norm = (float*)state + 2;
   hipError_t e;
-  if ((e = enqueue_packs(dn, tmp, lay, true, st)) != hipSuccess) return e;
-  if ((e = wos::launch_siren_fit(dn, tmp, tmp + lay.o_packT, tmp + lay.o_zero, r.pts, n, r.target, r.scale, loss, &dg, plan,
-                                 tmp + lay.o_work, st)) != hipSuccess)
+  if ((e = enqueue_packs(nets, E, tmp, lay, stride.member, true, st)) != hipSuccess) return e;
+  if ((e = wos::launch_siren_fit_members(nets, E, tmp, tmp + lay.o_packT, tmp + lay.o_zero, r.pts, n, r.m, loss,
+                                         wos::kFitStateWords, &dg, stride.grad, plan, tmp + lay.o_work, stride.member, st)) !=
+      hipSuccess)
     return e;
-  if (clip && (e = wos::launch_adam_norm(segs, norm, st)) != hipSuccess) return e;
-  return wos::launch_adam_update(segs, exp_avg, exp_avg_sq, sc, clip ? norm : nullptr, state, st);
+  if (clip && (e = wos::launch_adam_norm_members(adam, E, norm, st)) != hipSuccess) return e;
+  return wos::launch_adam_update_members(adam, E, sc, clip ? norm : nullptr, state, st);
 }
 
-// what the two loops take alike
+// what the two loops take alike: n_members networks of one shape, each with its moments, its row of
+// `losses` and its pair of `status`.  ensemble: the caller is an _ensemble entry point, whose
+// refusals name the member.
 struct FitRun {
-  const wos_siren_net* net;
+  bool ensemble;
+  int32_t n_members;
+  const wos_siren_net* nets;
   int64_t n_iters;
-  float *exp_avg, *exp_avg_sq;
+  float* const* exp_avg;
+  float* const* exp_avg_sq;
   int64_t step0;
   const wos_adam_params* opt;
   float stop_loss;
@@ -568,25 +595,75 @@ struct FitRun {
   uint32_t flags;
   int32_t device;
   hipStream_t st;
-};  // (the order of the entry points' own arguments)
+};
 struct NamedPtr {
-  const char* name;
+  std::string name;
   const void* p;
 };
 static size_t pad64(size_t floats) { return (floats + 63) / 64 * 64; }  // to a 256-byte boundary
+static std::string of_member(const FitRun& a, int e) { return a.ensemble ? " of member " + std::to_string(e) : ""; }
 
-// Both loops (the net already checked).  One stream-ordered temporary per run: packed | packedT | H zeros
-// | the largest plan's work (wos_siren_fit's layout), then `gathered` floats of the caller's own, the
-// flat gradients (weights, then biases: the order of exp_avg) and the state words [stop flag, loss,
-// norm], each on a 256-byte boundary.  sizes_check and rows_check: the caller's own refusals, at their
-// places among the shared ones; `in`: its three input arrays.  n_of(i): the rows of iteration i.
-// feed(i, pending, gathered, state, rows): where they lie, after enqueuing what brings them there and
-// the commit of iteration `pending` (-1: none is due).  clamped non-null: status[1] as read back after
-// a blocking run.
+// The members' networks: the envelope of each, then one shape for all.  The first refusal of the
+// loops, as siren_net_check is of the single-network entry points.
+static int fit_run_nets_check(const std::string& fn, const FitRun& a) {
+  if (!a.ensemble) return siren_net_check(fn, a.nets);
+  if (a.n_members < 1 || a.n_members > wos::kSirenMaxMembers)
+    return fail(WOS_E_INVALID, fn + ": n_members must be 1.." + std::to_string(wos::kSirenMaxMembers) + ", got " +
+                                   std::to_string(a.n_members));
+  if (!a.nets) return fail(WOS_E_INVALID, fn + ": null nets");
+  for (int e = 0; e < a.n_members; e++)
+    if (int rc = siren_net_check(fn + ": member " + std::to_string(e), &a.nets[e])) return rc;
+  const wos_siren_net& n0 = a.nets[0];
+  for (int e = 1; e < a.n_members; e++) {
+    const wos_siren_net& ne = a.nets[e];
+    const auto differs = [&](const char* field, const std::string& mine, const std::string& first) {
+      return fail(WOS_E_INVALID, fn + ": member " + std::to_string(e) + ": " + field + " is " + mine + ", member 0's " + first +
+                                     " (the members of an ensemble have one shape)");
+    };
+    if (ne.d_in != n0.d_in) return differs("d_in", std::to_string(ne.d_in), std::to_string(n0.d_in));
+    if (ne.d_out != n0.d_out) return differs("d_out", std::to_string(ne.d_out), std::to_string(n0.d_out));
+    if (ne.hidden != n0.hidden) return differs("hidden", std::to_string(ne.hidden), std::to_string(n0.hidden));
+    if (ne.n_hidden_layers != n0.n_hidden_layers)
+      return differs("n_hidden_layers", std::to_string(ne.n_hidden_layers), std::to_string(n0.n_hidden_layers));
+    if (ne.omega != n0.omega) return differs("omega", std::to_string(ne.omega), std::to_string(n0.omega));
+  }
+  return WOS_OK;
+}
+
+// no two members train the same tensor or keep their moments in the same buffer
+static int fit_run_alias_check(const std::string& fn, const FitRun& a) {
+  const int NL = a.nets[0].n_hidden_layers + 2;
+  for (int e = 1; e < a.n_members; e++)
+    for (int f = 0; f < e; f++) {
+      const std::string pair = ": members " + std::to_string(f) + " and " + std::to_string(e) + " share ";
+      for (int l = 0; l < NL; l++)
+        for (int m = 0; m < NL; m++) {
+          if (a.nets[e].weights[l] == a.nets[f].weights[m])
+            return fail(WOS_E_INVALID, fn + pair + "a weights pointer (layers " + std::to_string(m) + " and " + std::to_string(l) + ")");
+          if (a.nets[e].biases[l] == a.nets[f].biases[m])
+            return fail(WOS_E_INVALID, fn + pair + "a biases pointer (layers " + std::to_string(m) + " and " + std::to_string(l) + ")");
+        }
+      if (a.exp_avg[e] == a.exp_avg[f]) return fail(WOS_E_INVALID, fn + pair + "an exp_avg buffer");
+      if (a.exp_avg_sq[e] == a.exp_avg_sq[f]) return fail(WOS_E_INVALID, fn + pair + "an exp_avg_sq buffer");
+      if (a.exp_avg[e] == a.exp_avg_sq[f] || a.exp_avg_sq[e] == a.exp_avg[f])
+        return fail(WOS_E_INVALID, fn + pair + "a moment buffer (one's exp_avg is the other's exp_avg_sq)");
+    }
+  return WOS_OK;
+}
+
+// Both loops, for one network and for an ensemble.  One stream-ordered temporary per run: per member
+// packed | packedT | H zeros | the largest plan's work (wos_siren_fit's layout), then `gathered` floats
+// of the caller's own, per member the flat gradients (weights, then biases: the order of exp_avg) and
+// per member the state words [stop flag, loss, norm], each on a 256-byte boundary.  sizes_check and
+// rows_check: the caller's own refusals, at their places among the shared ones; `in`: its input
+// arrays.  n_of(i): the rows of iteration i.  feed(i, pending, gathered, state, rows): where they lie,
+// after enqueuing what brings them there and the commit of iteration `pending` (-1: none is due).
+// clamped non-null: status[1] as read back after a blocking run.
 template <class Sizes, class Rows, class NOf, class Feed>
-static int fit_run_loop(const std::string& fn, const FitRun& a, const NamedPtr (&in)[3], Sizes&& sizes_check,
+static int fit_run_loop(const std::string& fn, const FitRun& a, const std::vector<NamedPtr>& in, Sizes&& sizes_check,
                         Rows&& rows_check, size_t gathered, NOf&& n_of, Feed&& feed, int64_t* clamped) {
-  const wos_siren_net* net = a.net;
+  const int E = a.n_members;
+  const wos_siren_net* net = a.nets;  // member 0: every member has its shape
   const int D = net->d_in, H = net->hidden, L = net->n_hidden_layers;
   const int64_t n_iters = a.n_iters;
   hipStream_t st = a.st;
@@ -604,9 +681,14 @@ static int fit_run_loop(const std::string& fn, const FitRun& a, const NamedPtr (
   if (!a.status) return fail(WOS_E_INVALID, fn + ": null status");
   if (!a.exp_avg) return fail(WOS_E_INVALID, fn + ": null exp_avg");
   if (!a.exp_avg_sq) return fail(WOS_E_INVALID, fn + ": null exp_avg_sq");
+  for (int e = 0; e < E; e++) {
+    if (!a.exp_avg[e]) return fail(WOS_E_INVALID, fn + ": null exp_avg" + of_member(a, e));
+    if (!a.exp_avg_sq[e]) return fail(WOS_E_INVALID, fn + ": null exp_avg_sq" + of_member(a, e));
+  }
   if (std::isnan(a.stop_loss)) return fail(WOS_E_INVALID, fn + ": stop_loss is NaN (negative: never stop)");
   if (int rc = adam_params_check(fn, a.opt)) return rc;
   WOS_TRY(rows_check());
+  WOS_TRY(fit_run_alias_check(fn, a));
   WOS_TRY(stash_cap_check(fn, a.workspace_bytes, wos::siren_fit_stash_floats_per_tile(H, L) * sizeof(float)));
   const int32_t device = a.device;
   HIP_TRY(hipSetDevice(device));
@@ -615,7 +697,7 @@ static int fit_run_loop(const std::string& fn, const FitRun& a, const NamedPtr (
   WOS_TRY(plan_args(device, a.workspace_bytes, wos::siren_fit_tile_lds_bytes(D, H), &pa));
   wos::SirenFitPlan plan{};
   int64_t plan_n = -1;
-  const auto plan_of = [&](int64_t n) -> const wos::SirenFitPlan& {  // wos_siren_fit's plan for n rows
+  const auto plan_of = [&](int64_t n) -> const wos::SirenFitPlan& {  // wos_siren_fit's plan for n rows, per member
     if (n != plan_n) plan = wos::siren_fit_plan(dn, n, pa.stash_cap, pa.resident);
     plan_n = n;
     return plan;
@@ -624,34 +706,47 @@ static int fit_run_loop(const std::string& fn, const FitRun& a, const NamedPtr (
   for (int64_t i = 0; i < n_iters; i++) work = std::max(work, plan_of(n_of(i)).total(true));
   const DevTmp lay(dn, true, work);
   size_t n_w[wos::kSirenMaxLayers], n_b[wos::kSirenMaxLayers];
-  const size_t o_own = pad64(lay.floats), o_g = o_own + gathered, o_state = o_g + pad64(layer_counts(net, n_w, n_b));
+  const FitStrides stride{pad64(lay.floats), pad64(layer_counts(net, n_w, n_b))};
+  const size_t o_own = E * stride.member, o_g = o_own + gathered, o_state = o_g + E * stride.grad;
   const bool clip = a.opt->max_grad_norm > 0.0, blocking = !(a.flags & WOS_ASYNC);
-  return with_tmp(fn, o_state + 64, false, a.flags, st, [&](Tmp& t) -> hipError_t {
+  return with_tmp(fn, o_state + (size_t)E * wos::kFitStateWords, false, a.flags, st, [&](Tmp& t) -> hipError_t {
     float* tmp = t.base;
-    wos::AdamSegs segs{};
-    wos::SirenGrads dg{};
-    fit_run_bind(net, tmp + o_g, dn, segs, dg);
+    wos::SirenNets nets{};
+    wos::AdamMembers adam{};
+    wos::SirenGrads dg{};  // member 0's: member e's lie e * stride.grad further on
+    for (int e = E - 1; e >= 0; e--) {
+      nets.v[e] = dn;
+      fit_run_bind(&a.nets[e], tmp + o_g + e * stride.grad, nets.v[e], adam.segs[e], dg);
+      adam.exp_avg[e] = a.exp_avg[e];
+      adam.exp_avg_sq[e] = a.exp_avg_sq[e];
+    }
     int* state = (int*)(tmp + o_state);
-    const auto commit = [&](int64_t i) { return wos::launch_fit_run_commit(state, i, a.stop_loss, a.losses, a.status, st); };
+    const auto commit = [&](int64_t i) {
+      return wos::launch_fit_run_commit_members(E, state, i, a.stop_loss, a.losses, n_iters, a.status, st);
+    };
     hipError_t e;
-    if ((e = hipMemsetAsync(state, 0, 64 * sizeof(float), st)) != hipSuccess) return e;
-    if ((e = hipMemsetAsync(a.status, 0, 2 * sizeof(int64_t), st)) != hipSuccess) return e;
-    if ((e = hipMemsetD32Async((hipDeviceptr_t)a.losses, 0x7FC00000, (size_t)n_iters, st)) != hipSuccess) return e;
-    int stopped = 0;       // the flag as last read on the host (check_every > 0)
-    int64_t pending = -1;  // the iteration whose commit has not been enqueued yet
+    if ((e = hipMemsetAsync(state, 0, (size_t)E * wos::kFitStateWords * sizeof(float), st)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(a.status, 0, (size_t)E * 2 * sizeof(int64_t), st)) != hipSuccess) return e;
+    if ((e = hipMemsetD32Async((hipDeviceptr_t)a.losses, 0x7FC00000, (size_t)E * n_iters, st)) != hipSuccess) return e;
+    int flags[wos::kSirenMaxMembers * wos::kFitStateWords] = {};  // the state words as last read on the host (check_every > 0)
+    bool stopped = false;                                         // every member's flag was set then
+    int64_t pending = -1;                                         // the iteration whose commit has not been enqueued yet
     for (int64_t i = 0; i < n_iters && !stopped; i++) {
       FitRows r{};
       if ((e = feed(i, pending, tmp + o_own, state, r)) != hipSuccess) return e;
       const int64_t n = n_of(i);
-      if ((e = fit_run_step(dn, tmp, lay, r, n, plan_of(n), dg, segs, a.exp_avg, a.exp_avg_sq,
-                            adam_scalars(*a.opt, a.step0 + i + 1), clip, state, st)) != hipSuccess)
+      if ((e = fit_run_step(nets, E, tmp, lay, stride, r, n, plan_of(n), dg, adam, adam_scalars(*a.opt, a.step0 + i + 1), clip,
+                            state, st)) != hipSuccess)
         return e;
       pending = i;
       if (a.check_every > 0 && (i + 1) % a.check_every == 0 && i + 1 < n_iters) {
         if ((e = commit(i)) != hipSuccess) return e;
         pending = -1;
-        if ((e = hipMemcpyAsync(&stopped, state, sizeof(int), hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
+        const size_t words = (size_t)(E - 1) * wos::kFitStateWords + 1;
+        if ((e = hipMemcpyAsync(flags, state, words * sizeof(int), hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
         if ((e = hipStreamSynchronize(st)) != hipSuccess) return e;
+        stopped = true;
+        for (int m = 0; m < E; m++) stopped = stopped && flags[m * wos::kFitStateWords] != 0;
       }
     }
     if (pending >= 0 && (e = commit(pending)) != hipSuccess) return e;
@@ -660,25 +755,27 @@ static int fit_run_loop(const std::string& fn, const FitRun& a, const NamedPtr (
   });
 }
 
-extern "C" {
-
-// Iteration i gathers the rows idx[i * batch ..] of the pool into the temporary (points | target |
-// scale); the gather carries the commit of the iteration before.
-int wos_siren_fit_run(const wos_siren_net* net, const float* pool_pts, const float* pool_target, const float* pool_scale,
-                      int64_t n_pool, const int64_t* idx, int64_t n_iters, int64_t batch, float* exp_avg,
-                      float* exp_avg_sq, int64_t step0, const wos_adam_params* opt, float stop_loss, int32_t check_every,
-                      float* losses, int64_t* status, size_t workspace_bytes, uint32_t flags, int32_t device,
-                      void* stream) {
-  const std::string fn = "wos_siren_fit_run";
-  if (int rc = siren_net_check(fn, net)) return rc;
-  const int D = net->d_in, DO = net->d_out;
-  hipStream_t st = (hipStream_t)stream;
-  const FitRun a{net, n_iters, exp_avg, exp_avg_sq, step0, opt, stop_loss, check_every, losses, status, workspace_bytes,
-                 flags, device, st};
-  const size_t B = (size_t)batch, g_pts = pad64(B * D), g_t = pad64(B * DO), g_s = pool_scale ? g_t : 0;
+// The pool form for one network and for an ensemble.  Iteration i gathers the rows idx[i * batch ..]
+// of the pool into the temporary (the shared points, then per member target | scale); the gather
+// carries the commit of the iteration before.
+static int fit_run_pool(const std::string& fn, const FitRun& a, const float* pool_pts, const float* const* pool_target,
+                        const float* const* pool_scale, int64_t n_pool, const int64_t* idx, int64_t batch) {
+  if (int rc = fit_run_nets_check(fn, a)) return rc;
+  const int E = a.n_members, D = a.nets[0].d_in, DO = a.nets[0].d_out;
+  std::vector<NamedPtr> in{{"pool_pts", pool_pts}, {"pool_target", pool_target}};
+  wos::FitPools pools{};
+  bool scaled = false;
+  for (int e = 0; e < E && pool_target; e++) {
+    in.push_back({"pool_target" + of_member(a, e), pool_target[e]});
+    pools.target[e] = pool_target[e];
+    pools.scale[e] = pool_scale ? pool_scale[e] : nullptr;
+    scaled = scaled || pools.scale[e];
+  }
+  in.push_back({"idx", idx});
+  const size_t B = (size_t)batch, g_pts = pad64(B * D), g_t = pad64(B * DO), g_s = scaled ? g_t : 0, g_rows = g_t + g_s;
   int64_t bad = 0;
   const int rc = fit_run_loop(
-      fn, a, {{"pool_pts", pool_pts}, {"pool_target", pool_target}, {"idx", idx}},
+      fn, a, in,
       [&]() -> int {
         if (batch <= 0) return fail(WOS_E_INVALID, fn + ": batch must be positive, got " + std::to_string(batch));
         if (n_pool <= 0) return fail(WOS_E_INVALID, fn + ": n_pool must be positive, got " + std::to_string(n_pool));
@@ -686,12 +783,16 @@ int wos_siren_fit_run(const wos_siren_net* net, const float* pool_pts, const flo
           return fail(WOS_E_INVALID, fn + ": batch: too many points for one step");
         return WOS_OK;
       },
-      [] { return WOS_OK; }, g_pts + g_t + g_s, [&](int64_t) { return batch; },
+      [] { return WOS_OK; }, g_pts + E * g_rows, [&](int64_t) { return batch; },
       [&](int64_t i, int64_t pending, float* own, int* state, FitRows& r) {
-        float *b_pts = own, *b_t = own + g_pts, *b_s = pool_scale ? b_t + g_t : nullptr;
-        r = {b_pts, b_t, b_s};
-        return wos::launch_fit_run_gather(D, DO, pool_pts, pool_target, pool_scale, n_pool, idx + i * batch, batch, b_pts, b_t,
-                                          b_s, state, pending, stop_loss, losses, status, st);
+        float *b_pts = own, *b_t = own + g_pts, *b_s = scaled ? b_t + g_t : nullptr;
+        r.pts = b_pts;
+        for (int e = 0; e < E; e++) {
+          r.m.target[e] = b_t + e * g_rows;
+          r.m.scale[e] = pools.scale[e] ? b_s + e * g_rows : nullptr;
+        }
+        return wos::launch_fit_run_gather_members(D, DO, E, pool_pts, pools, n_pool, idx + i * batch, batch, b_pts, b_t, b_s,
+                                                  g_rows, state, pending, a.stop_loss, a.losses, a.n_iters, a.status, a.st);
       },
       &bad);
   if (rc == WOS_OK && bad != 0)
@@ -699,21 +800,19 @@ int wos_siren_fit_run(const wos_siren_net* net, const float* pool_pts, const flo
   return rc;
 }
 
-// wos_siren_fit_run without a pool: iteration i's rows offsets[i] .. offsets[i + 1] - 1 are read in
-// place, with wos_siren_fit's plan for that many rows.  The commit that the gather carries there is a
-// launch of its own here, between two iterations.
-int wos_siren_fit_run_batches(const wos_siren_net* net, const float* pts, const float* target, const float* scale,
-                              const int64_t* offsets, int64_t n_iters, float* exp_avg, float* exp_avg_sq, int64_t step0,
-                              const wos_adam_params* opt, float stop_loss, int32_t check_every, float* losses,
-                              int64_t* status, size_t workspace_bytes, uint32_t flags, int32_t device, void* stream) {
-  const std::string fn = "wos_siren_fit_run_batches";
-  if (int rc = siren_net_check(fn, net)) return rc;
-  const int D = net->d_in, DO = net->d_out;
-  hipStream_t st = (hipStream_t)stream;
-  const FitRun a{net, n_iters, exp_avg, exp_avg_sq, step0, opt, stop_loss, check_every, losses, status, workspace_bytes,
-                 flags, device, st};
+// The form without a pool: iteration i's rows offsets[i] .. offsets[i + 1] - 1 are read in place, with
+// wos_siren_fit's plan for that many rows.  The commit that the gather carries there is a launch of
+// its own here, between two iterations.
+static int fit_run_rows(const std::string& fn, const FitRun& a, const float* pts, const float* const* target,
+                        const float* const* scale, const int64_t* offsets) {
+  if (int rc = fit_run_nets_check(fn, a)) return rc;
+  const int E = a.n_members, D = a.nets[0].d_in, DO = a.nets[0].d_out;
+  const int64_t n_iters = a.n_iters;
+  std::vector<NamedPtr> in{{"pts", pts}, {"target", target}};
+  for (int e = 0; e < E && target; e++) in.push_back({"target" + of_member(a, e), target[e]});
+  in.push_back({"offsets", offsets});
   return fit_run_loop(
-      fn, a, {{"pts", pts}, {"target", target}, {"offsets", offsets}}, [] { return WOS_OK; },
+      fn, a, in, [] { return WOS_OK; },
       [&]() -> int {
         if (offsets[0] < 0) return fail(WOS_E_INVALID, fn + ": offsets[0] must be >= 0, got " + std::to_string(offsets[0]));
         for (int64_t i = 0; i < n_iters; i++) {
@@ -729,10 +828,61 @@ int wos_siren_fit_run_batches(const wos_siren_net* net, const float* pts, const 
       0, [&](int64_t i) { return offsets[i + 1] - offsets[i]; },
       [&](int64_t i, int64_t pending, float*, int* state, FitRows& r) {
         const int64_t row = offsets[i];
-        r = {pts + row * D, target + row * DO, scale ? scale + row * DO : nullptr};
-        return pending >= 0 ? wos::launch_fit_run_commit(state, pending, stop_loss, losses, status, st) : hipSuccess;
+        r.pts = pts + row * D;
+        for (int e = 0; e < E; e++) {
+          r.m.target[e] = target[e] + row * DO;
+          r.m.scale[e] = scale && scale[e] ? scale[e] + row * DO : nullptr;
+        }
+        return pending >= 0 ? wos::launch_fit_run_commit_members(E, state, pending, a.stop_loss, a.losses, n_iters, a.status, a.st)
+                            : hipSuccess;
       },
       nullptr);
+}
+
+extern "C" {
+
+int wos_siren_fit_run(const wos_siren_net* net, const float* pool_pts, const float* pool_target, const float* pool_scale,
+                      int64_t n_pool, const int64_t* idx, int64_t n_iters, int64_t batch, float* exp_avg,
+                      float* exp_avg_sq, int64_t step0, const wos_adam_params* opt, float stop_loss, int32_t check_every,
+                      float* losses, int64_t* status, size_t workspace_bytes, uint32_t flags, int32_t device,
+                      void* stream) {
+  const FitRun a{false, 1, net, n_iters, &exp_avg, &exp_avg_sq, step0, opt, stop_loss, check_every, losses, status,
+                 workspace_bytes, flags, device, (hipStream_t)stream};
+  return fit_run_pool("wos_siren_fit_run", a, pool_pts, &pool_target, &pool_scale, n_pool, idx, batch);
+}
+
+int wos_siren_fit_run_batches(const wos_siren_net* net, const float* pts, const float* target, const float* scale,
+                              const int64_t* offsets, int64_t n_iters, float* exp_avg, float* exp_avg_sq, int64_t step0,
+                              const wos_adam_params* opt, float stop_loss, int32_t check_every, float* losses,
+                              int64_t* status, size_t workspace_bytes, uint32_t flags, int32_t device, void* stream) {
+  const FitRun a{false, 1, net, n_iters, &exp_avg, &exp_avg_sq, step0, opt, stop_loss, check_every, losses, status,
+                 workspace_bytes, flags, device, (hipStream_t)stream};
+  return fit_run_rows("wos_siren_fit_run_batches", a, pts, &target, &scale, offsets);
+}
+
+// The two loops for n_members networks of one shape on the same points, index draw or row offsets,
+// optimiser parameters and step0: every launch of an iteration covers all members, and member e ends
+// with the bits of the single-network call on its own arguments.
+int wos_siren_fit_run_ensemble(int32_t n_members, const wos_siren_net* nets, const float* pool_pts,
+                               const float* const* pool_target, const float* const* pool_scale, int64_t n_pool,
+                               const int64_t* idx, int64_t n_iters, int64_t batch, float* const* exp_avg,
+                               float* const* exp_avg_sq, int64_t step0, const wos_adam_params* opt, float stop_loss,
+                               int32_t check_every, float* losses, int64_t* status, size_t workspace_bytes, uint32_t flags,
+                               int32_t device, void* stream) {
+  const FitRun a{true, n_members, nets, n_iters, exp_avg, exp_avg_sq, step0, opt, stop_loss, check_every, losses, status,
+                 workspace_bytes, flags, device, (hipStream_t)stream};
+  return fit_run_pool("wos_siren_fit_run_ensemble", a, pool_pts, pool_target, pool_scale, n_pool, idx, batch);
+}
+
+int wos_siren_fit_run_batches_ensemble(int32_t n_members, const wos_siren_net* nets, const float* pts,
+                                       const float* const* target, const float* const* scale, const int64_t* offsets,
+                                       int64_t n_iters, float* const* exp_avg, float* const* exp_avg_sq, int64_t step0,
+                                       const wos_adam_params* opt, float stop_loss, int32_t check_every, float* losses,
+                                       int64_t* status, size_t workspace_bytes, uint32_t flags, int32_t device,
+                                       void* stream) {
+  const FitRun a{true, n_members, nets, n_iters, exp_avg, exp_avg_sq, step0, opt, stop_loss, check_every, losses, status,
+                 workspace_bytes, flags, device, (hipStream_t)stream};
+  return fit_run_rows("wos_siren_fit_run_batches_ensemble", a, pts, target, scale, offsets);
 }
 
 }  // extern "C"

@@ -22,12 +22,27 @@ struct SirenNet {
   const float* b[kSirenMaxLayers];
 };
 
+// An ensemble: up to kSirenMaxMembers networks of one shape trained side by side.  A launch with a
+// member axis carries every member's own pointers in its arguments (about 740 bytes of SirenNet);
+// what the members keep in the call's temporary lies a fixed stride apart, member e at + e * stride.
+constexpr int kSirenMaxMembers = 4;
+struct SirenNets {
+  SirenNet v[kSirenMaxMembers];
+};
+// the rows of one fit step per member: target (and scale, null: 1) [n][d_out]
+struct SirenMemberRows {
+  const float* target[kSirenMaxMembers];
+  const float* scale[kSirenMaxMembers];
+};
+
 // floats of the fragment-ordered copy of the L hidden weight matrices (0 for L = 0)
 inline size_t siren_pack_floats(int H, int L) { return (size_t)L * H * H; }
 
 // Rewrites hidden layer l's W [H][H] as packed[l][r][q][lane][e] = W[32 r + (lane & 31)][8 q + 2 e + (lane >> 5)]:
 // the A operand of k-step 4 q + e of row tile r, one 16-byte load per lane and four k-steps.
 hipError_t launch_siren_pack(const SirenNet& net, float* packed, hipStream_t s);
+// The same for members 0 .. E - 1 in one launch: member e's copy at packed + e * member_stride.
+hipError_t launch_siren_pack_members(const SirenNets& nets, int E, float* packed, size_t member_stride, hipStream_t s);
 
 // u [n][d_out], jac [n][d_out][d_in], div [n]: each may be null.  packed: launch_siren_pack's.
 hipError_t launch_siren_eval(const SirenNet& net, const float* packed, const float* pts, int64_t n, float* u,
@@ -46,6 +61,8 @@ hipError_t launch_siren_layer_packed(int H, int d_in, int64_t n, const float* pa
 // ---- backward (wos_siren_vjp.hip) --------------------------------------------------------------
 // packedT[l][r][q][lane][e] = W[8 q + 2 e + (lane >> 5)][32 r + (lane & 31)]: launch_siren_pack's copy of W^T.
 hipError_t launch_siren_pack_transposed(const SirenNet& net, float* packedT, hipStream_t s);
+hipError_t launch_siren_pack_transposed_members(const SirenNets& nets, int E, float* packedT, size_t member_stride,
+                                                hipStream_t s);
 
 // Gradient pointers of one network, shapes of SirenNet's w and b.
 struct SirenGrads {
@@ -94,10 +111,16 @@ struct SirenReduceSegs {
 // that depends on n_part alone.
 hipError_t siren_reduce(const float* part, int n_part, size_t stride, const SirenReduceSegs& segs, bool accumulate,
                         hipStream_t s);
+// E members in one launch: member e reads part + e * part_member_stride and writes dst[k] + e * dst_member_stride.
+hipError_t siren_reduce_members(const float* part, int n_part, size_t stride, const SirenReduceSegs& segs, bool accumulate,
+                                int E, size_t part_member_stride, size_t dst_member_stride, hipStream_t s);
 // part[slice][l] [H][H] = dZ_l X_{l-1}^T over the slice's column blocks: ds, xs [L][tiles][H][C * 32]
 // (layer_stride apart), C columns per point, columns of points past n_valid masked.
 hipError_t siren_wgrad(const float* ds, const float* xs, size_t layer_stride, int H, int C, int tiles, int64_t n_valid,
                        float* part, int L, hipStream_t s);
+// E members in one launch (grid z = member * L + layer): member e's ds, xs and part at + e * member_stride.
+hipError_t siren_wgrad_members(const float* ds, const float* xs, size_t layer_stride, int H, int C, int tiles,
+                               int64_t n_valid, float* part, int L, int E, size_t member_stride, hipStream_t s);
 
 // wos_selftest_siren_vjp_layer's device half: dX = W^T dZ from the transposed pack and
 // siren_hidden_gemm, dW = sum dZ X^T from the weight-gradient kernel and its reduction.  dZ, X, dX
@@ -130,6 +153,14 @@ size_t siren_fit_tile_lds_bytes(int d_in, int H);  // dynamic LDS of one tile wo
 hipError_t launch_siren_fit(const SirenNet& net, const float* packed, const float* packedT, const float* zeros,
                             const float* pts, int64_t n, const float* target, const float* scale, float* loss,
                             const SirenGrads* grads, const SirenFitPlan& plan, float* work, hipStream_t s);
+// The same step for members 0 .. E - 1 on the same points, each launch covering all of them: member e
+// does exactly what launch_siren_fit does on nets.v[e] and its rows.  packed, packedT and work are
+// member 0's, member e's lie e * member_stride floats further on; `zeros` is shared.  loss: member e's
+// at loss + e * loss_stride.  grads: member 0's, each pointer of member e's grad_stride floats further on.
+hipError_t launch_siren_fit_members(const SirenNets& nets, int E, const float* packed, const float* packedT,
+                                    const float* zeros, const float* pts, int64_t n, const SirenMemberRows& rows,
+                                    float* loss, size_t loss_stride, const SirenGrads* grads, size_t grad_stride,
+                                    const SirenFitPlan& plan, float* work, size_t member_stride, hipStream_t s);
 
 // ---- optimiser step and the device-resident fit loop (wos_siren_train.hip) ----------------------
 // The tensors of one Adam step in their flat order: tensor k holds the elements [end[k - 1], end[k])
@@ -147,12 +178,26 @@ struct AdamSegs {
 struct AdamScalars {
   float b2, omb1, omb2, bc2, ss, eps, max_norm;
 };
+// One Adam step per member: its tensors and its two moment buffers.
+struct AdamMembers {
+  AdamSegs segs[kSirenMaxMembers];
+  float* exp_avg[kSirenMaxMembers];
+  float* exp_avg_sq[kSirenMaxMembers];
+};
+// A fit loop's state words, kFitStateWords per member: [0] the sticky stop flag, [1] the bits of the
+// iteration's loss, [2] the gradient norm.
+constexpr int kFitStateWords = 64;
 // norm[0] = the L2 norm of all gradients, one workgroup, a fixed order.
 hipError_t launch_adam_norm(const AdamSegs& segs, float* norm, hipStream_t s);
+// One workgroup per member: member e's norm to norm[e * kFitStateWords].
+hipError_t launch_adam_norm_members(const AdamMembers& m, int E, float* norm, hipStream_t s);
 // norm non-null: the gradients count as g * min(max_norm / (norm[0] + 1e-6f), 1).  stop non-null and
 // stop[0] != 0: nothing is written.
 hipError_t launch_adam_update(const AdamSegs& segs, float* exp_avg, float* exp_avg_sq, const AdamScalars& sc,
                               const float* norm, const int* stop, hipStream_t s);
+// All members in one launch: member e's norm and stop words lie e * kFitStateWords further on.
+hipError_t launch_adam_update_members(const AdamMembers& m, int E, const AdamScalars& sc, const float* norm,
+                                      const int* stop, hipStream_t s);
 // wos_siren_fit_run's state: state[0] the sticky stop flag, state[1] the bits of the iteration's loss.
 // The gather copies rows idx[0 .. batch) of the pool arrays (pool_scale and scale may be null) into
 // pts / target / scale, clamping and counting (status[1]) an index outside [0, n_pool), and commits
@@ -164,5 +209,19 @@ hipError_t launch_fit_run_gather(int d_in, int d_out, const float* pool_pts, con
                                  int64_t* status, hipStream_t s);
 hipError_t launch_fit_run_commit(int* state, int64_t iter, float stop_loss, float* losses, int64_t* status,
                                  hipStream_t s);
+// The same for E members that share the pool's points and the index draw.  Member e gathers its own
+// pool_target[e] / pool_scale[e] (a null entry: no scale) into target / scale + e * rows_stride and
+// commits into state + e * kFitStateWords, losses + e * losses_stride and status + 2 e; member 0
+// writes the shared pts.
+struct FitPools {
+  const float* target[kSirenMaxMembers];
+  const float* scale[kSirenMaxMembers];
+};
+hipError_t launch_fit_run_gather_members(int d_in, int d_out, int E, const float* pool_pts, const FitPools& pools,
+                                         int64_t n_pool, const int64_t* idx, int64_t batch, float* pts, float* target,
+                                         float* scale, size_t rows_stride, int* state, int64_t prev, float stop_loss,
+                                         float* losses, int64_t losses_stride, int64_t* status, hipStream_t s);
+hipError_t launch_fit_run_commit_members(int E, int* state, int64_t iter, float stop_loss, float* losses,
+                                         int64_t losses_stride, int64_t* status, hipStream_t s);
 
 }  // namespace wos

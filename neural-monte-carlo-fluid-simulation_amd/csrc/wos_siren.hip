@@ -34,7 +34,11 @@
 
 namespace wos {
 
-__global__ __launch_bounds__(256) void siren_pack_kernel(const SirenNet net, float* __restrict__ packed) {
+// grid y: the member, whose copy lies blockIdx.y * member_stride floats into `packed`
+__global__ __launch_bounds__(256) void siren_pack_kernel(const SirenNets nets, float* __restrict__ packed,
+                                                        size_t member_stride) {
+  const SirenNet& net = nets.v[blockIdx.y];
+  packed += blockIdx.y * member_stride;
   const int H = net.H, Q = H >> 3;
   const size_t per = (size_t)H * H, total = per * net.L;
   for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
@@ -198,12 +202,18 @@ __global__ __launch_bounds__(256) void siren_layer_selftest_kernel(int H, const 
   }
 }
 
-hipError_t launch_siren_pack(const SirenNet& net, float* packed, hipStream_t s) {
-  const size_t total = siren_pack_floats(net.H, net.L);
+hipError_t launch_siren_pack_members(const SirenNets& nets, int E, float* packed, size_t member_stride, hipStream_t s) {
+  const size_t total = siren_pack_floats(nets.v[0].H, nets.v[0].L);
   if (total == 0) return hipSuccess;
   const unsigned grid = (unsigned)((total + 255) / 256);
-  hipLaunchKernelGGL(siren_pack_kernel, dim3(grid), dim3(256), 0, s, net, packed);
+  hipLaunchKernelGGL(siren_pack_kernel, dim3(grid, E), dim3(256), 0, s, nets, packed, member_stride);
   return hipGetLastError();
+}
+
+hipError_t launch_siren_pack(const SirenNet& net, float* packed, hipStream_t s) {
+  SirenNets nets{};
+  nets.v[0] = net;
+  return launch_siren_pack_members(nets, 1, packed, 0, s);
 }
 
 template <int D, bool TAN, int RT>

@@ -31,19 +31,36 @@
 namespace wos {
 
 // xs: [L + 1][T][H][32], ds: [L][T][H][32] (layer_stride = T H 32); part: [tile][P], the backward's
-// layout: dWo [d_out][H] | dbo [d_out] | db_0 .. db_L [H] each | dW0 [H][D]; loss_part: [tile]
+// layout: dWo [d_out][H] | dbo [d_out] | db_0 .. db_L [H] each | dW0 [H][D]; loss_part: [tile].
+// Grid y is the member: its network and rows come from the argument arrays, and its packed copies,
+// stash and partials lie blockIdx.y * member_stride floats past member 0's.  The points and the
+// zeros are shared.
 template <int D, int RT, bool GRADS>
-__global__ __launch_bounds__(256) void siren_fit_tile_kernel(const SirenNet net, const float4* __restrict__ packed,
+__global__ __launch_bounds__(256) void siren_fit_tile_kernel(const SirenNets nets, const float4* __restrict__ packed,
                                                             const float4* __restrict__ packedT,
                                                             const float* __restrict__ zeros,
                                                             const float* __restrict__ pts, int64_t n,
-                                                            const float* __restrict__ target,
-                                                            const float* __restrict__ scale, float inv_count,
+                                                            const SirenMemberRows rows, float inv_count,
                                                             float* __restrict__ xs, float* __restrict__ ds,
                                                             size_t layer_stride, float* __restrict__ tile_part, int P,
-                                                            float* __restrict__ loss_part) {
+                                                            float* __restrict__ loss_part, size_t member_stride) {
   constexpr int cols = 32;
   extern __shared__ __attribute__((aligned(16))) float s_mem[];
+  const int member = blockIdx.y;
+  const SirenNet& net = nets.v[member];
+  const float* __restrict__ target = rows.target[member];
+  const float* __restrict__ scale = rows.scale[member];
+  {  // (a stride that is a multiple of four floats: the packed copies are read as float4)
+    const size_t off = member * member_stride;
+    packed += off / 4;
+    loss_part += off;
+    if (GRADS) {
+      packedT += off / 4;
+      xs += off;
+      ds += off;
+      tile_part += off;
+    }
+  }
   const int H = net.H, L = net.L, DO = net.d_out;
   const float omega = net.omega;
   float* Xl = s_mem;             // [H][32]
@@ -250,11 +267,14 @@ __global__ __launch_bounds__(256) void siren_fit_tile_kernel(const SirenNet net,
 // loss = (first ? 0 : loss) + sum of part[0 .. n_part), divided by `count` after the last chunk;
 // between chunks loss[0] holds the running sum of squares.  One workgroup: thread t adds the
 // partials t, t + 256, ... as a chain, then the 256 chains' sums pairwise, (t, t + 128), (t, t + 64), ...
+// One workgroup per member: its partials at part + e * part_stride, its loss at loss[e * loss_stride].
 __global__ __launch_bounds__(256) void siren_fit_loss_kernel(const float* __restrict__ part, int n_part,
                                                             float* __restrict__ loss, float count, int first,
-                                                            int last) {
+                                                            int last, size_t part_stride, size_t loss_stride) {
   __shared__ float sm[256];
   const int tid = threadIdx.x;
+  part += blockIdx.x * part_stride;
+  loss += blockIdx.x * loss_stride;
   float s = 0.0f;
   for (int i = tid; i < n_part; i += 256) s = s + part[i];
   sm[tid] = s;
@@ -288,36 +308,45 @@ SirenFitPlan siren_fit_plan(const SirenNet& net, int64_t n, size_t stash_cap_byt
   return p;
 }
 
+// what one chunk's tile launch takes
+struct FitTileArgs {
+  const float *packed, *packedT, *zeros, *pts;
+  int64_t n;
+  SirenMemberRows rows;
+  float inv_count;
+  float *xs, *ds;
+  size_t layer_stride;
+  float* tile_part;
+  int P;
+  float* loss_part;
+  size_t member_stride;
+};
+
 template <int D, int RT, bool GRADS>
-static hipError_t siren_fit_tile_launch(const SirenNet& net, const float* packed, const float* packedT,
-                                        const float* zeros, const float* pts, int64_t n, const float* target,
-                                        const float* scale, float inv_count, float* xs, float* ds, size_t layer_stride,
-                                        float* tile_part, int P, float* loss_part, hipStream_t s) {
-  const size_t lds = siren_fit_tile_lds_bytes(D, net.H);
-  const int64_t grid = (n + kSirenTile - 1) / kSirenTile;
-  hipLaunchKernelGGL((siren_fit_tile_kernel<D, RT, GRADS>), dim3((unsigned)grid), dim3(256), lds, s, net,
-                     (const float4*)packed, (const float4*)packedT, zeros, pts, n, target, scale, inv_count, xs, ds,
-                     layer_stride, tile_part, P, loss_part);
+static hipError_t siren_fit_tile_launch(const SirenNets& nets, int E, const FitTileArgs& a, hipStream_t s) {
+  const size_t lds = siren_fit_tile_lds_bytes(D, nets.v[0].H);
+  const int64_t grid = (a.n + kSirenTile - 1) / kSirenTile;
+  hipLaunchKernelGGL((siren_fit_tile_kernel<D, RT, GRADS>), dim3((unsigned)grid, E), dim3(256), lds, s, nets,
+                     (const float4*)a.packed, (const float4*)a.packedT, a.zeros, a.pts, a.n, a.rows, a.inv_count, a.xs,
+                     a.ds, a.layer_stride, a.tile_part, a.P, a.loss_part, a.member_stride);
   return hipGetLastError();
 }
 
 template <bool GRADS>
-static hipError_t siren_fit_tile_select(const SirenNet& net, const float* packed, const float* packedT,
-                                        const float* zeros, const float* pts, int64_t n, const float* target,
-                                        const float* scale, float inv_count, float* xs, float* ds, size_t layer_stride,
-                                        float* tile_part, int P, float* loss_part, hipStream_t s) {
+static hipError_t siren_fit_tile_select(const SirenNets& nets, int E, const FitTileArgs& a, hipStream_t s) {
+  const SirenNet& net = nets.v[0];
   if (net.d_in == 2)
-    return net.H > 128 ? siren_fit_tile_launch<2, 2, GRADS>(net, packed, packedT, zeros, pts, n, target, scale, inv_count, xs, ds, layer_stride, tile_part, P, loss_part, s)
-                       : siren_fit_tile_launch<2, 1, GRADS>(net, packed, packedT, zeros, pts, n, target, scale, inv_count, xs, ds, layer_stride, tile_part, P, loss_part, s);
-  return net.H > 128 ? siren_fit_tile_launch<3, 2, GRADS>(net, packed, packedT, zeros, pts, n, target, scale, inv_count, xs, ds, layer_stride, tile_part, P, loss_part, s)
-                     : siren_fit_tile_launch<3, 1, GRADS>(net, packed, packedT, zeros, pts, n, target, scale, inv_count, xs, ds, layer_stride, tile_part, P, loss_part, s);
+    return net.H > 128 ? siren_fit_tile_launch<2, 2, GRADS>(nets, E, a, s) : siren_fit_tile_launch<2, 1, GRADS>(nets, E, a, s);
+  return net.H > 128 ? siren_fit_tile_launch<3, 2, GRADS>(nets, E, a, s) : siren_fit_tile_launch<3, 1, GRADS>(nets, E, a, s);
 }
 
-hipError_t launch_siren_fit(const SirenNet& net, const float* packed, const float* packedT, const float* zeros,
-                            const float* pts, int64_t n, const float* target, const float* scale, float* loss,
-                            const SirenGrads* grads, const SirenFitPlan& plan, float* work, hipStream_t s) {
+hipError_t launch_siren_fit_members(const SirenNets& nets, int E, const float* packed, const float* packedT,
+                                    const float* zeros, const float* pts, int64_t n, const SirenMemberRows& rows,
+                                    float* loss, size_t loss_stride, const SirenGrads* grads, size_t grad_stride,
+                                    const SirenFitPlan& plan, float* work, size_t member_stride, hipStream_t s) {
+  const SirenNet& net = nets.v[0];  // every member has its shape
   const int D = net.d_in, DO = net.d_out, H = net.H, L = net.L, cols = 32;
-  if (n <= 0 || plan.tiles < 1) return hipErrorInvalidValue;
+  if (n <= 0 || plan.tiles < 1 || E < 1 || E > kSirenMaxMembers) return hipErrorInvalidValue;
   hipError_t e;
   const int T = plan.tiles, P = (int)siren_vjp_tile_part_floats(net);
   const size_t layer_stride = (size_t)T * H * cols;
@@ -347,24 +376,54 @@ hipError_t launch_siren_fit(const SirenNet& net, const float* packed, const floa
     const int64_t nc = n - base < per_chunk ? n - base : per_chunk;
     const int tiles = (int)((nc + kSirenTile - 1) / kSirenTile);
     const bool acc = base > 0, last = base + per_chunk >= n;
-    const float* cp = pts + base * D;
-    const float* ct = target + base * DO;
-    const float* cs = scale ? scale + base * DO : nullptr;
-    e = grads ? siren_fit_tile_select<true>(net, packed, packedT, zeros, cp, nc, ct, cs, inv_count, xs, ds, layer_stride, tile_part, P, loss_part, s)
-              : siren_fit_tile_select<false>(net, packed, nullptr, nullptr, cp, nc, ct, cs, inv_count, nullptr, nullptr, 0, nullptr, 0, loss_part, s);
+    FitTileArgs a{};
+    a.packed = packed;
+    a.pts = pts + base * D;
+    a.n = nc;
+    for (int m = 0; m < E; m++) {
+      a.rows.target[m] = rows.target[m] + base * DO;
+      a.rows.scale[m] = rows.scale[m] ? rows.scale[m] + base * DO : nullptr;
+    }
+    a.inv_count = inv_count;
+    a.loss_part = loss_part;
+    a.member_stride = member_stride;
+    if (grads) {
+      a.packedT = packedT;
+      a.zeros = zeros;
+      a.xs = xs;
+      a.ds = ds;
+      a.layer_stride = layer_stride;
+      a.tile_part = tile_part;
+      a.P = P;
+    }
+    e = grads ? siren_fit_tile_select<true>(nets, E, a, s) : siren_fit_tile_select<false>(nets, E, a, s);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(siren_fit_loss_kernel, dim3(1), dim3(256), 0, s, loss_part, tiles, loss, count, acc ? 0 : 1,
-                       last ? 1 : 0);
+    hipLaunchKernelGGL(siren_fit_loss_kernel, dim3(E), dim3(256), 0, s, loss_part, tiles, loss, count, acc ? 0 : 1,
+                       last ? 1 : 0, member_stride, loss_stride);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     if (!grads) continue;
-    if ((e = siren_reduce(tile_part, tiles, P, tile_segs, acc, s)) != hipSuccess) return e;
+    if ((e = siren_reduce_members(tile_part, tiles, P, tile_segs, acc, E, member_stride, grad_stride, s)) != hipSuccess) return e;
     if (L > 0) {
-      if ((e = siren_wgrad(ds, xs, layer_stride, H, 1, tiles, nc, slice_part, L, s)) != hipSuccess) return e;
+      if ((e = siren_wgrad_members(ds, xs, layer_stride, H, 1, tiles, nc, slice_part, L, E, member_stride, s)) != hipSuccess)
+        return e;
       const int slices = (tiles + kSirenWgradSliceBlocks - 1) / kSirenWgradSliceBlocks;
-      if ((e = siren_reduce(slice_part, slices, (size_t)L * H * H, slice_segs, acc, s)) != hipSuccess) return e;
+      if ((e = siren_reduce_members(slice_part, slices, (size_t)L * H * H, slice_segs, acc, E, member_stride, grad_stride, s)) !=
+          hipSuccess)
+        return e;
     }
   }
   return hipSuccess;
+}
+
+hipError_t launch_siren_fit(const SirenNet& net, const float* packed, const float* packedT, const float* zeros,
+                            const float* pts, int64_t n, const float* target, const float* scale, float* loss,
+                            const SirenGrads* grads, const SirenFitPlan& plan, float* work, hipStream_t s) {
+  SirenNets nets{};
+  nets.v[0] = net;
+  SirenMemberRows rows{};
+  rows.target[0] = target;
+  rows.scale[0] = scale;
+  return launch_siren_fit_members(nets, 1, packed, packedT, zeros, pts, n, rows, loss, 0, grads, 0, plan, work, 0, s);
 }
 
 }  // namespace wos

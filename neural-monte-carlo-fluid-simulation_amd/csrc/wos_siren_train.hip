@@ -6,15 +6,22 @@
 // amsgrad, weight decay and maximize off: f32, one operation per rounding (-ffp-contract=off), the
 // five step scalars rounded once from double on the host.  clip_grad_norm_'s norm is one workgroup's
 // sum in a fixed order, so the same call gives the same bits.  The gradients are read, never written.
+//
+// Every kernel here has a member axis (wos_siren_fit_run_ensemble; DESIGN.md "Ensemble fit loops"): a
+// launch covers the E <= kSirenMaxMembers networks of an ensemble, each block working on its member's
+// own tensors exactly as the single-network launch, E = 1, does.
 #include "wos_siren.h"
 
 namespace wos {
 
 // S = sum g^2 over the flat order of the tensors: thread t chains acc = acc + g[e] * g[e] over
 // e = t, t + 256, ... (the product rounded, then the sum), the 256 chains' sums pairwise (t, t + 128),
-// (t, t + 64), ... -- siren_fit_loss_kernel's shape.  norm[0] = sqrtf(S).
-__global__ __launch_bounds__(256) void adam_norm_kernel(const AdamSegs segs, float* __restrict__ norm) {
+// (t, t + 64), ... -- siren_fit_loss_kernel's shape.  norm[0] = sqrtf(S).  One workgroup per member:
+// its norm goes to norm[blockIdx.x * kFitStateWords].
+__global__ __launch_bounds__(256) void adam_norm_kernel(const AdamMembers members, float* __restrict__ norm) {
   __shared__ float sm[256];
+  const AdamSegs& segs = members.segs[blockIdx.x];
+  norm += blockIdx.x * kFitStateWords;
   const int tid = threadIdx.x;
   float acc = 0.0f;
   for (int k = 0; k < segs.n; k++) {  // a thread's elements of tensor k follow its elements of tensor k - 1
@@ -39,11 +46,17 @@ __global__ __launch_bounds__(256) void adam_norm_kernel(const AdamSegs segs, flo
 
 // One launch over all tensors; element e of the flat order belongs to the tensor k with
 // end[k - 1] <= e < end[k].  norm null: no clipping and no multiply.  stop non-null and set: a no-op.
-__global__ __launch_bounds__(256) void adam_update_kernel(const AdamSegs segs, float* __restrict__ m_all,
-                                                         float* __restrict__ v_all, const AdamScalars sc,
+// Grid y is the member: its tensors and moments from `members`, its norm and stop words
+// blockIdx.y * kFitStateWords further on.
+__global__ __launch_bounds__(256) void adam_update_kernel(const AdamMembers members, const AdamScalars sc,
                                                          const float* __restrict__ norm,
                                                          const int* __restrict__ stop) {
-  if (stop && stop[0] != 0) return;
+  const int member = blockIdx.y;
+  const AdamSegs& segs = members.segs[member];
+  float* __restrict__ m_all = members.exp_avg[member];
+  float* __restrict__ v_all = members.exp_avg_sq[member];
+  if (norm) norm += member * kFitStateWords;
+  if (stop && stop[member * kFitStateWords] != 0) return;
   const int64_t total = segs.end[segs.n - 1];
   float c = 1.0f;
   if (norm) {
@@ -91,46 +104,94 @@ __device__ __forceinline__ void fit_run_commit(int* state, int64_t iter, float s
   if (stop_loss >= 0.0f && loss <= stop_loss) state[0] = 1;
 }
 
-__global__ void fit_run_commit_kernel(int* state, int64_t iter, float stop_loss, float* losses, long long* status) {
-  if (blockIdx.x == 0 && threadIdx.x == 0) fit_run_commit(state, iter, stop_loss, losses, status);
+// thread e commits member e: its state words, its row of losses and its status pair
+__global__ void fit_run_commit_kernel(int n_members, int* state, int64_t iter, float stop_loss, float* losses,
+                                      int64_t losses_stride, long long* status) {
+  const int e = threadIdx.x;
+  if (blockIdx.x == 0 && e < n_members)
+    fit_run_commit(state + e * kFitStateWords, iter, stop_loss, losses + e * losses_stride, status + 2 * e);
 }
 
 // Rows idx[j] of the pool into the batch buffers; an index outside [0, n_pool) is clamped and
 // counted in status[1].  Thread 0 also commits iteration `prev` (prev < 0: nothing to commit).
+// Grid y is the member: it gathers its own pool's target and scale into target / scale +
+// member * rows_stride and commits its own state, losses and status; the points are shared, and
+// member 0 writes them.
 template <int D>
-__global__ __launch_bounds__(256) void fit_run_gather_kernel(const float* __restrict__ pool_pts,
-                                                            const float* __restrict__ pool_target,
-                                                            const float* __restrict__ pool_scale, int64_t n_pool,
-                                                            const long long* __restrict__ idx, int64_t batch, int d_out,
-                                                            float* __restrict__ pts, float* __restrict__ target,
-                                                            float* __restrict__ scale, int* state, int64_t prev,
-                                                            float stop_loss, float* losses, long long* status) {
+__global__ __launch_bounds__(256) void fit_run_gather_kernel(const float* __restrict__ pool_pts, const FitPools pools,
+                                                            int64_t n_pool, const long long* __restrict__ idx,
+                                                            int64_t batch, int d_out, float* __restrict__ pts,
+                                                            float* __restrict__ target, float* __restrict__ scale,
+                                                            size_t rows_stride, int* state, int64_t prev,
+                                                            float stop_loss, float* losses, int64_t losses_stride,
+                                                            long long* status) {
+  const int member = blockIdx.y;
+  const float* __restrict__ pool_target = pools.target[member];
+  const float* __restrict__ pool_scale = pools.scale[member];
+  target += member * rows_stride;
+  scale += member * rows_stride;
+  status += 2 * member;
   const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (j == 0 && prev >= 0) fit_run_commit(state, prev, stop_loss, losses, status);
+  if (j == 0 && prev >= 0)
+    fit_run_commit(state + member * kFitStateWords, prev, stop_loss, losses + member * losses_stride, status);
   if (j >= batch) return;
   long long r = idx[j];
   if (r < 0 || r >= n_pool) {
     atomicAdd((unsigned long long*)&status[1], 1ull);
     r = r < 0 ? 0 : n_pool - 1;
   }
+  if (member == 0) {
 #pragma unroll
-  for (int k = 0; k < D; k++) pts[j * D + k] = pool_pts[r * D + k];
+    for (int k = 0; k < D; k++) pts[j * D + k] = pool_pts[r * D + k];
+  }
   for (int i = 0; i < d_out; i++) {
     target[j * d_out + i] = pool_target[r * d_out + i];
     if (pool_scale) scale[j * d_out + i] = pool_scale[r * d_out + i];
   }
 }
 
-hipError_t launch_adam_norm(const AdamSegs& segs, float* norm, hipStream_t s) {
-  hipLaunchKernelGGL(adam_norm_kernel, dim3(1), dim3(256), 0, s, segs, norm);
+hipError_t launch_adam_norm_members(const AdamMembers& m, int E, float* norm, hipStream_t s) {
+  hipLaunchKernelGGL(adam_norm_kernel, dim3(E), dim3(256), 0, s, m, norm);
   return hipGetLastError();
+}
+
+hipError_t launch_adam_update_members(const AdamMembers& m, int E, const AdamScalars& sc, const float* norm,
+                                      const int* stop, hipStream_t s) {
+  const AdamSegs& segs = m.segs[0];  // every member's tensors have member 0's counts
+  const int64_t total = segs.end[segs.n - 1], blocks = (total + 255) / 256;
+  const unsigned grid = (unsigned)(blocks < (1 << 20) ? blocks : (1 << 20));  // grid-stride past 2^28 elements
+  hipLaunchKernelGGL(adam_update_kernel, dim3(grid, E), dim3(256), 0, s, m, sc, norm, stop);
+  return hipGetLastError();
+}
+
+hipError_t launch_adam_norm(const AdamSegs& segs, float* norm, hipStream_t s) {
+  AdamMembers m{};
+  m.segs[0] = segs;
+  return launch_adam_norm_members(m, 1, norm, s);
 }
 
 hipError_t launch_adam_update(const AdamSegs& segs, float* exp_avg, float* exp_avg_sq, const AdamScalars& sc,
                               const float* norm, const int* stop, hipStream_t s) {
-  const int64_t total = segs.end[segs.n - 1], blocks = (total + 255) / 256;
-  const unsigned grid = (unsigned)(blocks < (1 << 20) ? blocks : (1 << 20));  // grid-stride past 2^28 elements
-  hipLaunchKernelGGL(adam_update_kernel, dim3(grid), dim3(256), 0, s, segs, exp_avg, exp_avg_sq, sc, norm, stop);
+  AdamMembers m{};
+  m.segs[0] = segs;
+  m.exp_avg[0] = exp_avg;
+  m.exp_avg_sq[0] = exp_avg_sq;
+  return launch_adam_update_members(m, 1, sc, norm, stop, s);
+}
+
+hipError_t launch_fit_run_gather_members(int d_in, int d_out, int E, const float* pool_pts, const FitPools& pools,
+                                         int64_t n_pool, const int64_t* idx, int64_t batch, float* pts, float* target,
+                                         float* scale, size_t rows_stride, int* state, int64_t prev, float stop_loss,
+                                         float* losses, int64_t losses_stride, int64_t* status, hipStream_t s) {
+  const dim3 grid((unsigned)((batch + 255) / 256), E);
+  if (d_in == 2)
+    hipLaunchKernelGGL(fit_run_gather_kernel<2>, grid, dim3(256), 0, s, pool_pts, pools, n_pool, (const long long*)idx,
+                       batch, d_out, pts, target, scale, rows_stride, state, prev, stop_loss, losses, losses_stride,
+                       (long long*)status);
+  else
+    hipLaunchKernelGGL(fit_run_gather_kernel<3>, grid, dim3(256), 0, s, pool_pts, pools, n_pool, (const long long*)idx,
+                       batch, d_out, pts, target, scale, rows_stride, state, prev, stop_loss, losses, losses_stride,
+                       (long long*)status);
   return hipGetLastError();
 }
 
@@ -138,22 +199,23 @@ hipError_t launch_fit_run_gather(int d_in, int d_out, const float* pool_pts, con
                                  const float* pool_scale, int64_t n_pool, const int64_t* idx, int64_t batch, float* pts,
                                  float* target, float* scale, int* state, int64_t prev, float stop_loss, float* losses,
                                  int64_t* status, hipStream_t s) {
-  const dim3 grid((unsigned)((batch + 255) / 256));
-  if (d_in == 2)
-    hipLaunchKernelGGL(fit_run_gather_kernel<2>, grid, dim3(256), 0, s, pool_pts, pool_target, pool_scale, n_pool,
-                       (const long long*)idx, batch, d_out, pts, target, scale, state, prev, stop_loss, losses,
-                       (long long*)status);
-  else
-    hipLaunchKernelGGL(fit_run_gather_kernel<3>, grid, dim3(256), 0, s, pool_pts, pool_target, pool_scale, n_pool,
-                       (const long long*)idx, batch, d_out, pts, target, scale, state, prev, stop_loss, losses,
-                       (long long*)status);
+  FitPools pools{};
+  pools.target[0] = pool_target;
+  pools.scale[0] = pool_scale;
+  return launch_fit_run_gather_members(d_in, d_out, 1, pool_pts, pools, n_pool, idx, batch, pts, target, scale, 0, state, prev,
+                                       stop_loss, losses, 0, status, s);
+}
+
+hipError_t launch_fit_run_commit_members(int E, int* state, int64_t iter, float stop_loss, float* losses,
+                                         int64_t losses_stride, int64_t* status, hipStream_t s) {
+  hipLaunchKernelGGL(fit_run_commit_kernel, dim3(1), dim3(64), 0, s, E, state, iter, stop_loss, losses, losses_stride,
+                     (long long*)status);
   return hipGetLastError();
 }
 
 hipError_t launch_fit_run_commit(int* state, int64_t iter, float stop_loss, float* losses, int64_t* status,
                                  hipStream_t s) {
-  hipLaunchKernelGGL(fit_run_commit_kernel, dim3(1), dim3(64), 0, s, state, iter, stop_loss, losses, (long long*)status);
-  return hipGetLastError();
+  return launch_fit_run_commit_members(1, state, iter, stop_loss, losses, 0, status, s);
 }
 
 }  // namespace wos

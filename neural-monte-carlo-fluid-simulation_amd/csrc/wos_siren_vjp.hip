@@ -30,7 +30,11 @@
 
 namespace wos {
 
-__global__ __launch_bounds__(256) void siren_pack_transposed_kernel(const SirenNet net, float* __restrict__ packed) {
+// grid y: the member, as in siren_pack_kernel
+__global__ __launch_bounds__(256) void siren_pack_transposed_kernel(const SirenNets nets, float* __restrict__ packed,
+                                                                   size_t member_stride) {
+  const SirenNet& net = nets.v[blockIdx.y];
+  packed += blockIdx.y * member_stride;
   const int H = net.H, Q = H >> 3;
   const size_t per = (size_t)H * H, total = per * net.L;
   for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
@@ -279,22 +283,22 @@ __global__ __launch_bounds__(256) void siren_vjp_tile_kernel(const SirenNet net,
 
 // dW = A B^T over K: A = ds + z * layer_stride, B = xs + z * layer_stride, both [T][H][cols] with
 // K = (tile, column).  Workgroup (x: output tile of 128 x 128, y: slice of kSirenWgradSliceBlocks
-// 32-column blocks, z: layer); wave (wr, wc) owns 64 x 64 of it as 2 x 2 MFMA tiles.  A block of
+// 32-column blocks, z: layer, and above it the member, whose ds, xs and part lie member_stride apart); wave (wr, wc) owns 64 x 64 of it as 2 x 2 MFMA tiles.  A block of
 // K is staged in LDS as [128][33]: stored along K (32 banks a row), read down the rows at stride
 // 33 (32 banks again).  Columns of points past n_valid are read as zero.
 constexpr int kWgradTile = 128, kWgradPitch = 33;
 
 __global__ __launch_bounds__(256) void siren_wgrad_kernel(const float* __restrict__ ds, const float* __restrict__ xs,
                                                          size_t layer_stride, int H, int C, int n_kb, int64_t n_valid,
-                                                         float* __restrict__ part, int L) {
+                                                         float* __restrict__ part, int L, size_t member_stride) {
   __shared__ float As[kWgradTile * kWgradPitch];
   __shared__ float Bs[kWgradTile * kWgradPitch];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = tid & 31, half = lane >> 5;
   const int TB = (H + kWgradTile - 1) / kWgradTile;
   const int tr = blockIdx.x / TB, tc = blockIdx.x - tr * TB;
-  const int lz = blockIdx.z, cols = C * 32;
-  const float* A = ds + (size_t)lz * layer_stride;
-  const float* B = xs + (size_t)lz * layer_stride;
+  const int member = blockIdx.z / L, lz = blockIdx.z - member * L, cols = C * 32;  // grid z = member * L + layer
+  const float* A = ds + member * member_stride + (size_t)lz * layer_stride;
+  const float* B = xs + member * member_stride + (size_t)lz * layer_stride;
   const int wr = wave >> 1, wc = wave & 1;
   const int row0 = tr * kWgradTile + 64 * wr, col0 = tc * kWgradTile + 64 * wc;
   const bool busy = row0 < H && col0 < H;  // wave-uniform
@@ -346,7 +350,7 @@ __global__ __launch_bounds__(256) void siren_wgrad_kernel(const float* __restric
     __syncthreads();
   }
   if (!busy) return;
-  float* out = part + ((size_t)blockIdx.y * L + lz) * H * H;
+  float* out = part + member * member_stride + ((size_t)blockIdx.y * L + lz) * H * H;
 #pragma unroll
   for (int a = 0; a < 2; a++)
 #pragma unroll
@@ -364,8 +368,10 @@ __global__ __launch_bounds__(256) void siren_wgrad_kernel(const float* __restric
 // per element: thread y adds the partials i = y, y + 8, ... as a chain, then thread 0 adds the
 // eight chains' sums in the order y = 0 .. 7.  The order depends on n_part alone.
 __global__ __launch_bounds__(256) void siren_reduce_kernel(const float* __restrict__ part, int n_part, size_t stride,
-                                                          const SirenReduceSegs segs, int count, int accumulate) {
+                                                          const SirenReduceSegs segs, int count, int accumulate,
+                                                          size_t part_member_stride, size_t dst_member_stride) {
   __shared__ float sm[8][33];
+  part += blockIdx.y * part_member_stride;  // grid y: the member
   const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
   const int e = blockIdx.x * 32 + tx;
   float s = 0.0f;
@@ -381,7 +387,7 @@ __global__ __launch_bounds__(256) void siren_reduce_kernel(const float* __restri
 #pragma unroll
   for (int k = 0; k < kReduceSegs; k++) {
     const int begin = k == 0 ? 0 : segs.end[k - 1];
-    if (k < segs.n && e >= begin && e < segs.end[k]) out = segs.dst[k] + (e - begin);
+    if (k < segs.n && e >= begin && e < segs.end[k]) out = segs.dst[k] + blockIdx.y * dst_member_stride + (e - begin);
   }
   if (out) *out = accumulate ? *out + total : total;
 }
@@ -402,12 +408,19 @@ __global__ __launch_bounds__(256) void siren_vjp_image_kernel(const float* __res
 
 size_t siren_vjp_tile_lds_bytes(int d_in, int H) { return ((size_t)(H + 3) * (1 + d_in) * 32 + d_in * 32) * sizeof(float); }
 
-hipError_t launch_siren_pack_transposed(const SirenNet& net, float* packedT, hipStream_t s) {
-  const size_t total = siren_pack_floats(net.H, net.L);
+hipError_t launch_siren_pack_transposed_members(const SirenNets& nets, int E, float* packedT, size_t member_stride,
+                                                hipStream_t s) {
+  const size_t total = siren_pack_floats(nets.v[0].H, nets.v[0].L);
   if (total == 0) return hipSuccess;
   const unsigned grid = (unsigned)((total + 255) / 256);
-  hipLaunchKernelGGL(siren_pack_transposed_kernel, dim3(grid), dim3(256), 0, s, net, packedT);
+  hipLaunchKernelGGL(siren_pack_transposed_kernel, dim3(grid, E), dim3(256), 0, s, nets, packedT, member_stride);
   return hipGetLastError();
+}
+
+hipError_t launch_siren_pack_transposed(const SirenNet& net, float* packedT, hipStream_t s) {
+  SirenNets nets{};
+  nets.v[0] = net;
+  return launch_siren_pack_transposed_members(nets, 1, packedT, 0, s);
 }
 
 SirenVjpPlan siren_vjp_plan(const SirenNet& net, int64_t n, size_t stash_cap_bytes, int resident_tiles) {
@@ -428,21 +441,31 @@ SirenVjpPlan siren_vjp_plan(const SirenNet& net, int64_t n, size_t stash_cap_byt
   return p;
 }
 
+hipError_t siren_reduce_members(const float* part, int n_part, size_t stride, const SirenReduceSegs& segs, bool accumulate,
+                                int E, size_t part_member_stride, size_t dst_member_stride, hipStream_t s) {
+  const int count = segs.end[segs.n - 1];
+  hipLaunchKernelGGL(siren_reduce_kernel, dim3((unsigned)((count + 31) / 32), E), dim3(256), 0, s, part, n_part, stride,
+                     segs, count, accumulate ? 1 : 0, part_member_stride, dst_member_stride);
+  return hipGetLastError();
+}
+
 hipError_t siren_reduce(const float* part, int n_part, size_t stride, const SirenReduceSegs& segs, bool accumulate,
                         hipStream_t s) {
-  const int count = segs.end[segs.n - 1];
-  hipLaunchKernelGGL(siren_reduce_kernel, dim3((unsigned)((count + 31) / 32)), dim3(256), 0, s, part, n_part, stride,
-                     segs, count, accumulate ? 1 : 0);
+  return siren_reduce_members(part, n_part, stride, segs, accumulate, 1, 0, 0, s);
+}
+
+hipError_t siren_wgrad_members(const float* ds, const float* xs, size_t layer_stride, int H, int C, int tiles,
+                               int64_t n_valid, float* part, int L, int E, size_t member_stride, hipStream_t s) {
+  const int TB = (H + kWgradTile - 1) / kWgradTile, n_kb = tiles * C;
+  const int slices = (n_kb + kSirenWgradSliceBlocks - 1) / kSirenWgradSliceBlocks;
+  hipLaunchKernelGGL(siren_wgrad_kernel, dim3(TB * TB, slices, L * E), dim3(256), 0, s, ds, xs, layer_stride, H, C, n_kb,
+                     n_valid, part, L, member_stride);
   return hipGetLastError();
 }
 
 hipError_t siren_wgrad(const float* ds, const float* xs, size_t layer_stride, int H, int C, int tiles, int64_t n_valid,
                        float* part, int L, hipStream_t s) {
-  const int TB = (H + kWgradTile - 1) / kWgradTile, n_kb = tiles * C;
-  const int slices = (n_kb + kSirenWgradSliceBlocks - 1) / kSirenWgradSliceBlocks;
-  hipLaunchKernelGGL(siren_wgrad_kernel, dim3(TB * TB, slices, L), dim3(256), 0, s, ds, xs, layer_stride, H, C, n_kb,
-                     n_valid, part, L);
-  return hipGetLastError();
+  return siren_wgrad_members(ds, xs, layer_stride, H, C, tiles, n_valid, part, L, 1, 0, s);
 }
 
 template <int D, int RT>

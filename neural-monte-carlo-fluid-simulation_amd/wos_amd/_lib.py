@@ -137,6 +137,7 @@ EXPORTS = (
     "wos_siren_vjp", "wos_selftest_siren_vjp_layer",
     "wos_siren_fit",
     "wos_adam_step", "wos_siren_fit_run", "wos_siren_fit_run_batches",
+    "wos_siren_fit_run_ensemble", "wos_siren_fit_run_batches_ensemble",
     "wos_set_length_hints", "wos_length_hint_stats", "wos_selftest_hint_key",
 )
 
@@ -267,6 +268,18 @@ def load():
                                                 C.POINTER(C.c_int64), C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
                                                 C.POINTER(AdamParams), C.c_float, C.c_int32, C.c_void_p, C.c_void_p,
                                                 C.c_size_t, C.c_uint32, C.c_int32, C.c_void_p]
+    if hasattr(L, "wos_siren_fit_run_ensemble"):  # additive within ABI 10 as well
+        ptrs = C.POINTER(C.c_void_p)  # a host array of device pointers, one per member
+        L.wos_siren_fit_run_ensemble.restype = C.c_int
+        L.wos_siren_fit_run_ensemble.argtypes = [C.c_int32, C.POINTER(SirenNet), C.c_void_p, ptrs, ptrs, C.c_int64,
+                                                 C.c_void_p, C.c_int64, C.c_int64, ptrs, ptrs, C.c_int64,
+                                                 C.POINTER(AdamParams), C.c_float, C.c_int32, C.c_void_p, C.c_void_p,
+                                                 C.c_size_t, C.c_uint32, C.c_int32, C.c_void_p]
+        L.wos_siren_fit_run_batches_ensemble.restype = C.c_int
+        L.wos_siren_fit_run_batches_ensemble.argtypes = [C.c_int32, C.POINTER(SirenNet), C.c_void_p, ptrs, ptrs,
+                                                         C.POINTER(C.c_int64), C.c_int64, ptrs, ptrs, C.c_int64,
+                                                         C.POINTER(AdamParams), C.c_float, C.c_int32, C.c_void_p,
+                                                         C.c_void_p, C.c_size_t, C.c_uint32, C.c_int32, C.c_void_p]
     L.wos_selftest_siren_vjp_layer.restype = C.c_int
     L.wos_selftest_siren_vjp_layer.argtypes = [C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                                C.c_void_p, C.c_void_p, C.c_int32]

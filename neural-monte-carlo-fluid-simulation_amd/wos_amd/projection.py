@@ -448,6 +448,52 @@ class PressureProjector:
                 break
         return torch.cat(losses), state
 
+    def fit_projection_ensemble(self, networks, networks_prev, grad_p, n_samples, n_iters, *, states=None, wraps=None,
+                                generator=None, early_stop=None, iters_per_call=256, lr=1e-4):
+        """fit_projection for the E <= 4 members of an ensemble after one multi-channel solve, trained in
+        one device loop (wos_amd.siren.fit_run_ensemble).  networks and networks_prev are lists of E
+        networks of one shape, grad_p the (E, N, dim) of solve() on an (E, ...) source; states and wraps,
+        when given, lists with one entry per member (an entry of wraps may be None).  The members share
+        the sample pool and the index draw: one torch.randint(0, hi, (n_samples,)) per iteration serves
+        all of them -- common random numbers, as the solve's walks are.  Member e equals fit_projection
+        on (networks[e], networks_prev[e], grad_p[e]) with a generator seeded alike, bit for bit, as
+        long as no member has stopped early: a stopped member leaves the later blocks (its network
+        frozen, its losses NaN) while the others go on, and no further block is drawn once every member
+        has stopped.  EVERY NETWORK IS UPDATED IN PLACE.  Returns (losses [E, n_iters], states)."""
+        who = "fit_projection_ensemble"
+        n_iters, per_call = int(n_iters), int(iters_per_call)
+        if n_iters < 1 or per_call < 1:
+            raise ValueError(f"{who}: n_iters and iters_per_call must be positive, got {n_iters}, {per_call}")
+        networks = list(networks)
+        E = len(networks)
+        if not 1 <= E <= _siren.MAX_MEMBERS:
+            raise ValueError(f"{who}: an ensemble has 1..{_siren.MAX_MEMBERS} members, got {E}")
+        prevs, wraps = _per_member(who, "networks_prev", list(networks_prev), E), _per_member(who, "wraps", wraps, E)
+        n = self.samples.shape[0]
+        if tuple(grad_p.shape) != (E, n, self.dim):
+            raise ValueError(f"{who}: grad_p must be {(E, n, self.dim)}, a multi-channel solve's, got {tuple(grad_p.shape)}")
+        states = [_siren.AdamState(net, lr=lr) for net in networks] if states is None else _per_member(who, "states", states, E)
+        stop = _stop_loss(early_stop)
+        hi = n - 1 if self.dim == 2 else n
+        targets, scales = [], []
+        with torch.no_grad():
+            for e in range(E):
+                u_prev = _siren.eval(prevs[e], self.samples)
+                if wraps[e] is None:
+                    scale, target = None, u_prev - grad_p[e]
+                else:
+                    scale, offset = _diagonal(wraps[e], self.samples, u_prev.shape[-1])
+                    target = wraps[e](self.samples, u_prev) - grad_p[e] - offset
+                targets.append(target)
+                scales.append(scale)
+
+        def run_block(first, k, live):
+            idx = torch.stack([torch.randint(0, hi, (n_samples,), device=self.device, generator=generator)
+                               for _ in range(k)])
+            return _siren.fit_run_ensemble([networks[e] for e in live], [states[e] for e in live], self.samples,
+                                           [targets[e] for e in live], [scales[e] for e in live], idx, stop_loss=stop)
+        return _ensemble_blocks(who, networks, states, n_iters, per_call, stop, run_block), states
+
 
 _checked_wraps = weakref.WeakSet()
 
@@ -501,6 +547,38 @@ def _advection_target(network_prev, x, dt, size, network_tilde, wrap):
     return target, scale
 
 
+def _advection_block(who, first, k, d, dev, size, n_samples, samples, keep, generator):
+    """The points of iterations first .. first + k - 1 of an advection fit, flattened, and their row
+    counts: (x [sum(counts), d], counts).  fit_advection's rules for n_samples, samples and keep."""
+    if samples is None:
+        x = torch.stack([torch.rand(int(n_samples), d, device=dev, generator=generator) for _ in range(k)])
+        for c in range(d):
+            x[..., c] = x[..., c] * (size[2 * c + 1] - size[2 * c]) + size[2 * c]
+    else:
+        x = samples(k)
+        if x.dim() != 3 or x.shape[0] != k or x.shape[1] < 1 or x.shape[2] != d:
+            raise ValueError(f"{who}: samples({k}) must return [{k}, n, {d}], got shape {tuple(x.shape)}")
+        x = x.detach()
+    n = int(x.shape[1])
+    x = x.reshape(k * n, d)
+    if keep is None:
+        counts = [n] * k
+    else:
+        mask = keep(x)
+        if mask.dtype != torch.bool or tuple(mask.shape) != (k * n,):
+            raise ValueError(f"{who}: keep must return a bool mask of shape {(k * n,)}, got {mask.dtype} "
+                             f"{tuple(mask.shape)}")
+        counts = mask.reshape(k, n).sum(dim=1).tolist()  # the block's one host synchronisation
+        for i, c in enumerate(counts):
+            if c < 1:
+                raise ValueError(f"{who}: keep left iteration {first + i} without a point (its loss is a mean "
+                                 f"over nothing); the network and the state are as the {first} iterations before this "
+                                 f"block left them")
+        # the kept rows in their order; the size is known, so this does not wait for the device again
+        x = x[torch.nonzero_static(mask, size=sum(counts)).squeeze(1)]
+    return x, counts
+
+
 def fit_advection(network, network_prev, dt, size, n_iters, *, n_samples=None, samples=None, network_tilde=None,
                   wrap=None, keep=None, state=None, generator=None, early_stop=None, iters_per_call=256, lr=1e-4):
     """The whole training loop of _advect_velocity (n_iters iterations of advection_fit_loss, backward
@@ -552,32 +630,7 @@ def fit_advection(network, network_prev, dt, size, n_iters, *, n_samples=None, s
     losses = []
     for first in range(0, n_iters, per_call):
         k = min(per_call, n_iters - first)
-        if samples is None:
-            x = torch.stack([torch.rand(int(n_samples), d, device=dev, generator=generator) for _ in range(k)])
-            for c in range(d):
-                x[..., c] = x[..., c] * (size[2 * c + 1] - size[2 * c]) + size[2 * c]
-        else:
-            x = samples(k)
-            if x.dim() != 3 or x.shape[0] != k or x.shape[1] < 1 or x.shape[2] != d:
-                raise ValueError(f"fit_advection: samples({k}) must return [{k}, n, {d}], got shape {tuple(x.shape)}")
-            x = x.detach()
-        n = int(x.shape[1])
-        x = x.reshape(k * n, d)
-        if keep is None:
-            counts = [n] * k
-        else:
-            mask = keep(x)
-            if mask.dtype != torch.bool or tuple(mask.shape) != (k * n,):
-                raise ValueError(f"fit_advection: keep must return a bool mask of shape {(k * n,)}, got {mask.dtype} "
-                                 f"{tuple(mask.shape)}")
-            counts = mask.reshape(k, n).sum(dim=1).tolist()  # the block's one host synchronisation
-            for i, c in enumerate(counts):
-                if c < 1:
-                    raise ValueError(f"fit_advection: keep left iteration {first + i} without a point (its loss is a mean "
-                                     f"over nothing); the network and the state are as the {first} iterations before this "
-                                     f"block left them")
-            # the kept rows in their order; the size is known, so this does not wait for the device again
-            x = x[torch.nonzero_static(mask, size=sum(counts)).squeeze(1)]
+        x, counts = _advection_block("fit_advection", first, k, d, dev, size, n_samples, samples, keep, generator)
         target, scale = _advection_target(network_prev, x, dt, size, network_tilde, wrap)
         block, status = _siren.fit_run_batches(network, state, x, target, scale, counts, stop_loss=stop)
         losses.append(block)
@@ -591,3 +644,85 @@ def fit_advection(network, network_prev, dt, size, n_iters, *, n_samples=None, s
                 losses.append(torch.full((n_iters - first - k,), float("nan"), dtype=block.dtype, device=block.device))
             break
     return torch.cat(losses), state
+
+
+def _stop_loss(early_stop):
+    return None if early_stop is None or early_stop is False else (1.1e-10 if early_stop is True else float(early_stop))
+
+
+def _per_member(who, name, values, E):
+    """A per-member argument as a list of E entries (None: E times None)."""
+    if values is None:
+        return [None] * E
+    values = list(values)
+    if len(values) != E:
+        raise ValueError(f"{who}: {name} must hold one entry per member ({E}), got {len(values)}")
+    return values
+
+
+def _ensemble_blocks(who, networks, states, n_iters, per_call, stop, run_block):
+    """The block loop of the two ensemble fits.  run_block(first, k, live) -> (block [len(live), k],
+    status [len(live), 2]) trains the members `live` (indices into networks) for iterations
+    first .. first + k - 1.  A member that has stopped leaves the later blocks, so its network stays
+    as the stop left it and its losses stay NaN; no block is run once every member has stopped."""
+    E = len(networks)
+    live = list(range(E))
+    losses = None
+    for first in range(0, n_iters, per_call):
+        k = min(per_call, n_iters - first)
+        block, status = run_block(first, k, live)
+        if losses is None:
+            losses = torch.full((E, n_iters), float("nan"), dtype=block.dtype, device=block.device)
+        losses[live, first:first + k] = block
+        if stop is None:
+            continue
+        # as in fit_projection: a stop at the block's last iteration leaves status[e][0] == k, and the last
+        # applied loss tells, by the device's own test
+        applied = status[:, 0].tolist()
+        last = block[torch.arange(len(live)), torch.tensor(applied) - 1].tolist()
+        live = [e for e, a, loss in zip(live, applied, last) if not (a < k or loss <= float(np.float32(stop)))]
+        if not live:
+            break
+    return losses
+
+
+def fit_advection_ensemble(networks, networks_prev, dt, size, n_iters, *, n_samples=None, samples=None, networks_tilde=None,
+                           wraps=None, keep=None, states=None, generator=None, early_stop=None, iters_per_call=256, lr=1e-4):
+    """fit_advection for the E <= 4 members of an ensemble on one obstacle mesh, trained in one device
+    loop (wos_amd.siren.fit_run_batches_ensemble).  networks, networks_prev and, when given,
+    networks_tilde, wraps and states are lists with one entry per member (an entry of wraps or of
+    networks_tilde may be None).  The members share the points -- one torch.rand per iteration, or one
+    samples(k), serves all of them -- and one `keep` filter, so the row counts are common; the previous
+    networks and wraps are evaluated per member, each in one launch over the block's rows, as
+    fit_advection does.  Member e equals fit_advection on member e with a generator seeded alike, bit
+    for bit, as long as no member has stopped early: a stopped member leaves the later blocks (its
+    network frozen, its losses NaN) while the others go on, and no further block is drawn once every
+    member has stopped.  EVERY NETWORK IS UPDATED IN PLACE.  Returns (losses [E, n_iters], states)."""
+    who = "fit_advection_ensemble"
+    n_iters, per_call = int(n_iters), int(iters_per_call)
+    if n_iters < 1 or per_call < 1:
+        raise ValueError(f"{who}: n_iters and iters_per_call must be positive, got {n_iters}, {per_call}")
+    if (n_samples is None) == (samples is None):
+        raise ValueError(f"{who}: give exactly one of n_samples (torch.rand points per iteration) and samples "
+                         "(a callable samples(k) -> [k, n, d_in])")
+    if n_samples is not None and int(n_samples) < 1:
+        raise ValueError(f"{who}: n_samples must be positive, got {n_samples}")
+    networks = list(networks)
+    E = len(networks)
+    if not 1 <= E <= _siren.MAX_MEMBERS:
+        raise ValueError(f"{who}: an ensemble has 1..{_siren.MAX_MEMBERS} members, got {E}")
+    prevs, tildes = _per_member(who, "networks_prev", list(networks_prev), E), _per_member(who, "networks_tilde", networks_tilde, E)
+    wraps = _per_member(who, "wraps", wraps, E)
+    p = _siren.pack(networks[0])
+    d, dev = p.d_in, p.weights[0].device
+    if len(size) != 2 * d:
+        raise ValueError(f"{who}: size must hold {2 * d} bounds for {d} coordinates, got {len(size)}")
+    states = [_siren.AdamState(net, lr=lr) for net in networks] if states is None else _per_member(who, "states", states, E)
+    stop = _stop_loss(early_stop)
+
+    def run_block(first, k, live):
+        x, counts = _advection_block(who, first, k, d, dev, size, n_samples, samples, keep, generator)
+        rows = [_advection_target(prevs[e], x, dt, size, tildes[e], wraps[e]) for e in live]
+        return _siren.fit_run_batches_ensemble([networks[e] for e in live], [states[e] for e in live], x,
+                                               [t for t, _ in rows], [sc for _, sc in rows], counts, stop_loss=stop)
+    return _ensemble_blocks(who, networks, states, n_iters, per_call, stop, run_block), states

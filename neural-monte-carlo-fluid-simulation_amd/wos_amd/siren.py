@@ -28,6 +28,7 @@ from ._lib import check
 
 MAX_HIDDEN = 256          # csrc/wos_siren.h kSirenMaxHidden
 MAX_HIDDEN_LAYERS = 8     # csrc/wos_siren.h kSirenMaxHiddenLayers
+MAX_MEMBERS = 4           # csrc/wos_siren.h kSirenMaxMembers: the members of an ensemble fit loop
 
 PackedSiren = collections.namedtuple("PackedSiren", "d_in d_out hidden n_hidden_layers omega weights biases")
 
@@ -646,24 +647,39 @@ def fit_run(net, state, pool_x, pool_target, pool_scale, idx, *, stop_loss=None,
         raise ValueError(f"siren.fit_run: idx must be a contiguous int64 tensor [K, batch] on {dev}")
     K, batch = int(idx.shape[0]), int(idx.shape[1])
 
-    def call(L, net, *rest):
-        return L.wos_siren_fit_run(net, xs.data_ptr(), t.data_ptr(), None if sc is None else sc.data_ptr(), n_pool,
+    def call(L, head, *rest):
+        return L.wos_siren_fit_run(*head, xs.data_ptr(), t.data_ptr(), None if sc is None else sc.data_ptr(), n_pool,
                                    idx.data_ptr(), K, batch, *rest)
     return _run_loop("fit_run", "pool is", p, state, dev, [xs, t, idx] + ([] if sc is None else [sc]), K, call, stop_loss,
                      check_every, stream, workspace_bytes, clamps=True)
 
 
-def _run_loop(who, what, p, state, dev, inputs, K, call, stop_loss, check_every, stream, workspace_bytes, clamps=False):
-    """What fit_run() and fit_run_batches() share once their inputs are device tensors on `dev`: the
-    checks of the network, the state and the loop's settings, the outputs, the stream discipline, the
-    call -- call(library, net, *the arguments from exp_avg on) -- and the state's step after it."""
+def _run_loop(who, what, p, state, dev, inputs, K, call, stop_loss, check_every, stream, workspace_bytes, clamps=False,
+              ensemble=False):
+    """What fit_run(), fit_run_batches() and their ensemble forms share once their inputs are device
+    tensors on `dev`: the checks of the network, the state and the loop's settings, the outputs, the
+    stream discipline, the call -- call(library, head, *the arguments from exp_avg on), head being the
+    entry point's leading arguments, (net,) or (n_members, nets) -- and the state's step after it.
+    ensemble: p and state are the members' lists, the moments go over as arrays of pointers, losses
+    and status gain a leading member axis, and each state's step advances by its own status[e][0]."""
     import torch
-    tensors = p.weights + p.biases
-    if any(w.device != dev for w in tensors) or state.exp_avg.device != dev:
-        raise ValueError(f"siren.{who}: the {what} on {dev}, the network on {tensors[0].device}, the state on "
-                         f"{state.exp_avg.device}")
-    if state.counts != [int(w.numel()) for w in tensors]:
-        raise ValueError(f"siren.{who}: state was made for a network of another shape")
+    ps, states = (list(p), list(state)) if ensemble else ([p], [state])
+    tensors = []
+    for e, (q, sta) in enumerate(zip(ps, states)):
+        of = f" of member {e}" if ensemble else ""
+        mine = q.weights + q.biases
+        if any(w.device != dev for w in mine) or sta.exp_avg.device != dev:
+            raise ValueError(f"siren.{who}: the {what} on {dev}, the network{of} on {mine[0].device}, the state on "
+                             f"{sta.exp_avg.device}")
+        if sta.counts != [int(w.numel()) for w in mine]:
+            raise ValueError(f"siren.{who}: state{of} was made for a network of another shape")
+        tensors += mine
+    first = states[0]
+    for e, sta in enumerate(states[1:], 1):
+        if (sta.lr, sta.betas, sta.eps, sta.max_grad_norm if sta.clips else None, sta.step) != \
+                (first.lr, first.betas, first.eps, first.max_grad_norm if first.clips else None, first.step):
+            raise ValueError(f"siren.{who}: the members share the optimiser's parameters and its step: the state of member "
+                             f"{e} differs from member 0's in lr, betas, eps, max_grad_norm or step")
     ws = 0 if workspace_bytes is None else int(workspace_bytes)
     if ws < 0:
         raise ValueError(f"siren.{who}: workspace_bytes must be >= 0, got {workspace_bytes}")
@@ -672,27 +688,41 @@ def _run_loop(who, what, p, state, dev, inputs, K, call, stop_loss, check_every,
         raise ValueError(f"siren.{who}: check_every must be >= 0, got {check_every}")
     if stop_loss is not None and not float(stop_loss) >= 0.0:
         raise ValueError(f"siren.{who}: stop_loss must be None or >= 0, got {stop_loss}")
-    losses = torch.empty(K, dtype=torch.float32, device=dev)
-    status = torch.zeros(2, dtype=torch.int64, device=dev)  # zeros: a call refused before any device work applied nothing
-    s = _stream_of(stream, inputs + [losses, status, state.exp_avg, state.exp_avg_sq] + tensors, dev)
-    st, keep = _net_struct(p)
-    opt = state.params()
+    E = len(ps)
+    losses = torch.empty((E, K) if ensemble else K, dtype=torch.float32, device=dev)
+    # zeros: a call refused before any device work applied nothing
+    status = torch.zeros((E, 2) if ensemble else 2, dtype=torch.int64, device=dev)
+    moments = [sta.exp_avg for sta in states] + [sta.exp_avg_sq for sta in states]
+    s = _stream_of(stream, inputs + [losses, status] + moments + tensors, dev)
+    structs = [_net_struct(q) for q in ps]
+    if ensemble:
+        head = (E, (_lib.SirenNet * E)(*[st for st, _ in structs]))
+        m, v = _ptr_array(moments[:E]), _ptr_array(moments[E:])
+    else:
+        head = (C.byref(structs[0][0]),)
+        m, v = moments[0].data_ptr(), moments[1].data_ptr()
+    opt = first.params()
     flags = _lib.WOS_PTRS_DEVICE | (0 if check_every > 0 else _lib.WOS_ASYNC)
-    rc = call(_lib.load(), C.byref(st), state.exp_avg.data_ptr(), state.exp_avg_sq.data_ptr(), state.step, C.byref(opt),
-              -1.0 if stop_loss is None else float(stop_loss), check_every, losses.data_ptr(), status.data_ptr(), ws, flags,
-              dev.index or 0, s)
-    del keep
+    rc = call(_lib.load(), head, m, v, first.step, C.byref(opt), -1.0 if stop_loss is None else float(stop_loss), check_every,
+              losses.data_ptr(), status.data_ptr(), ws, flags, dev.index or 0, s)
+    del structs
+
+    def advance():  # each state by the iterations applied to its own network
+        applied = status.reshape(E, 2)[:, 0].tolist()
+        for sta, k in zip(states, applied):
+            sta.step += int(k)
     if clamps and rc == -1 and check_every > 0:
         # The blocking call refuses a clamped index only after the run: its iterations are applied to the
         # network and the moments, so the state's step follows them before the error is raised.
         torch.cuda.synchronize(dev)
-        state.step += int(status[0].item())
+        advance()
     check(rc, f"wos_siren_{who}")
     if stop_loss is None:
-        state.step += K
+        for sta in states:
+            sta.step += K
     else:
         _current_waits_for(stream, dev)
-        state.step += int(status[0].item())
+        advance()
     return losses, status
 
 
@@ -732,8 +762,8 @@ def fit_run_batches(net, state, x, target, scale, counts, *, stop_loss=None, che
     sc = None if scale is None else _operand("fit_run_batches", "scale", scale, (total, p.d_out), True, dev, "x")
     K = len(offsets) - 1
 
-    def call(L, net, *rest):
-        return L.wos_siren_fit_run_batches(net, xs.data_ptr(), t.data_ptr(), None if sc is None else sc.data_ptr(),
+    def call(L, head, *rest):
+        return L.wos_siren_fit_run_batches(*head, xs.data_ptr(), t.data_ptr(), None if sc is None else sc.data_ptr(),
                                            (C.c_int64 * (K + 1))(*offsets), K, *rest)
     return _run_loop("fit_run_batches", "points are", p, state, dev, [xs, t] + ([] if sc is None else [sc]), K, call,
                      stop_loss, check_every, stream, workspace_bytes)
@@ -751,6 +781,106 @@ def _batch_offsets(who, counts, total):
     if offsets[-1] != total:
         raise ValueError(f"{who}: counts sum to {offsets[-1]}, the tensors hold {total} rows")
     return offsets
+
+
+def _members(who, nets, states):
+    """The packed members of an ensemble call and their shared shape."""
+    ps = [net if isinstance(net, PackedSiren) else pack(net) for net in nets]
+    states = list(states)
+    if not 1 <= len(ps) <= MAX_MEMBERS:
+        raise ValueError(f"siren.{who}: an ensemble has 1..{MAX_MEMBERS} members, got {len(ps)}")
+    if len(states) != len(ps):
+        raise ValueError(f"siren.{who}: {len(ps)} networks, but {len(states)} states")
+    for e, q in enumerate(ps[1:], 1):
+        if tuple(q[:5]) != tuple(ps[0][:5]):
+            raise ValueError(f"siren.{who}: member {e} is {tuple(q[:5])}, member 0 {tuple(ps[0][:5])} (d_in, d_out, hidden, "
+                             f"n_hidden_layers, omega): the members of an ensemble have one shape")
+    return ps, states
+
+
+def _member_operands(who, name, arrays, E, shape, dev, like, optional=False):
+    """One operand per member, each as _operand() takes it; optional: the list, or an entry, may be None."""
+    if arrays is None and optional:
+        return [None] * E
+    arrays = list(arrays)
+    if len(arrays) != E:
+        raise ValueError(f"siren.{who}: {name} must hold one array per member ({E}), got {len(arrays)}")
+    return [None if a is None and optional else _operand(who, f"{name}[{e}]", a, shape, True, dev, like)
+            for e, a in enumerate(arrays)]
+
+
+def fit_run_ensemble(nets, states, pool_x, pool_targets, pool_scales, idx, *, stop_loss=None, check_every=0, stream=None,
+                     workspace_bytes=None):
+    """fit_run() for the E <= 4 members of an ensemble in one device loop (wos_siren_fit_run_ensemble):
+    nets and states are lists of E networks of one shape and their AdamStates (the same lr, betas, eps,
+    max_grad_norm and step), pool_targets a list of E tensors [n_pool, d_out], pool_scales None or a
+    list whose entries may be None.  The members share pool_x and the index draw idx -- common random
+    numbers, as the walks of a multi-channel solve -- and every launch of an iteration covers all of
+    them.  Member e's losses, parameters and moments are, bit for bit, fit_run()'s on member e alone.
+    EVERY NETWORK IS UPDATED IN PLACE.  Returns (losses [E, K], status [E, 2]) on the device.  The stop
+    is per member: a stopped member's updates and loss writes are no-ops while the others go on, each
+    state's step advances by its own status[e][0], and check_every=c stops enqueuing once every member
+    has stopped.  Everything else as in fit_run()."""
+    import torch
+    ps, states = _members("fit_run_ensemble", nets, states)
+    p, E = ps[0], len(ps)
+    if not (_is_torch(pool_x) and pool_x.is_cuda):
+        raise ValueError("siren.fit_run_ensemble: pool_x must be a CUDA tensor (device pointers only)")
+    dev = pool_x.device
+    if pool_x.dim() != 2 or pool_x.shape[1] != p.d_in or pool_x.shape[0] < 1:
+        raise ValueError(f"siren.fit_run_ensemble: pool_x must be [n_pool, {p.d_in}], got shape {tuple(pool_x.shape)}")
+    n_pool = int(pool_x.shape[0])
+    xs = pool_x.detach().to(torch.float32).contiguous()
+    ts = _member_operands("fit_run_ensemble", "pool_targets", pool_targets, E, (n_pool, p.d_out), dev, "pool_x")
+    scs = _member_operands("fit_run_ensemble", "pool_scales", pool_scales, E, (n_pool, p.d_out), dev, "pool_x", optional=True)
+    if not _is_torch(idx) or idx.device != dev or idx.dtype != torch.int64 or idx.dim() != 2 or not idx.is_contiguous() \
+            or idx.shape[0] < 1 or idx.shape[1] < 1:
+        raise ValueError(f"siren.fit_run_ensemble: idx must be a contiguous int64 tensor [K, batch] on {dev}")
+    K, batch = int(idx.shape[0]), int(idx.shape[1])
+    t_ptrs, s_ptrs = _ptr_array(ts), _opt_ptr_array(scs)
+
+    def call(L, head, *rest):
+        return L.wos_siren_fit_run_ensemble(*head, xs.data_ptr(), t_ptrs, s_ptrs, n_pool, idx.data_ptr(), K, batch, *rest)
+    return _run_loop("fit_run_ensemble", "pool is", ps, states, dev, [xs, idx] + ts + [sc for sc in scs if sc is not None], K,
+                     call, stop_loss, check_every, stream, workspace_bytes, clamps=True, ensemble=True)
+
+
+def fit_run_batches_ensemble(nets, states, x, targets, scales, counts, *, stop_loss=None, check_every=0, stream=None,
+                             workspace_bytes=None):
+    """fit_run_batches() for the E <= 4 members of an ensemble in one device loop
+    (wos_siren_fit_run_batches_ensemble): the members share the points x [total, d_in] and the row
+    counts; targets is a list of E tensors [total, d_out], scales None or a list whose entries may be
+    None.  Member e's losses, parameters and moments are, bit for bit, fit_run_batches()'s on member e
+    alone.  nets, states, the returned (losses [E, K], status [E, 2]) and the per-member stop as in
+    fit_run_ensemble()."""
+    import torch
+    ps, states = _members("fit_run_batches_ensemble", nets, states)
+    p, E = ps[0], len(ps)
+    if len(x.shape) != 2 or x.shape[1] != p.d_in or x.shape[0] < 1:
+        raise ValueError(f"siren.fit_run_batches_ensemble: x must be [total, {p.d_in}], got shape {tuple(x.shape)}")
+    total = int(x.shape[0])
+    offsets = _batch_offsets("siren.fit_run_batches_ensemble", counts, total)
+    if not (_is_torch(x) and x.is_cuda):
+        raise ValueError("siren.fit_run_batches_ensemble: x must be a CUDA tensor (device pointers only)")
+    dev = x.device
+    xs = x.detach().to(torch.float32).contiguous()
+    ts = _member_operands("fit_run_batches_ensemble", "targets", targets, E, (total, p.d_out), dev, "x")
+    scs = _member_operands("fit_run_batches_ensemble", "scales", scales, E, (total, p.d_out), dev, "x", optional=True)
+    K = len(offsets) - 1
+    t_ptrs, s_ptrs = _ptr_array(ts), _opt_ptr_array(scs)
+
+    def call(L, head, *rest):
+        return L.wos_siren_fit_run_batches_ensemble(*head, xs.data_ptr(), t_ptrs, s_ptrs, (C.c_int64 * (K + 1))(*offsets), K,
+                                                    *rest)
+    return _run_loop("fit_run_batches_ensemble", "points are", ps, states, dev, [xs] + ts + [sc for sc in scs if sc is not None],
+                     K, call, stop_loss, check_every, stream, workspace_bytes, ensemble=True)
+
+
+def _opt_ptr_array(arrays):
+    """_ptr_array over entries that may be None (a NULL entry); None when every entry is."""
+    if all(a is None for a in arrays):
+        return None
+    return (C.c_void_p * len(arrays))(*[None if a is None else a.data_ptr() for a in arrays])
 
 
 _probes = {}  # diagonal_wrap's probe of the last (shape, dtype, device)
