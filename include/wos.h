@@ -566,6 +566,66 @@ int wos_selftest_lhs_plan(int32_t n_pairs, int32_t dim, int32_t *out);
 int wos_selftest_rejection(int32_t dim, const float *R, const float *lambda, const float *x, int64_t n,
                            int32_t *edges, float *vals, int32_t *flags, int32_t device);
 
+/* Device self-test of the three geometry queries of a walk step -- the first ray hit, the star
+ * radius and the distance to the Dirichlet boundary -- for the GPU tests (added within ABI 10: a new
+ * entry point only; csrc/wos_selftest.hip).  The scene is planned exactly as wos_solve plans it under
+ * `schedule`, min_star_radius and silhouette_precision (LDS or global geometry, star grid, Dirichlet
+ * grid, the three hierarchies), workgroups of four waves stage the geometry as the walk kernel does,
+ * and wave w takes the 64-bit lane mask masks[w]: its set lanes take the next items in order, and
+ * every lane calls the wave-cooperative query with active / query / want false on clear lanes, as
+ * the walk step calls it.  The set bits of all n_masks masks must sum to n.
+ *   kind                 items[n][.]
+ *   WOS_GEO_RAY          origin[dim], direction[dim], tmax
+ *   WOS_GEO_STAR         x[dim], maxR, flip (0 or 1: computeStarRadius's flipNormalOrientation)
+ *   WOS_GEO_DIRICHLET    x[dim]
+ * out[n][3][WOS_GEO_OUT]: form 0 the plain sequential scan with no cull, form 1 the per-lane culled
+ * form (ray_hit, star_radius, dirichlet_dist_culled), form 2 the wave-cooperative form as shipped
+ * (ray_hit_wave, star_radius_wave, dirichlet_dist_step).  Ray: [0] 1.0 if hit, and where hit [1] d,
+ * [2..] p, [5..] unit normal (zeros otherwise).  Star: [0] the radius.  Dirichlet: [0] the distance,
+ * [1..] projectToDirichlet's point (forms 0 and 1; form 2 computes none).
+ * tags[n]: the regime form 2 took for the item's wave (WOS_GEO_RAY_*, WOS_GEO_STAR_*, WOS_GEO_DIR_*).
+ * sound[n]: bit WOS_GEO_S_* is set when that shortcut said "certainly reject" where the exact test
+ * accepts, over every primitive, candidate and group of the scene for the item (each judged against
+ * tmax / maxR alone); all zero means every shortcut kept its promise.  counts[n][WOS_GEO_COUNTS]:
+ * how often each shortcut fired (slot WOS_GEO_C_x) and declined (slot WOS_GEO_C_x + 1), how often
+ * silhouette_class2 returned 0, 1, 2 (WOS_GEO_C_CLASS + 0..2), and the length of the item's cell list.
+ * plan[8] (may be NULL): geom_global, star grid present, Dirichlet grid present, dynamic LDS bytes,
+ * the levels of the primitive, silhouette and Dirichlet group hierarchies, silhouette candidates.
+ * n = 0 succeeds without a launch.  A null argument, an unknown kind, a Dirichlet query on a scene
+ * without Dirichlet geometry or masks whose set bits do not sum to n are WOS_E_INVALID. */
+enum { WOS_GEO_RAY = 0, WOS_GEO_STAR = 1, WOS_GEO_DIRICHLET = 2 };
+#define WOS_GEO_OUT 8
+#define WOS_GEO_COUNTS 16
+enum { WOS_GEO_RAY_NONE = 0,   /* no lane of the wave queries */
+       WOS_GEO_RAY_LANE_SCAN,  /* few primitives, two or more lanes: each lane scans them all */
+       WOS_GEO_RAY_SOLO,       /* one querying lane: groups and primitives over the lanes, DPP minima */
+       WOS_GEO_RAY_LIST,       /* the cooperative LDS list over the flat group scan */
+       WOS_GEO_RAY_TREE };     /* the same list over the primitive-group hierarchy */
+enum { WOS_GEO_STAR_NONE = 0,    /* decided without a scan (minR > maxR, minR >= maxR, no primitives) */
+       WOS_GEO_STAR_SOLO_CELL,   /* one querying lane inside the star grid */
+       WOS_GEO_STAR_CELL_LISTS,  /* the windowed cell lists */
+       WOS_GEO_STAR_GROUPS,      /* the flat silhouette-group scan */
+       WOS_GEO_STAR_TREE,        /* the scan over the silhouette-group hierarchy */
+       WOS_GEO_STAR_MIXED = 0x100 }; /* or-ed in: the wave mixes lanes inside and outside the grid */
+enum { WOS_GEO_DIR_NONE = 0, WOS_GEO_DIR_GRID, /* the Dirichlet cell grid */
+       WOS_GEO_DIR_GRID_MISS,                  /* outside the grid: the culled scan */
+       WOS_GEO_DIR_SOLO, WOS_GEO_DIR_CULLED,   /* one wanting lane; the culled flat scan */
+       WOS_GEO_DIR_TREE };                     /* the culled scan over the Dirichlet-group hierarchy */
+#define WOS_GEO_S_RAY_BOX 0x1u        /* ray_box_maybe (a group or a hierarchy node above it) */
+#define WOS_GEO_S_RAY_PREFILTER 0x2u  /* ray_prim_prefilter against ray_prim_exact */
+#define WOS_GEO_S_BALL_BOX 0x4u       /* ball_box_maybe over a group holding an accepted candidate */
+#define WOS_GEO_S_CONE 0x8u           /* cone_culled over such a group */
+#define WOS_GEO_S_CLASS2 0x10u        /* silhouette_class2's 0 / 1 against is_silhouette */
+#define WOS_GEO_S_STAR_EARLY 0x20u    /* star_candidate's distance early-outs against d^2 <= r2 */
+#define WOS_GEO_S_STAR_CELL 0x40u     /* the star grid's cell list lacks the exact scan's winner */
+#define WOS_GEO_S_DIR_BOX 0x80u       /* a Dirichlet box bound above a member's computed d^2 */
+#define WOS_GEO_S_DIR_CELL 0x100u     /* the Dirichlet grid's cell list lacks the winning segment */
+enum { WOS_GEO_C_RAY_BOX = 0, WOS_GEO_C_PREFILTER = 2, WOS_GEO_C_BALL_BOX = 4, WOS_GEO_C_CONE = 6,
+       WOS_GEO_C_STAR_EARLY = 8, WOS_GEO_C_DIR_BOX = 10, WOS_GEO_C_CLASS = 12, WOS_GEO_C_CELL_LEN = 15 };
+int wos_selftest_geometry(wos_scene *s, uint32_t schedule, float min_star_radius, float silhouette_precision,
+                          int32_t kind, const float *items, int64_t n, const uint64_t *masks, int32_t n_masks,
+                          float *out, int32_t *tags, uint32_t *sound, uint32_t *counts, int32_t *plan);
+
 /* Device self-test of the indexed adjoint's sum kernels (csrc/wos_tape_index.hip) on a
  * caller-supplied index, without a scene: row [n_rows + 1] (row[0] = 0, non-decreasing), id and
  * w [row[n_rows]] (id & 0x7FFFFFFF < n_tasks; bit 31: take c), a and c [n_channels][n_tasks],

@@ -1,6 +1,8 @@
 // wos_capi_probes.cpp -- the self-test probes of the solve's kernels (wos_selftest_*, kernels in
 // wos_selftest.hip): they need neither a scene's workspace nor the device context, and each call owns
 // what it allocates.  The two SIREN probes are with their kernels' host half, wos_capi_siren.cpp.
+// wos_selftest_geometry alone takes a scene: it plans it as a solve does (solve_plan) and launches
+// its own kernel on that plan, touching nothing of the shared workspace.
 #include "wos_capi.h"
 
 using namespace wos::capi;
@@ -145,6 +147,82 @@ int wos_selftest_rejection(int32_t dim, const float* R, const float* lambda, con
   HIP_TRY(hipMemcpy(edges, d_edges, N * 6 * 4, hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(vals, d_vals, N * 3 * 4, hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(flags, d_flags, N * 4, hipMemcpyDeviceToHost));
+  return WOS_OK;
+}
+
+int wos_selftest_geometry(wos_scene* s, uint32_t schedule, float min_star_radius, float silhouette_precision,
+                          int32_t kind, const float* items, int64_t n, const uint64_t* masks, int32_t n_masks,
+                          float* out, int32_t* tags, uint32_t* sound, uint32_t* counts, int32_t* plan) {
+  if (!s || !items || !masks || !out || !tags || !sound || !counts)
+    return fail(WOS_E_INVALID, "wos_selftest_geometry: null argument");
+  if (kind != WOS_GEO_RAY && kind != WOS_GEO_STAR && kind != WOS_GEO_DIRICHLET)
+    return fail(WOS_E_INVALID, "wos_selftest_geometry: kind must be WOS_GEO_RAY (0), WOS_GEO_STAR (1) or "
+                               "WOS_GEO_DIRICHLET (2), got " + std::to_string(kind));
+  if (n < 0 || n > (1 << 20) || n_masks < 0 || n_masks > (1 << 20))
+    return fail(WOS_E_INVALID, "wos_selftest_geometry: bad item or mask count");
+  const wos::HostScene& host = s->geom->host;
+  const int dim = host.dim;
+  if (kind == WOS_GEO_DIRICHLET && host.n_dprims <= 0)
+    return fail(WOS_E_INVALID, "wos_selftest_geometry: the scene holds no Dirichlet boundary");
+  // the first item of every wave; the masks hold exactly the n items
+  std::vector<int32_t> first((size_t)n_masks);
+  int64_t bits = 0;
+  for (int32_t w = 0; w < n_masks; w++) {
+    first[w] = (int32_t)std::min<int64_t>(bits, n);
+    bits += __builtin_popcountll(masks[w]);
+  }
+  if (bits != n)
+    return fail(WOS_E_INVALID, "wos_selftest_geometry: the masks' set bits sum to " + std::to_string(bits) +
+                                   ", not to n = " + std::to_string(n));
+  wos_solver_params prm;
+  wos_default_params(&prm);
+  prm.schedule = schedule;
+  prm.min_star_radius = min_star_radius;
+  prm.silhouette_precision = silhouette_precision;
+  WOS_TRY(check_params("wos_selftest_geometry", &prm));
+  std::lock_guard<std::mutex> lock(s->mu);
+  HIP_TRY(hipSetDevice(s->device));
+  DevCtx& c = g_ctx[s->device];
+  std::lock_guard<std::mutex> lk(c.mu);
+  WOS_TRY(ctx_ready(c, s->device));
+  // the scene as a solve's walk kernel sees it
+  SolvePlan P;
+  WOS_TRY(solve_plan(c, s, &prm, SolveExtra{}, false, P));
+  if (plan) {
+    plan[0] = P.dsc.geom_global;
+    plan[1] = P.dsc.sgrid != nullptr;
+    plan[2] = P.dsc.dgrid != nullptr;
+    plan[3] = (int32_t)P.shmem_walk;
+    plan[4] = P.dsc.ptree.levels;
+    plan[5] = P.dsc.stree.levels;
+    plan[6] = P.dsc.dtree.levels;
+    plan[7] = P.dsc.n_sil;
+  }
+  if (n == 0) return WOS_OK;
+  const size_t N = (size_t)n;
+  const size_t iw = kind == WOS_GEO_RAY ? 2 * dim + 1 : (kind == WOS_GEO_STAR ? dim + 2 : dim);
+  DevBufs tmp;
+  float *d_items = nullptr, *d_out = nullptr;
+  unsigned long long* d_masks = nullptr;
+  int32_t *d_first = nullptr, *d_tags = nullptr;
+  uint32_t *d_sound = nullptr, *d_counts = nullptr;
+  HIP_TRY(tmp.get(&d_items, N * iw));
+  HIP_TRY(tmp.get(&d_masks, (size_t)n_masks));
+  HIP_TRY(tmp.get(&d_first, (size_t)n_masks));
+  HIP_TRY(tmp.get(&d_out, N * 3 * WOS_GEO_OUT));
+  HIP_TRY(tmp.get(&d_tags, N));
+  HIP_TRY(tmp.get(&d_sound, N));
+  HIP_TRY(tmp.get(&d_counts, N * WOS_GEO_COUNTS));
+  HIP_TRY(hipMemcpy(d_items, items, N * iw * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_masks, masks, (size_t)n_masks * 8, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_first, first.data(), (size_t)n_masks * 4, hipMemcpyHostToDevice));
+  HIP_TRY(wos::launch_geometry_selftest(dim, kind, P.dsc, P.dp, d_items, d_masks, d_first, n_masks, P.shmem_walk,
+                                        P.geom_floats_walk, d_out, d_tags, d_sound, d_counts, nullptr));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(out, d_out, N * 3 * WOS_GEO_OUT * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(tags, d_tags, N * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(sound, d_sound, N * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(counts, d_counts, N * WOS_GEO_COUNTS * 4, hipMemcpyDeviceToHost));
   return WOS_OK;
 }
 

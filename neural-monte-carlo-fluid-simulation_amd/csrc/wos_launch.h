@@ -78,6 +78,15 @@ void lhs_plan(int n_pairs, int dim, int32_t* out);  // wos_selftest_lhs_plan's o
 hipError_t launch_rejection_selftest(int dim, const float* rej_tab, const float* R, const float* lambda, const float* x,
                                      int64_t n, int32_t* edges, float* vals, int32_t* flags, hipStream_t s);
 
+// probe of the walk step's geometry queries (wos_selftest.hip; include/wos.h wos_selftest_geometry):
+// sc, prm, shmem and geom_floats as launch_walks takes them from a solve's plan; wave w takes lane
+// mask masks[w], its set lanes the items first[w], first[w] + 1, ...; out [n][3][WOS_GEO_OUT],
+// tags and sound [n], counts [n][WOS_GEO_COUNTS]
+hipError_t launch_geometry_selftest(int dim, int kind, const DevScene& sc, const DevParams& prm, const float* items,
+                                    const unsigned long long* masks, const int32_t* first, int n_masks, size_t shmem,
+                                    int geom_floats, float* out, int32_t* tags, uint32_t* sound, uint32_t* counts,
+                                    hipStream_t s);
+
 // boundary value caching (wos_bvc.hip), 2D
 hipError_t launch_bvc_point_info(const DevScene& sc, const float* pts, int64_t n, float* dd, float* nd,
                                  int32_t* inside, float* src, hipStream_t s);

@@ -280,4 +280,362 @@ hipError_t launch_rejection_selftest(int dim, const float* rej_tab, const float*
   return hipGetLastError();
 }
 
+// ---- the walk step's geometry queries (wos_selftest_geometry) ------------------------------------
+// One workgroup stages the geometry as the walk kernel does; wave w of the grid takes lane mask w,
+// its set lanes the next items in order, and every lane calls the wave-cooperative query convergently
+// (clear lanes with active / query / want false), as walk_iteration calls it.  Beside it each set lane
+// runs the plain sequential scan and the per-lane culled form, and every shortcut next to the exact
+// test over every primitive, candidate and group of the scene (the soundness word and the counts).
+// The branch tag restates the shipped function's own regime choice from the same wave-uniform values.
+namespace {
+
+// the ancestors of group g in tree T accept (ok(box)) -- the tree scans descend through them
+template <class Ok>
+__device__ __forceinline__ bool geo_tree_path_ok(const DevTree& T, int g, Ok ok) {
+  bool all = true;
+  for (int L = 1; L <= T.levels; L++) all = all && ok(tree_node(T, L, g >> (3 * L)));
+  return all;
+}
+
+__device__ __forceinline__ void geo_count(uint32_t* c, bool fired, int slot) { c[slot + (fired ? 0 : 1)]++; }
+
+template <int DIM, bool GG>
+__device__ __forceinline__ void geo_ray(const DevScene& sc, const LGeom& G, bool on, const float* it, RayLDS<DIM>* L,
+                                        int lane, float* out, int32_t* tag, uint32_t* snd, uint32_t* cnt) {
+  constexpr int PS = Layout<DIM>::prim;
+  const int np = sc.n_prims, ng = sc.n_pgroups;
+  float o[DIM], dir[DIM], tmax = 0.0f;
+  for (int k = 0; k < DIM; k++) { o[k] = 0.0f; dir[k] = 1.0f; }
+  if (on) {
+    for (int k = 0; k < DIM; k++) { o[k] = it[k]; dir[k] = it[DIM + k]; }
+    tmax = it[2 * DIM];
+  }
+  Hit h[3];
+  bool f[3] = {false, false, false};
+  if (on) {
+    f[0] = ray_hit_scan<DIM>(G.prim, np, o, dir, tmax, &h[0]);
+    f[1] = ray_hit<DIM>(G, np, ng, o, dir, tmax, &h[1]);
+  }
+  f[2] = ray_hit_wave<DIM, GG>(G, sc, on, o, dir, tmax, &h[2], L, lane);
+  // ray_hit_wave's regime
+  const uint64_t nmask = __ballot(on && np > 0);
+  const bool tree = GG && sc.ptree.levels > 0, lone = (nmask & (nmask - 1)) == 0;
+  const int t = nmask == 0 ? WOS_GEO_RAY_NONE
+                : (!tree && np <= (DIM == 2 ? kRayScanMax2 : kRayScanMax3) && !lone) ? WOS_GEO_RAY_LANE_SCAN
+                : (!tree && lone) ? WOS_GEO_RAY_SOLO : (tree ? WOS_GEO_RAY_TREE : WOS_GEO_RAY_LIST);
+  if (!on) return;
+  *tag = t;
+  for (int q = 0; q < 3; q++) {
+    float* r = out + q * WOS_GEO_OUT;
+    r[0] = f[q] ? 1.0f : 0.0f;
+    if (f[q]) {
+      r[1] = h[q].d;
+      for (int k = 0; k < DIM; k++) { r[2 + k] = h[q].p[k]; r[5 + k] = h[q].n[k]; }
+    }
+  }
+  float inv[DIM];
+  for (int k = 0; k < DIM; k++) inv[k] = __builtin_amdgcn_rcpf(dir[k]);
+  uint32_t s = 0;
+  for (int gi = 0; gi < ng; gi++) {
+    bool any = false;
+    const int p1 = (gi + 1) * kGroup < np ? (gi + 1) * kGroup : np;
+    for (int p = gi * kGroup; p < p1; p++) {
+      const float* P = G.prim + p * PS;
+      float rt = tmax;
+      Hit hh;
+      const bool exact = ray_prim_exact<DIM>(P, o, dir, rt, &hh);
+      const bool pass = ray_prim_prefilter<DIM>(P, o, dir, tmax);
+      geo_count(cnt, !pass, WOS_GEO_C_PREFILTER);
+      if (!pass && exact) s |= WOS_GEO_S_RAY_PREFILTER;
+      any = any || exact;
+    }
+    const bool maybe = ray_box_maybe<DIM>(G.pgroup + gi * kGroupStride, o, inv, tmax);
+    geo_count(cnt, !maybe, WOS_GEO_C_RAY_BOX);
+    const bool path = !tree || geo_tree_path_ok(sc.ptree, gi, [&](const float* B) { return ray_box_maybe<DIM>(B, o, inv, tmax); });
+    if (any && !(maybe && path)) s |= WOS_GEO_S_RAY_BOX;
+  }
+  *snd = s;
+}
+
+template <int DIM, bool GG>
+__device__ __forceinline__ void geo_star(const DevScene& sc, const DevParams& prm, const LGeom& G, bool on,
+                                         const float* it, StarLDS<DIM>* L, int lane, float* out, int32_t* tag,
+                                         uint32_t* snd, uint32_t* cnt) {
+  constexpr int SS = Layout<DIM>::sil;
+  const int ns = sc.n_sil, nsg = sc.n_sgroups;
+  const float minR = prm.min_star_radius, prec = prm.silhouette_precision;
+  float x[DIM], maxR = 0.0f;
+  bool flipOrient = false;
+  for (int k = 0; k < DIM; k++) x[k] = 0.0f;
+  if (on) {
+    for (int k = 0; k < DIM; k++) x[k] = it[k];
+    maxR = it[DIM];
+    flipOrient = it[DIM + 1] != 0.0f;
+  }
+  const bool flip = !flipOrient;  // computeStarRadius passes !flipNormalOrientation
+  const float r2_0 = maxR < kFltMax ? maxR * maxR : kFltMax, minR2 = minR * minR;
+  const bool need = on && !(minR > maxR) && sc.n_prims > 0 && !(minR2 >= r2_0);
+  // the exact distance and view of candidate s (the sequential loop's own arithmetic)
+  const auto cand = [&](int s, float* view) {
+    const float* S = G.sil + s * SS;
+    if constexpr (DIM == 2) {
+      view[0] = x[0] - S[0]; view[1] = x[1] - S[1];
+      return __builtin_sqrtf(view[0] * view[0] + view[1] * view[1]);
+    } else {
+      float pt[3], t;
+      const float d = cp_segment<3>(S, S + 3, x, pt, &t);
+      for (int k = 0; k < 3; k++) view[k] = x[k] - pt[k];
+      return d;
+    }
+  };
+  const auto is_sil = [&](int s, const float* view, float d) {
+    const float* S = G.sil + s * SS;
+    return (DIM == 2 ? S[6] : S[12]) != 0.0f ? true : is_silhouette<DIM>(S, view, d, flip, prec);
+  };
+  float r[3] = {0.0f, 0.0f, 0.0f};
+  int winner = -1;
+  if (on) {
+    // computeStarRadius as the oracle runs it: every candidate in index order, no cull
+    if (minR > maxR) {
+      r[0] = maxR;
+    } else {
+      r[0] = smax(maxR, minR);
+      if (need) {
+        float r2 = r2_0, best = 0.0f;
+        for (int s = 0; s < ns; s++) {
+          float view[DIM];
+          const float d = cand(s, view), d2 = d * d;
+          if (d2 > r2) continue;
+          if (is_sil(s, view, d) && d2 <= r2) {
+            r2 = d2; best = d; winner = s;
+            if (minR2 >= r2) break;
+          }
+        }
+        if (winner >= 0) r[0] = smax(best, minR);
+      }
+    }
+    r[1] = star_radius<DIM>(G, ns, nsg, sc.n_prims, x, minR, maxR, prec, flipOrient);
+  }
+  r[2] = star_radius_wave<DIM, GG>(G, sc, prm, on, x, maxR, flipOrient, L, lane);
+  // star_radius_wave's regime
+  const int cell = (need && G.sgrid != nullptr) ? star_cell<DIM>(sc, x) : -1;
+  const bool use_cell = cell >= 0;
+  const uint64_t nmask = __ballot(need), cmask = __ballot(use_cell);
+  const bool tree = GG && sc.stree.levels > 0, lone = (nmask & (nmask - 1)) == 0;
+  int t = !need ? WOS_GEO_STAR_NONE
+          : (lone && use_cell) ? WOS_GEO_STAR_SOLO_CELL
+          : use_cell ? WOS_GEO_STAR_CELL_LISTS : (tree ? WOS_GEO_STAR_TREE : WOS_GEO_STAR_GROUPS);
+  if (need && cmask != 0 && cmask != nmask) t |= WOS_GEO_STAR_MIXED;
+  if (!on) return;
+  *tag = t;
+  for (int q = 0; q < 3; q++) out[q * WOS_GEO_OUT] = r[q];
+  if (!need) return;
+  uint32_t sd = 0;
+  for (int gi = 0; gi < nsg; gi++) {
+    bool any = false;
+    const int s1 = (gi + 1) * kGroup < ns ? (gi + 1) * kGroup : ns;
+    for (int s = gi * kGroup; s < s1; s++) {
+      const float* S = G.sil + s * SS;
+      float view[DIM];
+      const float d = cand(s, view);
+      const bool in_ball = d * d <= r2_0, sil = is_sil(s, view, d);
+      any = any || (in_ball && sil);
+      bool early;
+      int cls = 2;
+      if constexpr (DIM == 2) {
+        const float d2raw = view[0] * view[0] + view[1] * view[1];
+        early = d2raw > r2_0 * 1.000001f;
+        if (S[6] == 0.0f) {
+          cls = silhouette_class2(S, view, d2raw, flip, prec);
+          cnt[WOS_GEO_C_CLASS + cls]++;
+          if ((cls == 0 && sil) || (cls == 1 && !sil)) sd |= WOS_GEO_S_CLASS2;
+        }
+      } else {
+        float e[3], hl[3];
+        for (int k = 0; k < 3; k++) { e[k] = x[k] - 0.5f * (S[k] + S[3 + k]); hl[k] = 0.5f * (S[3 + k] - S[k]); }
+        const float dm = __builtin_amdgcn_sqrtf(dotv<3>(e, e)), hr = __builtin_amdgcn_sqrtf(dotv<3>(hl, hl));
+        const float lo = dm - hr;
+        early = lo > 0.0f && lo * lo > r2_0 * 1.0001f + 1e-6f * dm * dm;
+      }
+      geo_count(cnt, early, WOS_GEO_C_STAR_EARLY);
+      // the early-outs as restated above, and as star_candidate itself applies them: it must not
+      // turn down a candidate the exact test accepts (silhouette_class2's 0 is judged above)
+      float d2c;
+      const bool shipped = star_candidate<DIM>(G, s, x, r2_0, flip, prec, &d2c);
+      if ((early && in_ball) || (in_ball && sil && !shipped && cls != 0)) sd |= WOS_GEO_S_STAR_EARLY;
+    }
+    const float* B = G.sgroup + gi * kSGroupStride;
+    const bool maybe = ball_box_maybe<DIM>(B, x, r2_0), culled = cone_culled<DIM>(B, x, prec);
+    geo_count(cnt, !maybe, WOS_GEO_C_BALL_BOX);
+    geo_count(cnt, culled, WOS_GEO_C_CONE);
+    const bool path = !tree || geo_tree_path_ok(sc.stree, gi, [&](const float* N) { return ball_box_maybe<DIM>(N, x, r2_0); });
+    if (any && !(maybe && path)) sd |= WOS_GEO_S_BALL_BOX;
+    if (any && culled) sd |= WOS_GEO_S_CONE;
+  }
+  if (use_cell) {
+    const uint16_t* off = reinterpret_cast<const uint16_t*>(G.sgrid);
+    const uint8_t* lst = reinterpret_cast<const uint8_t*>(G.sgrid + G.sgrid_off_words);
+    const int cb = off[cell], ce = off[cell + 1];
+    bool held = winner < 0;
+    for (int k = cb; k < ce; k++) held = held || (int)lst[k] == winner;
+    cnt[WOS_GEO_C_CELL_LEN] = (uint32_t)(ce - cb);
+    if (!held) sd |= WOS_GEO_S_STAR_CELL;
+  }
+  *snd = sd;
+}
+
+template <int DIM>
+__device__ __forceinline__ void geo_dirichlet(const DevScene& sc, const LGeom& G, bool on, const float* it, int lane,
+                                              float* out, int32_t* tag, uint32_t* snd, uint32_t* cnt) {
+  constexpr int PS = Layout<DIM>::prim;
+  const int nd = sc.n_dprims, ng = sc.n_dgroups;
+  float x[DIM];
+  for (int k = 0; k < DIM; k++) x[k] = on ? it[k] : 0.0f;
+  float d[3] = {0.0f, 0.0f, 0.0f}, proj[2][DIM];
+  int winner = -1;
+  float wd2 = kFltMax;
+  if (on) {
+    d[0] = dirichlet_dist_lane<DIM>(sc, x);
+    // projectToDirichlet: the same `<=` scan, keeping the closest point
+    for (int k = 0; k < DIM; k++) proj[0][k] = proj[1][k] = x[k];
+    for (int p = 0; p < nd; p++) {
+      float pt[DIM], t0, t1;
+      const float dp = cp_prim<DIM>(G.dprim + p * PS, x, pt, &t0, &t1);
+      if (dp * dp <= wd2) {
+        wd2 = dp * dp; winner = p;
+        for (int k = 0; k < DIM; k++) proj[0][k] = pt[k];
+      }
+    }
+    d[1] = dirichlet_dist_culled<DIM, true>(sc, G.dprim, G.dgroup, x, proj[1]);
+  }
+  dirichlet_dist_step<DIM>(sc, G, on, x, d[2], lane);
+  // dirichlet_dist_step's regime
+  int t = WOS_GEO_DIR_NONE;
+  int cell = -1;
+  if (nd > 0) {
+    if (DIM == 2 && sc.dgrid != nullptr) {
+      int c = 0;
+      bool inside = true;
+      for (int k = 1; k >= 0 && inside; k--) {
+        const int nk = sc.dgrid_n[k];
+        const float v = (x[k] - sc.dgrid_min[k]) * sc.dgrid_inv[k];
+        if (!(v >= 0.0f && v < (float)nk)) { inside = false; break; }
+        int i = (int)v;
+        if (i > nk - 1) i = nk - 1;
+        c = c * nk + i;
+      }
+      cell = inside ? c : -1;
+      t = inside ? WOS_GEO_DIR_GRID : WOS_GEO_DIR_GRID_MISS;
+    } else {
+      const uint64_t m = __ballot(on);
+      t = (m & (m - 1)) == 0 ? WOS_GEO_DIR_SOLO : (sc.dtree.levels > 0 ? WOS_GEO_DIR_TREE : WOS_GEO_DIR_CULLED);
+    }
+  }
+  if (!on) return;
+  *tag = t;
+  for (int q = 0; q < 3; q++) out[q * WOS_GEO_OUT] = d[q];
+  for (int q = 0; q < 2; q++)
+    for (int k = 0; k < DIM; k++) out[q * WOS_GEO_OUT + 1 + k] = proj[q][k];
+  if (nd <= 0) return;
+  uint32_t s = 0;
+  for (int gi = 0; gi < ng; gi++) {
+    const float* B = G.dgroup + gi * kGroupStride;
+    // the bound lies below the computed distance of every member, so a group the scans skip
+    // (bound above the running minimum) never holds the winner
+    const float lb = box_dist2<DIM>(B, x);
+    const int p1 = (gi + 1) * kGroup < nd ? (gi + 1) * kGroup : nd;
+    for (int p = gi * kGroup; p < p1; p++) {
+      float pt[DIM], t0, t1;
+      const float dp = cp_prim<DIM>(G.dprim + p * PS, x, pt, &t0, &t1);
+      bool below = !(lb > dp * dp);
+      for (int Lv = 1; Lv <= sc.dtree.levels; Lv++)
+        below = below && !(box_dist2<DIM>(tree_node(sc.dtree, Lv, gi >> (3 * Lv)), x) > dp * dp);
+      if (!below) s |= WOS_GEO_S_DIR_BOX;
+    }
+    geo_count(cnt, lb > wd2, WOS_GEO_C_DIR_BOX);
+  }
+  if (cell >= 0) {
+    const uint32_t b = sc.dgrid[cell], e = sc.dgrid[cell + 1];
+    const uint16_t* lst = reinterpret_cast<const uint16_t*>(sc.dgrid + sc.dgrid_off_words);
+    bool held = false;
+    for (uint32_t i = b; i < e; i++) held = held || (int)lst[i] == winner;
+    cnt[WOS_GEO_C_CELL_LEN] = e - b;
+    if (!held) s |= WOS_GEO_S_DIR_CELL;
+  }
+  *snd = s;
+}
+
+template <int DIM, bool GG, int KIND>
+__global__ __launch_bounds__(kBlock) void wos_geometry_selftest_kernel(const DevScene sc, const DevParams prm,
+                                                                      const float* __restrict__ items,
+                                                                      const unsigned long long* __restrict__ masks,
+                                                                      const int32_t* __restrict__ first, int n_masks,
+                                                                      int geom_floats, float* __restrict__ out,
+                                                                      int32_t* __restrict__ tags,
+                                                                      uint32_t* __restrict__ sound,
+                                                                      uint32_t* __restrict__ counts) {
+  extern __shared__ __attribute__((aligned(16))) float probe_smem[];
+  const int lane = threadIdx.x & (kWave - 1);
+  const LGeom G = stage_geometry<DIM, GG>(sc, probe_smem, true);
+  __syncthreads();
+  // per-wave scratch shared by the star and ray queries, as the walk kernel lays it out
+  const int wave_u = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / kWave));
+  char* wscratch = reinterpret_cast<char*>(probe_smem + geom_floats) + wave_u * walk_scratch_bytes<DIM>();
+  const int w = (int)blockIdx.x * (kBlock / kWave) + wave_u;
+  if (w >= n_masks) return;  // wave-uniform; no block barrier follows
+  const unsigned long long mask = masks[w];
+  const bool on = ((mask >> lane) & 1ull) != 0;
+  const int64_t i = (int64_t)first[w] + __popcll(mask & ((1ull << lane) - 1ull));
+  constexpr int IW = KIND == WOS_GEO_RAY ? 2 * DIM + 1 : (KIND == WOS_GEO_STAR ? DIM + 2 : DIM);
+  const float* it = items + (on ? i : 0) * IW;
+  float res[3 * WOS_GEO_OUT] = {};
+  uint32_t cnt[WOS_GEO_COUNTS] = {};
+  int32_t tag = 0;
+  uint32_t snd = 0;
+  if constexpr (KIND == WOS_GEO_RAY)
+    geo_ray<DIM, GG>(sc, G, on, it, reinterpret_cast<RayLDS<DIM>*>(wscratch), lane, res, &tag, &snd, cnt);
+  else if constexpr (KIND == WOS_GEO_STAR)
+    geo_star<DIM, GG>(sc, prm, G, on, it, reinterpret_cast<StarLDS<DIM>*>(wscratch), lane, res, &tag, &snd, cnt);
+  else
+    geo_dirichlet<DIM>(sc, G, on, it, lane, res, &tag, &snd, cnt);
+  if (!on) return;
+  for (int k = 0; k < 3 * WOS_GEO_OUT; k++) out[i * 3 * WOS_GEO_OUT + k] = res[k];
+  for (int k = 0; k < WOS_GEO_COUNTS; k++) counts[i * WOS_GEO_COUNTS + k] = cnt[k];
+  tags[i] = tag;
+  sound[i] = snd;
+}
+
+template <int DIM, bool GG>
+void launch_geometry_kind(int kind, const DevScene& sc, const DevParams& prm, const float* items,
+                          const unsigned long long* masks, const int32_t* first, int n_masks, size_t shmem,
+                          int geom_floats, float* out, int32_t* tags, uint32_t* sound, uint32_t* counts, hipStream_t s) {
+  const dim3 grid((n_masks + kBlock / kWave - 1) / (kBlock / kWave)), blk(kBlock);
+  if (kind == WOS_GEO_RAY)
+    hipLaunchKernelGGL((wos_geometry_selftest_kernel<DIM, GG, WOS_GEO_RAY>), grid, blk, shmem, s, sc, prm, items, masks,
+                       first, n_masks, geom_floats, out, tags, sound, counts);
+  else if (kind == WOS_GEO_STAR)
+    hipLaunchKernelGGL((wos_geometry_selftest_kernel<DIM, GG, WOS_GEO_STAR>), grid, blk, shmem, s, sc, prm, items, masks,
+                       first, n_masks, geom_floats, out, tags, sound, counts);
+  else
+    hipLaunchKernelGGL((wos_geometry_selftest_kernel<DIM, GG, WOS_GEO_DIRICHLET>), grid, blk, shmem, s, sc, prm, items,
+                       masks, first, n_masks, geom_floats, out, tags, sound, counts);
+}
+
+}  // namespace
+
+hipError_t launch_geometry_selftest(int dim, int kind, const DevScene& sc, const DevParams& prm, const float* items,
+                                    const unsigned long long* masks, const int32_t* first, int n_masks, size_t shmem,
+                                    int geom_floats, float* out, int32_t* tags, uint32_t* sound, uint32_t* counts,
+                                    hipStream_t s) {
+  if (dim == 2 && sc.geom_global)
+    launch_geometry_kind<2, true>(kind, sc, prm, items, masks, first, n_masks, shmem, geom_floats, out, tags, sound, counts, s);
+  else if (dim == 2)
+    launch_geometry_kind<2, false>(kind, sc, prm, items, masks, first, n_masks, shmem, geom_floats, out, tags, sound, counts, s);
+  else if (sc.geom_global)
+    launch_geometry_kind<3, true>(kind, sc, prm, items, masks, first, n_masks, shmem, geom_floats, out, tags, sound, counts, s);
+  else
+    launch_geometry_kind<3, false>(kind, sc, prm, items, masks, first, n_masks, shmem, geom_floats, out, tags, sound, counts, s);
+  return hipGetLastError();
+}
+
 }  // namespace wos

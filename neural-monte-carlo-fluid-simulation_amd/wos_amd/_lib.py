@@ -131,7 +131,7 @@ EXPORTS = (
     "wos_tape_record", "wos_tape_solve", "wos_tape_get_info", "wos_tape_destroy",
     "wos_tape_vjp", "wos_tape_read",
     "wos_tape_index_build", "wos_tape_index_get_info", "wos_tape_index_read", "wos_tape_vjp_indexed",
-    "wos_selftest_tape_rowsum", "wos_selftest_rejection",
+    "wos_selftest_tape_rowsum", "wos_selftest_rejection", "wos_selftest_geometry",
     "wos_scene_query",
     "wos_siren_eval", "wos_selftest_siren_layer",
     "wos_siren_vjp", "wos_selftest_siren_vjp_layer",
@@ -140,6 +140,19 @@ EXPORTS = (
     "wos_siren_fit_run_ensemble", "wos_siren_fit_run_batches_ensemble",
     "wos_set_length_hints", "wos_length_hint_stats", "wos_selftest_hint_key",
 )
+
+# include/wos.h WOS_GEO_*: wos_selftest_geometry's kinds, regime tags, soundness bits and count slots
+GEO_RAY, GEO_STAR, GEO_DIRICHLET = 0, 1, 2
+GEO_OUT, GEO_COUNTS = 8, 16
+GEO_RAY_NONE, GEO_RAY_LANE_SCAN, GEO_RAY_SOLO, GEO_RAY_LIST, GEO_RAY_TREE = range(5)
+GEO_STAR_NONE, GEO_STAR_SOLO_CELL, GEO_STAR_CELL_LISTS, GEO_STAR_GROUPS, GEO_STAR_TREE = range(5)
+GEO_STAR_MIXED = 0x100
+GEO_DIR_NONE, GEO_DIR_GRID, GEO_DIR_GRID_MISS, GEO_DIR_SOLO, GEO_DIR_CULLED, GEO_DIR_TREE = range(6)
+GEO_SOUND = {"ray_box": 0x1, "ray_prefilter": 0x2, "ball_box": 0x4, "cone": 0x8, "class2": 0x10,
+             "star_early": 0x20, "star_cell": 0x40, "dir_box": 0x80, "dir_cell": 0x100}
+# counts[:, slot] fired, counts[:, slot + 1] declined
+GEO_COUNT = {"ray_box": 0, "ray_prefilter": 2, "ball_box": 4, "cone": 6, "star_early": 8, "dir_box": 10}
+GEO_C_CLASS, GEO_C_CELL_LEN = 12, 15
 
 # include/wos.h WOS_QUERY_*: the boundary wos_scene_query's dist / signed_dist / closest describe
 QUERY_NEUMANN, QUERY_DIRICHLET = 0, 1
@@ -301,6 +314,11 @@ def load():
     L.wos_selftest_rejection.restype = C.c_int
     L.wos_selftest_rejection.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_int32]
+    if hasattr(L, "wos_selftest_geometry"):  # additive within ABI 10 as well
+        L.wos_selftest_geometry.restype = C.c_int
+        L.wos_selftest_geometry.argtypes = [C.c_void_p, C.c_uint32, C.c_float, C.c_float, C.c_int32, C.c_void_p,
+                                            C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p]
     L.wos_last_error.restype = C.c_char_p
     L.wos_last_error.argtypes = []
     L.wos_abi_version.restype = C.c_int32

@@ -452,6 +452,33 @@ class WosScene:
             check(L.wos_scene_query(self._h, which, mask, x.ctypes.data, n, *ptr, s, 0), "wos_scene_query")
         return tuple(out)
 
+    def selftest_geometry(self, kind, items, masks, *, schedule=0, min_star_radius=1e-3, silhouette_precision=1e-3):
+        """The walk step's geometry queries on `items`, run by the kernels' own device code on the
+        scene planned as a solve under `schedule` plans it (wos_selftest_geometry).  kind: "ray"
+        (items [n, 2 dim + 1] = origin, direction, tmax), "star" ([n, dim + 2] = x, maxR, flip) or
+        "dirichlet" ([n, dim] = x); masks: one 64-bit lane mask per wave, whose set bits take the
+        items in order.  Returns a dict: out float32 [n, 3, 8] (exact scan, per-lane culled form,
+        wave-cooperative form), tags int32 [n], sound uint32 [n], counts uint32 [n, 16] (_lib.GEO_*)
+        and plan = a dict of how the scene was planned (geom_global, star_grid, dir_grid, lds_bytes,
+        ptree / stree / dtree levels, n_silhouettes)."""
+        k = {"ray": _lib.GEO_RAY, "star": _lib.GEO_STAR, "dirichlet": _lib.GEO_DIRICHLET}.get(kind, kind)
+        width = {_lib.GEO_RAY: 2 * self.dim + 1, _lib.GEO_STAR: self.dim + 2, _lib.GEO_DIRICHLET: self.dim}.get(k, 1)
+        x = np.ascontiguousarray(items, dtype=np.float32).reshape(-1, width)
+        m = np.ascontiguousarray(masks, dtype=np.uint64).reshape(-1)
+        n = x.shape[0]
+        out = np.zeros((n, 3, _lib.GEO_OUT), np.float32)
+        tags = np.zeros(n, np.int32)
+        sound = np.zeros(n, np.uint32)
+        counts = np.zeros((n, _lib.GEO_COUNTS), np.uint32)
+        plan = np.zeros(8, np.int32)
+        check(_lib.load().wos_selftest_geometry(self._h, int(schedule), float(min_star_radius),
+                                                float(silhouette_precision), int(k), x.ctypes.data, n, m.ctypes.data,
+                                                m.size, out.ctypes.data, tags.ctypes.data, sound.ctypes.data,
+                                                counts.ctypes.data, plan.ctypes.data), "wos_selftest_geometry")
+        names = ("geom_global", "star_grid", "dir_grid", "lds_bytes", "ptree", "stree", "dtree", "n_silhouettes")
+        return {"out": out, "tags": tags, "sound": sound, "counts": counts,
+                "plan": {k: int(p) for k, p in zip(names, plan)}}
+
     def record(self, pts, params=None, *, index_base=0, index_stride=1, max_bytes=None):
         """Record the walks of solve(pts, params, index_base=..., index_stride=...) once
         (wos_tape_record; blocking, about two solves).  The returned WalkTape replays them for

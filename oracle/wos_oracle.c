@@ -1935,6 +1935,65 @@ int oracle_point_info(const oracle_scene_desc *scene, const float *pt,
     return 0;
 }
 
+/* The three geometry queries of a walk step, batched: the scene is built once and the statics
+ * oracle_solve calls answer n items.  Arrays are [n][dim] (o, dir, x, p, nrm, proj) or [n]. */
+int oracle_ray_hits(const oracle_scene_desc *scene, const float *o, const float *dir, const float *tmax, int64_t n,
+                    int32_t *found, float *d, float *p, float *nrm)
+{
+    scene_t sc;
+    g_libm = 0;
+    if (scene_build(&sc, scene)) { scene_free(&sc); return -3; }
+    const int dim = sc.dim;
+    for (int64_t i = 0; i < n; i++) {
+        float oo[3] = {0, 0, 0}, dd[3] = {0, 0, 0};
+        for (int k = 0; k < dim; k++) { oo[k] = o[i * dim + k]; dd[k] = dir[i * dim + k]; }
+        hit_t h;
+        memset(&h, 0, sizeof(h));
+        found[i] = ray_first_hit(&sc.neu, oo, dd, tmax[i], &h, 0);
+        d[i] = found[i] ? h.d : 0.0f;
+        for (int k = 0; k < dim; k++) {
+            p[i * dim + k] = found[i] ? h.p[k] : 0.0f;
+            nrm[i * dim + k] = found[i] ? h.n[k] : 0.0f;
+        }
+    }
+    scene_free(&sc);
+    return 0;
+}
+
+int oracle_star_radii(const oracle_scene_desc *scene, const float *x, const float *maxR, const int32_t *flip,
+                      float minR, float prec, int64_t n, float *out)
+{
+    scene_t sc;
+    g_libm = 0;
+    if (scene_build(&sc, scene)) { scene_free(&sc); return -3; }
+    for (int64_t i = 0; i < n; i++) {
+        float xx[3] = {0, 0, 0};
+        for (int k = 0; k < sc.dim; k++) xx[k] = x[i * sc.dim + k];
+        out[i] = star_radius(&sc.neu, xx, minR, maxR[i], prec, flip ? flip[i] : 0);
+    }
+    scene_free(&sc);
+    return 0;
+}
+
+/* dist: computeDistToDirichlet; proj: projectToDirichlet's point (the same findClosestPoint scan);
+ * without Dirichlet geometry proj is x itself */
+int oracle_dirichlet_dists(const oracle_scene_desc *scene, const float *x, int64_t n, float *dist, float *proj)
+{
+    scene_t sc;
+    g_libm = 0;
+    if (scene_build(&sc, scene)) { scene_free(&sc); return -3; }
+    for (int64_t i = 0; i < n; i++) {
+        float xx[3] = {0, 0, 0};
+        for (int k = 0; k < sc.dim; k++) xx[k] = x[i * sc.dim + k];
+        dist[i] = dist_dirichlet(&sc, xx, 0);
+        cp_t c;
+        const int hit = closest_point(&sc.dir, xx, &c, 0) >= 0;
+        if (proj) for (int k = 0; k < sc.dim; k++) proj[i * sc.dim + k] = hit ? c.p[k] : xx[k];
+    }
+    scene_free(&sc);
+    return 0;
+}
+
 double oracle_bessel(int which, double x, int math_mode)
 {
     g_libm = math_mode == 1;

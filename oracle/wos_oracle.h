@@ -128,6 +128,19 @@ int oracle_point_info(const oracle_scene_desc *scene, const float *pt,
                       float *signed_neumann_dist, int32_t *inside,
                       float *star_radius, int32_t *n_silhouettes);
 
+/* The three geometry queries of a walk step over n items, the scene built once: the sequential
+ * brute-force scans oracle_solve itself calls.  Arrays are [n][dim] or [n].
+ *   oracle_ray_hits        intersectWithNeumann's first hit within tmax: found, and where found
+ *                          d, p and the unit normal nrm (zeros otherwise)
+ *   oracle_star_radii      computeStarRadius(x, minR, maxR, prec, flip); flip may be NULL (all 0)
+ *   oracle_dirichlet_dists computeDistToDirichlet and projectToDirichlet's point (proj may be
+ *                          NULL; x itself without Dirichlet geometry) */
+int oracle_ray_hits(const oracle_scene_desc *scene, const float *o, const float *dir, const float *tmax, int64_t n,
+                    int32_t *found, float *d, float *p, float *nrm);
+int oracle_star_radii(const oracle_scene_desc *scene, const float *x, const float *maxR, const int32_t *flip,
+                      float minR, float prec, int64_t n, float *out);
+int oracle_dirichlet_dists(const oracle_scene_desc *scene, const float *x, int64_t n, float *dist, float *proj);
+
 double oracle_bessel(int which, double x, int math_mode); /* 0:i0 1:i1 2:k0 3:k1 */
 double oracle_math(int which, double x, int math_mode);   /* 0 exp 1 log 2 sin 3 cos 4 atan, f32: 10 expf 11 logf 12 sinf 13 cosf 14 cbrtf */
 uint32_t oracle_seed32(uint64_t key, uint64_t idx, uint64_t pair, uint32_t tag);

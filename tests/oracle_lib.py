@@ -104,6 +104,14 @@ def lib():
         L.oracle_fcpw_bvh.restype = C.c_int
         L.oracle_fcpw_bvh.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+        L.oracle_ray_hits.restype = C.c_int
+        L.oracle_ray_hits.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.oracle_star_radii.restype = C.c_int
+        L.oracle_star_radii.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,
+                                        C.c_float, C.c_int64, C.c_void_p]
+        L.oracle_dirichlet_dists.restype = C.c_int
+        L.oracle_dirichlet_dists.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -226,6 +234,46 @@ def point_info(scene: OracleScene, pt):
         raise RuntimeError("oracle_point_info failed")
     keys = ["dirichlet_dist", "neumann_dist", "signed_neumann_dist", "inside", "star_radius", "n_silhouettes"]
     return {k: o.value for k, o in zip(keys, out)}
+
+
+def ray_hits(scene: OracleScene, o, d, tmax):
+    """The first ray hit of n rays (o, d [n, dim], tmax [n]): found [n] int32, d [n], p and unit normal [n, dim]."""
+    o = np.ascontiguousarray(o, np.float32)
+    d = np.ascontiguousarray(d, np.float32)
+    tmax = np.ascontiguousarray(tmax, np.float32)
+    n = o.shape[0]
+    found = np.zeros(n, np.int32)
+    dist = np.zeros(n, np.float32)
+    p = np.zeros((n, scene.dim), np.float32)
+    nrm = np.zeros((n, scene.dim), np.float32)
+    rc = lib().oracle_ray_hits(C.byref(scene.desc), o.ctypes.data, d.ctypes.data, tmax.ctypes.data, n,
+                               found.ctypes.data, dist.ctypes.data, p.ctypes.data, nrm.ctypes.data)
+    assert rc == 0, rc
+    return found, dist, p, nrm
+
+
+def star_radii(scene: OracleScene, x, max_r, flip=None, min_r=1e-3, prec=1e-3):
+    """computeStarRadius at n points x [n, dim] with maxR [n] (flip [n] int32 or None)."""
+    x = np.ascontiguousarray(x, np.float32)
+    max_r = np.ascontiguousarray(max_r, np.float32)
+    flip = None if flip is None else np.ascontiguousarray(flip, np.int32)
+    out = np.zeros(x.shape[0], np.float32)
+    rc = lib().oracle_star_radii(C.byref(scene.desc), x.ctypes.data, max_r.ctypes.data,
+                                 None if flip is None else flip.ctypes.data, min_r, prec, x.shape[0],
+                                 out.ctypes.data)
+    assert rc == 0, rc
+    return out
+
+
+def dirichlet_dists(scene: OracleScene, x):
+    """computeDistToDirichlet [n] and projectToDirichlet's point [n, dim] at n points x [n, dim]."""
+    x = np.ascontiguousarray(x, np.float32)
+    dist = np.zeros(x.shape[0], np.float32)
+    proj = np.zeros((x.shape[0], scene.dim), np.float32)
+    rc = lib().oracle_dirichlet_dists(C.byref(scene.desc), x.ctypes.data, x.shape[0], dist.ctypes.data,
+                                      proj.ctypes.data)
+    assert rc == 0, rc
+    return dist, proj
 
 
 def fcpw_pick(scene: OracleScene, x, R, us):

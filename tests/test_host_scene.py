@@ -7,6 +7,9 @@
 * soundness of the cone test (wos_kernel.hip cone_culled): for random query points,
   a group the test culls never holds a candidate the exact silhouette test
   (isWideSilhouetteVertex, wide_query_operations.h:328-358) accepts.
+
+The cone test checked here is a numpy float64 restatement; the device function itself, with its
+rsq and approximate sqrt, is checked beside the exact test by tests/test_gpu_geometry_probe.py.
 """
 import ctypes as C
 import os
