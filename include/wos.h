@@ -566,6 +566,36 @@ int wos_selftest_lhs_plan(int32_t n_pairs, int32_t dim, int32_t *out);
 int wos_selftest_rejection(int32_t dim, const float *R, const float *lambda, const float *x, int64_t n,
                            int32_t *edges, float *vals, int32_t *flags, int32_t device);
 
+/* Device self-test of the Green's-function members of the ball (Gfn, csrc/wos_device.h;
+ * distributions.h:273-832) and of the splat's 2D free-space functions (FreeSpace2, csrc/wos_bvc.hip;
+ * distributions.h:85-119, 168-219), for the GPU tests (added within ABI 10: a new entry point only;
+ * kernels in csrc/wos_selftest.hip and csrc/wos_bvc.hip).  One lane per item builds the ball as a
+ * solve does (init, update_ball), sets r, yVol = c + r dir and ySurf = c + R dir as sample_volume
+ * and the surface sample set them, and calls every member as shipped.  mode: WOS_GFN_HARMONIC,
+ * WOS_GFN_YUKAWA (reference semantics) or WOS_GFN_ROBUST (the robust kernels' instantiation with
+ * `robust` set: scaled members above mu R = 80).  items[n][WOS_GFN_ITEM]:
+ *   [0] R  [1] lambda  [2] r  [3..5] c  [6..8] dir (unit)  [9..11] x  [12..14] y
+ *   [15..16] n (2D unit normal of the free-space functions)  [17] the splat's radius clamp
+ * out[n][WOS_GFN_OUT], slots that do not apply 0:
+ *   [0..3] A0 A1 B0 B1 after update_ball (2D K0 I0 K1 I1, 3D exp sinh K32 I32 at mu R; the scaled
+ *          ke0 ie0 ke1 ie1 in 2D scaled balls, none in 3D scaled balls)  [4] mu R
+ *   [5] the ball's tag (0 harmonic, 1 Yukawa, 2 Yukawa with scaled members)
+ *   [6] evaluate  [7] gradient_norm  [8] poisson_kernel  [9] norm  [10..12] poisson_kernel_gradient
+ *   [13] dir_sampled_poisson_kernel(yVol)  [14] evaluate_xy(x, y)
+ *   [15] evaluate_k0i0  [16] gradient_norm_k1i1, both from one bessel_ik<true, true> at mu r as the
+ *          first-ball kernel feeds them (2D, tag 1)
+ *   [17..21] A0 A1 B0 B1 mu R after set_ball on the four values the point-setup kernel stores
+ *          (2D, tag 1)
+ *   [22] pdf_sphere_uniform(r)  [23..25] gradient
+ *   [26] free-space G(x, y)  [27..28] grad G  [29] P  [30..31] grad P at r = max(clamp, |y - x|),
+ *          harmonic in mode 0 and Yukawa otherwise (2D)
+ * n = 0 succeeds without a launch.  A null pointer, n < 0, dim outside 2..3 or an unknown mode is
+ * WOS_E_INVALID. */
+enum { WOS_GFN_HARMONIC = 0, WOS_GFN_YUKAWA = 1, WOS_GFN_ROBUST = 2 };
+#define WOS_GFN_ITEM 20
+#define WOS_GFN_OUT 32
+int wos_selftest_gfn(int32_t dim, int32_t mode, const float *items, int64_t n, float *out, int32_t device);
+
 /* Device self-test of the three geometry queries of a walk step -- the first ray hit, the star
  * radius and the distance to the Dirichlet boundary -- for the GPU tests (added within ABI 10: a new
  * entry point only; csrc/wos_selftest.hip).  The scene is planned exactly as wos_solve plans it under

@@ -225,6 +225,33 @@ struct FreeSpace2 {
   }
 };
 
+// wos_selftest_gfn's free-space part: FreeSpace2 on item i's (x, y, n) with the radius clamped as
+// splat_term clamps it, into slots 26..31 of the item's result (include/wos.h)
+__global__ __launch_bounds__(256) void wos_bvc_freespace_selftest_kernel(const float* __restrict__ items, int64_t n,
+                                                                         int yukawa, float* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float* it = items + i * kGfnItem;
+  float* o = out + i * kGfnOut;
+  FreeSpace2 gf;
+  gf.yukawa = yukawa != 0;
+  gf.lambda = it[1];
+  gf.sqrtLambda = __builtin_sqrtf(it[1]);
+  const float x[2] = {it[9], it[10]}, y[2] = {it[12], it[13]}, nrm[2] = {it[15], it[16]};
+  const float yx[2] = {y[0] - x[0], y[1] - x[1]};
+  const float xy[2] = {x[0] - y[0], x[1] - y[1]};
+  const float r = smax(it[17], __builtin_sqrtf(yx[0] * yx[0] + yx[1] * yx[1]));
+  float K0 = 0.0f, K1 = 0.0f, K2 = 0.0f;
+  if (gf.yukawa) gf.bessel_k(r * gf.sqrtLambda, &K0, &K1, &K2);
+  float dG[2], dP[2];
+  gf.gradient(r, xy, K1, dG);
+  gf.poisson_gradient(r, xy, nrm, K0, K1, K2, dP);
+  o[26] = gf.evaluate(r, K0);
+  o[27] = dG[0]; o[28] = dG[1];
+  o[29] = gf.poisson(r, xy, nrm, K1);
+  o[30] = dP[0]; o[31] = dP[1];
+}
+
 __device__ __forceinline__ bool finite_f(float v) { return __builtin_isfinite(v); }
 
 // One (evaluation point, cached sample) term of Splatter::splat: the estimate and its
@@ -438,6 +465,13 @@ hipError_t launch_bvc_start(const DevScene& sc, const DevParams& prm, const floa
 hipError_t launch_bvc_fd(const DevScene& sc, const float* pts, const float* sol, int64_t n, float* dn, hipStream_t s) {
   if (n <= 0) return hipSuccess;
   hipLaunchKernelGGL(wos_bvc_fd_kernel, dim3((int)((n + 255) / 256)), dim3(256), 0, s, sc, pts, sol, n, dn);
+  return hipGetLastError();
+}
+
+hipError_t launch_freespace_selftest(const float* items, int64_t n, int yukawa, float* out, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(wos_bvc_freespace_selftest_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, items, n,
+                     yukawa, out);
   return hipGetLastError();
 }
 

@@ -150,6 +150,29 @@ int wos_selftest_rejection(int32_t dim, const float* R, const float* lambda, con
   return WOS_OK;
 }
 
+int wos_selftest_gfn(int32_t dim, int32_t mode, const float* items, int64_t n, float* out, int32_t device) {
+  static_assert(WOS_GFN_ITEM == wos::kGfnItem && WOS_GFN_OUT == wos::kGfnOut, "include/wos.h and wos_launch.h agree");
+  if (!items || !out || n < 0 || n > (1LL << 24) || (dim != 2 && dim != 3))
+    return fail(WOS_E_INVALID, "wos_selftest_gfn: bad argument");
+  if (mode != WOS_GFN_HARMONIC && mode != WOS_GFN_YUKAWA && mode != WOS_GFN_ROBUST)
+    return fail(WOS_E_INVALID, "wos_selftest_gfn: mode must be WOS_GFN_HARMONIC (0), WOS_GFN_YUKAWA (1) or "
+                               "WOS_GFN_ROBUST (2), got " + std::to_string(mode));
+  if (n == 0) return WOS_OK;
+  const size_t N = (size_t)n;
+  HIP_TRY(hipSetDevice(device));
+  DevBufs tmp;
+  float *d_items = nullptr, *d_out = nullptr;
+  HIP_TRY(tmp.get(&d_items, N * WOS_GFN_ITEM));
+  HIP_TRY(tmp.get(&d_out, N * WOS_GFN_OUT));
+  HIP_TRY(hipMemcpy(d_items, items, N * WOS_GFN_ITEM * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemset(d_out, 0, N * WOS_GFN_OUT * 4));
+  HIP_TRY(wos::launch_gfn_selftest(dim, mode, d_items, n, d_out, nullptr));
+  if (dim == 2) HIP_TRY(wos::launch_freespace_selftest(d_items, n, mode != WOS_GFN_HARMONIC, d_out, nullptr));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(out, d_out, N * WOS_GFN_OUT * 4, hipMemcpyDeviceToHost));
+  return WOS_OK;
+}
+
 int wos_selftest_geometry(wos_scene* s, uint32_t schedule, float min_star_radius, float silhouette_precision,
                           int32_t kind, const float* items, int64_t n, const uint64_t* masks, int32_t n_masks,
                           float* out, int32_t* tags, uint32_t* sound, uint32_t* counts, int32_t* plan) {

@@ -87,6 +87,13 @@ hipError_t launch_geometry_selftest(int dim, int kind, const DevScene& sc, const
                                     int geom_floats, float* out, int32_t* tags, uint32_t* sound, uint32_t* counts,
                                     hipStream_t s);
 
+// probe of the Green's-function members (include/wos.h wos_selftest_gfn): n items of kGfnItem floats,
+// out [n][kGfnOut]; the ball's members from wos_selftest.hip (slots 0..25), the 2D free-space
+// functions from wos_bvc.hip beside FreeSpace2 (slots 26..31)
+constexpr int kGfnItem = 20, kGfnOut = 32;  // WOS_GFN_ITEM, WOS_GFN_OUT
+hipError_t launch_gfn_selftest(int dim, int mode, const float* items, int64_t n, float* out, hipStream_t s);
+hipError_t launch_freespace_selftest(const float* items, int64_t n, int yukawa, float* out, hipStream_t s);
+
 // boundary value caching (wos_bvc.hip), 2D
 hipError_t launch_bvc_point_info(const DevScene& sc, const float* pts, int64_t n, float* dd, float* nd,
                                  int32_t* inside, float* src, hipStream_t s);

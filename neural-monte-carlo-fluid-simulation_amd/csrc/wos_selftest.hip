@@ -4,7 +4,8 @@
 // the LDS layout wos_first_ball_kernel gives one wave, so a test can pin every regime of the
 // sampler against the oracle's sequential loop without a full solve.  And a probe of the rejection
 // sampler's decision functions (wos_selftest_rejection): the edge of each one over every draw a
-// stream can produce.  A translation unit of its own: what a unit instantiates changes its
+// stream can produce; and a probe of the
+// Green's-function members of the ball (wos_selftest_gfn).  A translation unit of its own: what a unit instantiates changes its
 // kernels' inlining and scratch (DESIGN.md "Kernel variants"), and these instantiations must not
 // touch the five kernel units.
 #include "wos_device.h"
@@ -277,6 +278,74 @@ hipError_t launch_rejection_selftest(int dim, const float* rej_tab, const float*
     hipLaunchKernelGGL(wos_rejection_selftest_kernel<2>, dim3(grid), dim3(256), 0, s, prm, R, lambda, x, n, edges, vals, flags);
   else
     hipLaunchKernelGGL(wos_rejection_selftest_kernel<3>, dim3(grid), dim3(256), 0, s, prm, R, lambda, x, n, edges, vals, flags);
+  return hipGetLastError();
+}
+
+// ---- the Green's-function members of the ball (wos_selftest_gfn) ----------------------------------
+// One lane per item: the ball as a solve builds it (init, update_ball), r, yVol and ySurf set as
+// sample_volume and the surface sample set them, then every member function as shipped.  The probe
+// adds no arithmetic to them.  MODE 0 harmonic, 1 Yukawa reference semantics, 2 the robust kernels'
+// instantiation with `robust` set.
+template <int DIM, int MODE>
+__global__ __launch_bounds__(256) void wos_gfn_selftest_kernel(const float* __restrict__ items, int64_t n,
+                                                               float* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float* it = items + i * WOS_GFN_ITEM;
+  float* o = out + i * WOS_GFN_OUT;
+  float c[DIM], dir[DIM], x[DIM], y[DIM];
+  for (int k = 0; k < DIM; k++) { c[k] = it[3 + k]; dir[k] = it[6 + k]; x[k] = it[9 + k]; y[k] = it[12 + k]; }
+  Gfn<DIM, MODE == 2> g;
+  g.muR = g.A0 = g.A1 = g.B0 = g.B1 = 0.0f;
+  g.init(MODE != 0, it[1]);
+  g.update_ball(c, it[0], MODE == 2);
+  g.r = it[2];
+  for (int k = 0; k < DIM; k++) { g.yVol[k] = g.c[k] + g.r * dir[k]; g.ySurf[k] = g.c[k] + g.R * dir[k]; }
+  float res[WOS_GFN_OUT] = {};
+  const bool members = g.yukawa == 1 || (g.yukawa == kYukScaled && DIM == 2);
+  if (members) { res[0] = g.A0; res[1] = g.A1; res[2] = g.B0; res[3] = g.B1; }
+  if (g.yukawa) res[4] = g.muR;
+  res[5] = (float)g.yukawa;
+  res[6] = g.evaluate();
+  res[7] = g.gradient_norm();
+  res[8] = g.poisson_kernel();
+  res[9] = g.norm();
+  g.poisson_kernel_gradient(res + 10);
+  res[13] = g.dir_sampled_poisson_kernel(g.yVol);
+  res[14] = g.evaluate_xy(x, y);
+  if constexpr (DIM == 2 && MODE != 0) {
+    if (g.yukawa == 1) {
+      // the fused forms, fed as the first-ball kernel feeds them
+      double i0, k0, i1, k1;
+      bessel_ik<true, true>((double)(g.r * g.sqrtLambda), &i0, &k0, &i1, &k1);
+      res[15] = g.evaluate_k0i0(k0, i0);
+      res[16] = g.gradient_norm_k1i1(k1, i1);
+      // set_ball on the members the point-setup kernel stores (its own update_ball)
+      Gfn<2> gp;
+      gp.init(true, it[1]);
+      gp.update_ball(c, it[0], false);
+      const float pb[4] = {gp.A0, gp.A1, gp.B0, gp.B1};
+      Gfn<2> gs;
+      gs.init(true, it[1]);
+      gs.set_ball(c, it[0], pb);
+      res[17] = gs.A0; res[18] = gs.A1; res[19] = gs.B0; res[20] = gs.B1; res[21] = gs.muR;
+    }
+  }
+  res[22] = pdf_sphere_uniform<DIM>(g.r);
+  g.gradient(res + 23);
+  // [26..31] belong to the free-space probe (wos_bvc.hip)
+  for (int k = 0; k < 26; k++) o[k] = res[k];
+}
+
+hipError_t launch_gfn_selftest(int dim, int mode, const float* items, int64_t n, float* out, hipStream_t s) {
+  const dim3 grid((unsigned)((n + 255) / 256)), blk(256);
+#define WOS_GFN_LAUNCH(D, M) hipLaunchKernelGGL((wos_gfn_selftest_kernel<D, M>), grid, blk, 0, s, items, n, out)
+  if (dim == 2) {
+    if (mode == 0) WOS_GFN_LAUNCH(2, 0); else if (mode == 1) WOS_GFN_LAUNCH(2, 1); else WOS_GFN_LAUNCH(2, 2);
+  } else {
+    if (mode == 0) WOS_GFN_LAUNCH(3, 0); else if (mode == 1) WOS_GFN_LAUNCH(3, 1); else WOS_GFN_LAUNCH(3, 2);
+  }
+#undef WOS_GFN_LAUNCH
   return hipGetLastError();
 }
 

@@ -131,7 +131,7 @@ EXPORTS = (
     "wos_tape_record", "wos_tape_solve", "wos_tape_get_info", "wos_tape_destroy",
     "wos_tape_vjp", "wos_tape_read",
     "wos_tape_index_build", "wos_tape_index_get_info", "wos_tape_index_read", "wos_tape_vjp_indexed",
-    "wos_selftest_tape_rowsum", "wos_selftest_rejection", "wos_selftest_geometry",
+    "wos_selftest_tape_rowsum", "wos_selftest_rejection", "wos_selftest_geometry", "wos_selftest_gfn",
     "wos_scene_query",
     "wos_siren_eval", "wos_selftest_siren_layer",
     "wos_siren_vjp", "wos_selftest_siren_vjp_layer",
@@ -140,6 +140,10 @@ EXPORTS = (
     "wos_siren_fit_run_ensemble", "wos_siren_fit_run_batches_ensemble",
     "wos_set_length_hints", "wos_length_hint_stats", "wos_selftest_hint_key",
 )
+
+# include/wos.h WOS_GFN_*: wos_selftest_gfn's modes and its item and result widths
+GFN_HARMONIC, GFN_YUKAWA, GFN_ROBUST = 0, 1, 2
+GFN_ITEM, GFN_OUT = 20, 32
 
 # include/wos.h WOS_GEO_*: wos_selftest_geometry's kinds, regime tags, soundness bits and count slots
 GEO_RAY, GEO_STAR, GEO_DIRICHLET = 0, 1, 2
@@ -321,6 +325,8 @@ def load():
                                             C.c_void_p, C.c_void_p]
     L.wos_last_error.restype = C.c_char_p
     L.wos_last_error.argtypes = []
+    L.wos_selftest_gfn.restype = C.c_int
+    L.wos_selftest_gfn.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32]
     L.wos_abi_version.restype = C.c_int32
     L.wos_device_count.restype = C.c_int32
     if L.wos_abi_version() != ABI_VERSION:

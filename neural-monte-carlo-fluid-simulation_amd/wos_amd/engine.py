@@ -825,6 +825,17 @@ def selftest_rejection(dim, R, lam, x, device=0):
     return edges, vals, flags
 
 
+def selftest_gfn(dim, mode, items, device=0):
+    """The Green's-function members of the ball and the 2D free-space functions on items
+    float32 [n, GFN_ITEM], run by the kernels' own device code (wos_selftest_gfn; layouts in
+    include/wos.h).  mode 0 harmonic, 1 Yukawa, 2 Yukawa robust.  Returns float32 [n, GFN_OUT]."""
+    items = np.ascontiguousarray(items, dtype=np.float32).reshape(-1, _lib.GFN_ITEM)
+    out = np.zeros((items.shape[0], _lib.GFN_OUT), np.float32)
+    check(_lib.load().wos_selftest_gfn(int(dim), int(mode), items.ctypes.data, items.shape[0], out.ctypes.data,
+                                       device), "wos_selftest_gfn")
+    return out
+
+
 def selftest_lhs(key, gidx, n_pairs, dim, jump_lds=True, device=0):
     """The first-ball kernel's stratified samples of the point indices gidx, built by the
     kernel's own device code (wos_selftest_lhs): float32 [n, 2 n_pairs, dim - 1]."""

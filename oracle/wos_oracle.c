@@ -2245,6 +2245,50 @@ static void fs2_k(float mur, float *K0, float *K1, float *K2)
     *K2 = (float)(k0 + (1.0 * tox) * k1);
 }
 
+static float fs2_evaluate(const fs2_t *gf, float r, float K0)
+{
+    if (!gf->yukawa) return (float)((double)(-m_logf(r)) / TWO_PI_D);
+    return (float)((double)K0 / TWO_PI_D);
+}
+
+static void fs2_gradient(const fs2_t *gf, float r, const float *xy, float K1, float *dG)
+{
+    if (!gf->yukawa) {
+        float s = (float)(TWO_PI_D * (double)(r * r));
+        for (int k = 0; k < 2; k++) dG[k] = (-xy[k]) / s;
+        return;
+    }
+    float Qr = gf->sqrtLambda * K1;
+    float s = (float)(TWO_PI_D * (double)r);
+    for (int k = 0; k < 2; k++) dG[k] = ((-xy[k]) * Qr) / s;
+}
+
+static float fs2_poisson(const fs2_t *gf, float r, const float *xy, const float *n, float K1)
+{
+    float nd = n[0] * xy[0] + n[1] * xy[1];
+    if (!gf->yukawa) return (float)((double)nd / (TWO_PI_D * (double)(r * r)));
+    float Qr = gf->sqrtLambda * K1;
+    return (float)((double)(nd * Qr) / (TWO_PI_D * (double)r));
+}
+
+static void fs2_poisson_gradient(const fs2_t *gf, float r, const float *xy, const float *n, float K0, float K1,
+                                 float K2, float *dP)
+{
+    float r2 = r * r;
+    float nd = n[0] * xy[0] + n[1] * xy[1];
+    if (!gf->yukawa) {
+        float c = 2.0f * (nd / r2);
+        float s = (float)(TWO_PI_D * (double)r2);
+        for (int k = 0; k < 2; k++) dP[k] = (n[k] - c * xy[k]) / s;
+        return;
+    }
+    float Qr1 = gf->sqrtLambda * K1;
+    float Qr2 = gf->lambda * (K0 + K2) / 2.0f;
+    float c = (nd / r2) * (Qr1 + r * Qr2);
+    float s = (float)(TWO_PI_D * (double)r);
+    for (int k = 0; k < 2; k++) dP[k] = (n[k] * Qr1 - c * xy[k]) / s;
+}
+
 typedef struct { float mean, g[2]; int n; } sstat_t;
 static void sstat_add(sstat_t *s, float est, const float *ge)
 {
@@ -2268,39 +2312,15 @@ static void bvc_splat_point(const fs2_t *gf, const float *x, const recbuf_t *rb,
         float r = smaxf(radius_clamp, sqrtf(yx[0] * yx[0] + yx[1] * yx[1]));
         float K0 = 0, K1 = 0, K2 = 0;
         if (gf->yukawa) fs2_k(r * gf->sqrtLambda, &K0, &K1, &K2);
-        float G, dG[2];
-        if (!gf->yukawa) {
-            G = (float)((double)(-m_logf(r)) / TWO_PI_D);
-            float s = (float)(TWO_PI_D * (double)(r * r));
-            for (int k = 0; k < 2; k++) dG[k] = (-xy[k]) / s;
-        } else {
-            G = (float)((double)K0 / TWO_PI_D);
-            float Qr = gf->sqrtLambda * K1;
-            float s = (float)(TWO_PI_D * (double)r);
-            for (int k = 0; k < 2; k++) dG[k] = ((-xy[k]) * Qr) / s;
-        }
+        float G = fs2_evaluate(gf, r, K0), dG[2];
+        fs2_gradient(gf, r, xy, K1, dG);
         float dGNorm = sqrtf(dG[0] * dG[0] + dG[1] * dG[1]);
         float est, ge[2];
         if (kind != KB_DOMAIN) {
             float sg = slot == 1 ? -1.0f : 1.0f;
             float n[2] = {R[2] * sg, R[3] * sg};
-            float nd = n[0] * xy[0] + n[1] * xy[1];
-            float P, dP[2];
-            float r2 = r * r;
-            if (!gf->yukawa) {
-                P = (float)((double)nd / (TWO_PI_D * (double)r2));
-                float c = 2.0f * (nd / r2);
-                float s = (float)(TWO_PI_D * (double)r2);
-                for (int k = 0; k < 2; k++) dP[k] = (n[k] - c * xy[k]) / s;
-            } else {
-                float Qr = gf->sqrtLambda * K1;
-                P = (float)((double)(nd * Qr) / (TWO_PI_D * (double)r));
-                float Qr1 = gf->sqrtLambda * K1;
-                float Qr2 = gf->lambda * (K0 + K2) / 2.0f;
-                float c = (nd / r2) * (Qr1 + r * Qr2);
-                float s = (float)(TWO_PI_D * (double)r);
-                for (int k = 0; k < 2; k++) dP[k] = (n[k] * Qr1 - c * xy[k]) / s;
-            }
+            float P = fs2_poisson(gf, r, xy, n, K1), dP[2];
+            fs2_poisson_gradient(gf, r, xy, n, K0, K1, K2, dP);
             float dPNorm = sqrtf(dP[0] * dP[0] + dP[1] * dP[1]);
             if (!(isfinite(G) && isfinite(P) && isfinite(dGNorm) && isfinite(dPNorm))) continue;
             if (reg > 0.0f) { r /= reg; P *= 1.0f - m_expf(-r * r); }
@@ -2473,4 +2493,64 @@ int oracle_bvc(const oracle_scene_desc *scene, const oracle_params *prm, const o
     bseg_free(&B);
     scene_free(&sc);
     return rc;
+}
+
+/* ========================================================================= */
+/* The Green's-function members on caller-supplied items (tests/test_gfn_cpu.py,
+ * tests/test_gpu_gfn.py): the gfn_* and fs2_* functions above as the solves call them,
+ * no arithmetic of its own beyond setting yVol, ySurf and r as sampleVolume and the
+ * surface sample set them and the splat's clamped radius.  Layouts: wos_oracle.h. */
+/* ========================================================================= */
+int oracle_gfn(int dim, int mode, const float *items, int64_t n, float *out)
+{
+    if (!items || !out || n < 0) return -1;
+    if ((dim != 2 && dim != 3) || mode < 0 || mode > 2) return -2;
+    g_libm = 0;
+    g_robust = mode == 2;
+    for (int64_t i = 0; i < n; i++) {
+        const float *it = items + ORACLE_GFN_ITEM * i;
+        float *o = out + ORACLE_GFN_OUT * i;
+        for (int k = 0; k < ORACLE_GFN_OUT; k++) o[k] = 0.0f;
+        float c[3] = {0, 0, 0}, dir[3] = {0, 0, 0}, x[3] = {0, 0, 0}, y[3] = {0, 0, 0};
+        for (int k = 0; k < dim; k++) { c[k] = it[3 + k]; dir[k] = it[6 + k]; x[k] = it[9 + k]; y[k] = it[12 + k]; }
+        gfn_t g;
+        gfn_init(&g, dim, mode != 0, it[1]);
+        gfn_update_ball(&g, c, it[0]);
+        g.r = it[2];
+        for (int k = 0; k < dim; k++) { g.yVol[k] = g.c[k] + g.r * dir[k]; g.ySurf[k] = g.c[k] + g.R * dir[k]; }
+        const int tag = !g.yukawa ? 0 : (g.scaled ? 2 : 1);
+        if (tag == 1 || (tag == 2 && dim == 2)) {
+            o[0] = dim == 2 ? g.K0muR : g.expmuR; o[1] = dim == 2 ? g.I0muR : g.sinhmuR;
+            o[2] = dim == 2 ? g.K1muR : g.K32muR; o[3] = dim == 2 ? g.I1muR : g.I32muR;
+        }
+        if (tag != 0) o[4] = g.muR;
+        o[5] = (float)tag;
+        o[6] = gfn_evaluate(&g);
+        o[7] = gfn_gradient_norm(&g);
+        o[8] = gfn_poisson_kernel(&g);
+        o[9] = gfn_norm(&g);
+        gfn_poisson_kernel_gradient(&g, o + 10);
+        o[13] = gfn_dir_sampled_poisson_kernel(&g, g.yVol);
+        o[14] = gfn_evaluate_xy(&g, x, y);
+        if (dim == 2 && tag == 1) {  /* the device's fused forms and set_ball restate these */
+            o[15] = o[6]; o[16] = o[7];
+            for (int k = 0; k < 5; k++) o[17 + k] = o[k];
+        }
+        o[22] = pdf_sphere_uniform(dim, g.r);
+        gfn_gradient(&g, o + 23);
+        if (dim == 2) {
+            fs2_t gf = {mode != 0, it[1], sqrtf(it[1])};
+            const float n2[2] = {it[15], it[16]};
+            float yx[2] = {y[0] - x[0], y[1] - x[1]}, xy[2] = {x[0] - y[0], x[1] - y[1]};
+            float r = smaxf(it[17], sqrtf(yx[0] * yx[0] + yx[1] * yx[1]));
+            float K0 = 0, K1 = 0, K2 = 0;
+            if (gf.yukawa) fs2_k(r * gf.sqrtLambda, &K0, &K1, &K2);
+            o[26] = fs2_evaluate(&gf, r, K0);
+            fs2_gradient(&gf, r, xy, K1, o + 27);
+            o[29] = fs2_poisson(&gf, r, xy, n2, K1);
+            fs2_poisson_gradient(&gf, r, xy, n2, K0, K1, K2, o + 30);
+        }
+    }
+    g_robust = 0;
+    return 0;
 }

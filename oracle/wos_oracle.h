@@ -141,6 +141,24 @@ int oracle_star_radii(const oracle_scene_desc *scene, const float *x, const floa
                       float minR, float prec, int64_t n, float *out);
 int oracle_dirichlet_dists(const oracle_scene_desc *scene, const float *x, int64_t n, float *dist, float *proj);
 
+/* Green's-function members of the ball (gfn_*) and the 2D free-space functions of the splat
+ * (fs2_*) on n items, as the solves call them.  mode 0 harmonic, 1 Yukawa (reference
+ * semantics), 2 Yukawa robust.  An item is ORACLE_GFN_ITEM floats:
+ *   [0] R  [1] lambda  [2] r  [3..5] c  [6..8] dir (yVol = c + r dir, ySurf = c + R dir)
+ *   [9..11] x  [12..14] y  [15..16] n (2D unit normal)  [17] the splat's radius clamp
+ * and a result ORACLE_GFN_OUT floats:
+ *   [0..3] members (2D K0 I0 K1 I1, 3D exp sinh K32 I32 at mu R; scaled in 2D robust balls)
+ *   [4] mu R  [5] tag (0 harmonic, 1 Yukawa, 2 scaled)  [6] evaluate  [7] gradient_norm
+ *   [8] poisson_kernel  [9] norm  [10..12] poisson_kernel_gradient
+ *   [13] dir_sampled_poisson_kernel(yVol)  [14] evaluate_xy(x, y)
+ *   [15] [16] evaluate, gradient_norm again and [17..21] the members and mu R again (2D, tag 1:
+ *   the device's fused forms and set_ball)  [22] pdf_sphere_uniform(r)  [23..25] gradient
+ *   [26] free-space G(x, y)  [27..28] its gradient  [29] P  [30..31] its gradient (2D)
+ * Slots that do not apply are 0.  Returns 0, -1 (null or n < 0) or -2 (dim, mode). */
+#define ORACLE_GFN_ITEM 20
+#define ORACLE_GFN_OUT 32
+int oracle_gfn(int dim, int mode, const float *items, int64_t n, float *out);
+
 double oracle_bessel(int which, double x, int math_mode); /* 0:i0 1:i1 2:k0 3:k1 */
 double oracle_math(int which, double x, int math_mode);   /* 0 exp 1 log 2 sin 3 cos 4 atan, f32: 10 expf 11 logf 12 sinf 13 cosf 14 cbrtf */
 uint32_t oracle_seed32(uint64_t key, uint64_t idx, uint64_t pair, uint32_t tag);

@@ -112,6 +112,8 @@ def lib():
                                         C.c_float, C.c_int64, C.c_void_p]
         L.oracle_dirichlet_dists.restype = C.c_int
         L.oracle_dirichlet_dists.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        L.oracle_gfn.restype = C.c_int
+        L.oracle_gfn.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]
         _lib = L
     return _lib
 
@@ -351,3 +353,18 @@ def bvc(scene: OracleScene, params: Params, bp: BvcParams):
         raise RuntimeError(f"oracle_bvc failed rc={rc}")
     return (sol.reshape(g, g), grad.reshape(g, g, 2), samples[:int(counts[3]) * 8].reshape(-1, 8).copy(),
             counts, st.as_dict())
+
+
+GFN_ITEM, GFN_OUT = 20, 32  # oracle/wos_oracle.h ORACLE_GFN_ITEM, ORACLE_GFN_OUT
+
+
+def gfn(dim, mode, items):
+    """oracle_gfn: the Green's-function members and the 2D free-space functions on items
+    float32 [n, GFN_ITEM] (layouts in oracle/wos_oracle.h); mode 0 harmonic, 1 Yukawa,
+    2 Yukawa robust.  Returns float32 [n, GFN_OUT]."""
+    items = np.ascontiguousarray(items, dtype=np.float32).reshape(-1, GFN_ITEM)
+    out = np.zeros((items.shape[0], GFN_OUT), np.float32)
+    rc = lib().oracle_gfn(int(dim), int(mode), items.ctypes.data, items.shape[0], out.ctypes.data)
+    if rc != 0:
+        raise RuntimeError(f"oracle_gfn failed: {rc}")
+    return out
