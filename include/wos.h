@@ -36,6 +36,11 @@ enum {
 #define WOS_PTRS_DEVICE 0x1u   /* pts/p/grad/n_est/steps are device pointers on the scene's device */
 #define WOS_ASYNC       0x2u   /* with WOS_PTRS_DEVICE: enqueue on `stream` and return; only
                                   stats->ticket is filled (read the rest with wos_solve_stats) */
+/* flag for wos_siren_fit, wos_siren_fit_run, wos_siren_fit_run_batches and the two _ensemble loops
+ * (added within ABI 10; a library older than this flag ignores the bit and reads `scale` as
+ * [rows][d_out], so a caller that sets it needs a library that knows it) */
+#define WOS_FIT_SCALE_MATRIX 0x4u /* scale / pool_scale / every non-NULL entry of the ensemble arrays is a
+                                     row-major d_out x d_out matrix per row: [rows][d_out][d_out] */
 
 /* A boundary mesh: 2D line segments (dim=2) or 3D triangles (dim=3). */
 typedef struct wos_mesh {
@@ -761,7 +766,16 @@ int wos_selftest_siren_vjp_layer(int32_t hidden, int32_t d_in, int64_t n_points,
  * same n and workspace_bytes returns the same bits in loss and in every gradient.  Envelope and
  * pointer rules are wos_siren_vjp's: host pointers (staged, blocking), WOS_PTRS_DEVICE, or
  * WOS_PTRS_DEVICE | WOS_ASYNC on `stream`; loss is a pointer of the same kind as pts.  There is no
- * gradient with respect to the points, scale, target or omega. */
+ * gradient with respect to the points, scale, target or omega.
+ * WOS_FIT_SCALE_MATRIX: scale is S[n*d_out*d_out], a row-major matrix per point, for a wrap
+ * u = S(x) N(x) + c(x) that mixes the network's components (a free-slip wall, u = (I - (1 - w) n n^T) N):
+ *   loss[0] = 1 / (n d_out) * sum_p sum_i ((S[p] u(x_p))_i - target[p][i])^2
+ * with r_i = -target_i, then r_i = fma(S[i][m], u_m, r_i) for m = 0 .. d_out - 1 in order, and the seed
+ * d loss / d u_m = acc (1 / (n d_out)), g_i = r_i + r_i, acc = S[0][m] g_0 (a rounded product), then
+ * acc = fma(S[i][m], g_i, acc) for i = 1 .. d_out - 1; everything else as above.  A matrix whose
+ * off-diagonal entries are exact zeros gives, for finite u, the values of the call without the flag on
+ * its diagonal (only the sign of an exact zero may differ).  The flag with a NULL scale is
+ * WOS_E_INVALID, naming scale.  Without the flag nothing changes. */
 int wos_siren_fit(const wos_siren_net *net, const float *pts, int64_t n,
                   const float *target, const float *scale, float *loss,
                   float *const *grad_weights, float *const *grad_biases,
@@ -838,7 +852,10 @@ int wos_adam_step(int32_t n_tensors, const int64_t *counts,
  * stops sets check_every.
  * WOS_E_INVALID: n_iters, batch or n_pool <= 0, step0 < 0, a NULL idx, losses, status, pool_pts or
  * pool_target, a NaN stop_loss, wos_adam_step's parameter rules, wos_siren_eval's envelope.
- * A non-zero workspace_bytes below one tile is WOS_E_CAPACITY, as in wos_siren_fit. */
+ * A non-zero workspace_bytes below one tile is WOS_E_CAPACITY, as in wos_siren_fit.
+ * WOS_FIT_SCALE_MATRIX: pool_scale is [n_pool*d_out*d_out], the gather copies rows of d_out * d_out
+ * floats and the step is wos_siren_fit's with the flag; with a NULL pool_scale it is WOS_E_INVALID,
+ * naming pool_scale. */
 int wos_siren_fit_run(const wos_siren_net *net,
                       const float *pool_pts, const float *pool_target, const float *pool_scale, int64_t n_pool,
                       const int64_t *idx, int64_t n_iters, int64_t batch,
@@ -870,7 +887,10 @@ int wos_siren_fit_run(const wos_siren_net *net,
  * target, offsets, losses, status, exp_avg or exp_avg_sq, offsets[0] < 0, an iteration without rows
  * (offsets[i+1] <= offsets[i]: a mean over nothing; the iteration is named), a NaN stop_loss,
  * check_every < 0 or check_every > 0 with WOS_ASYNC, wos_adam_step's parameter rules,
- * wos_siren_eval's envelope.  A non-zero workspace_bytes below one tile is WOS_E_CAPACITY. */
+ * wos_siren_eval's envelope.  A non-zero workspace_bytes below one tile is WOS_E_CAPACITY.
+ * WOS_FIT_SCALE_MATRIX: scale is [total*d_out*d_out], iteration i reads it from
+ * scale + offsets[i]*d_out*d_out on, and the step is wos_siren_fit's with the flag; with a NULL scale
+ * it is WOS_E_INVALID, naming scale. */
 int wos_siren_fit_run_batches(const wos_siren_net *net,
                               const float *pts, const float *target, const float *scale,
                               const int64_t *offsets, int64_t n_iters,
@@ -900,7 +920,10 @@ int wos_siren_fit_run_batches(const wos_siren_net *net,
  * n_members outside 1..WOS_MAX_CHANNELS, members that differ in d_in, d_out, hidden,
  * n_hidden_layers or omega, two members sharing a weights or biases pointer or a moment buffer, a
  * NULL entry of nets' arrays, pool_target / target, exp_avg or exp_avg_sq, and every refusal of the
- * single-network entry points. */
+ * single-network entry points.
+ * WOS_FIT_SCALE_MATRIX covers every member that has a scale: each non-NULL entry of pool_scale / scale
+ * is [rows][d_out][d_out]; a NULL entry is still the identity (the unscaled step's bits).  The flag
+ * with a NULL array, or with every entry NULL, is WOS_E_INVALID, naming pool_scale / scale. */
 int wos_siren_fit_run_ensemble(int32_t n_members, const wos_siren_net *nets,
                                const float *pool_pts, const float *const *pool_target,
                                const float *const *pool_scale, int64_t n_pool,

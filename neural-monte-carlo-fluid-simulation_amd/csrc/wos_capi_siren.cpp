@@ -47,6 +47,9 @@ static int stash_cap_check(const std::string& fn, size_t workspace_bytes, size_t
   return WOS_OK;
 }
 
+// floats per row of a fit's scale: d_out, or with WOS_FIT_SCALE_MATRIX d_out * d_out
+static int scale_width(uint32_t flags, int d_out) { return (flags & WOS_FIT_SCALE_MATRIX) ? d_out * d_out : d_out; }
+
 // ---- the network as the launchers take it --------------------------------------------------------
 // wos_siren_net -> wos::SirenNet without layer pointers
 static wos::SirenNet net_view(const wos_siren_net* net) {
@@ -349,6 +352,8 @@ int wos_siren_fit(const wos_siren_net* net, const float* pts, int64_t n, const f
   const int D = net->d_in, DO = net->d_out, H = net->hidden, L = net->n_hidden_layers, NL = L + 2;
   if (!loss) return fail(WOS_E_INVALID, fn + ": null loss");
   if (!target) return fail(WOS_E_INVALID, fn + ": null target");
+  if ((flags & WOS_FIT_SCALE_MATRIX) && !scale)
+    return fail(WOS_E_INVALID, fn + ": null scale with WOS_FIT_SCALE_MATRIX (the flag says how scale is laid out)");
   if ((grad_weights == nullptr) != (grad_biases == nullptr))
     return fail(WOS_E_INVALID, fn + ": exactly one of grad_weights and grad_biases is null (both null: the loss alone)");
   const bool grads = grad_weights != nullptr;
@@ -367,7 +372,8 @@ int wos_siren_fit(const wos_siren_net* net, const float* pts, int64_t n, const f
   WOS_TRY(plan_args(device, workspace_bytes, wos::siren_fit_tile_lds_bytes(D, H), &pa));
   const wos::SirenFitPlan plan = wos::siren_fit_plan(dn, n, pa.stash_cap, pa.resident);
   const DevTmp lay(dn, grads, plan.total(grads));
-  const size_t N = (size_t)n, ns = scale ? N * DO : 0;
+  const int SW = scale_width(flags, DO);
+  const size_t N = (size_t)n, ns = scale ? N * SW : 0;
   const bool dev_ptrs = (flags & WOS_PTRS_DEVICE) != 0;
   return with_tmp(fn, lay.floats + (dev_ptrs ? 0 : (grads ? 2 : 1) * n_par + N * D + N * DO + ns + 1), !dev_ptrs, flags, st,
                   [&](Tmp& t) -> hipError_t {
@@ -387,7 +393,7 @@ int wos_siren_fit(const wos_siren_net* net, const float* pts, int64_t n, const f
     hipError_t e;
     if ((e = enqueue_packs(dn, tmp, lay, grads, st)) != hipSuccess) return e;
     if ((e = wos::launch_siren_fit(dn, tmp, grads ? tmp + lay.o_packT : nullptr, grads ? tmp + lay.o_zero : nullptr, d_pts, n,
-                                   d_target, d_scale, d_loss, grads ? &dg : nullptr, plan, tmp + lay.o_work, st)) != hipSuccess ||
+                                   d_target, d_scale, SW, d_loss, grads ? &dg : nullptr, plan, tmp + lay.o_work, st)) != hipSuccess ||
         dev_ptrs)
       return e;
     t.down(loss, d_loss, 1);
@@ -772,7 +778,11 @@ static int fit_run_pool(const std::string& fn, const FitRun& a, const float* poo
     scaled = scaled || pools.scale[e];
   }
   in.push_back({"idx", idx});
-  const size_t B = (size_t)batch, g_pts = pad64(B * D), g_t = pad64(B * DO), g_s = scaled ? g_t : 0, g_rows = g_t + g_s;
+  if ((a.flags & WOS_FIT_SCALE_MATRIX) && !scaled)
+    return fail(WOS_E_INVALID, fn + ": null pool_scale with WOS_FIT_SCALE_MATRIX (the flag says how pool_scale is laid out)");
+  pools.scale_width = scale_width(a.flags, DO);
+  const size_t B = (size_t)batch, g_pts = pad64(B * D), g_t = pad64(B * DO), g_s = scaled ? pad64(B * pools.scale_width) : 0,
+               g_rows = g_t + g_s;
   int64_t bad = 0;
   const int rc = fit_run_loop(
       fn, a, in,
@@ -791,6 +801,7 @@ static int fit_run_pool(const std::string& fn, const FitRun& a, const float* poo
           r.m.target[e] = b_t + e * g_rows;
           r.m.scale[e] = pools.scale[e] ? b_s + e * g_rows : nullptr;
         }
+        r.m.scale_width = pools.scale_width;
         return wos::launch_fit_run_gather_members(D, DO, E, pool_pts, pools, n_pool, idx + i * batch, batch, b_pts, b_t, b_s,
                                                   g_rows, state, pending, a.stop_loss, a.losses, a.n_iters, a.status, a.st);
       },
@@ -811,6 +822,12 @@ static int fit_run_rows(const std::string& fn, const FitRun& a, const float* pts
   std::vector<NamedPtr> in{{"pts", pts}, {"target", target}};
   for (int e = 0; e < E && target; e++) in.push_back({"target" + of_member(a, e), target[e]});
   in.push_back({"offsets", offsets});
+  const int SW = scale_width(a.flags, DO);
+  if (a.flags & WOS_FIT_SCALE_MATRIX) {
+    bool scaled = false;
+    for (int e = 0; e < E && scale; e++) scaled = scaled || scale[e];
+    if (!scaled) return fail(WOS_E_INVALID, fn + ": null scale with WOS_FIT_SCALE_MATRIX (the flag says how scale is laid out)");
+  }
   return fit_run_loop(
       fn, a, in, [] { return WOS_OK; },
       [&]() -> int {
@@ -831,8 +848,9 @@ static int fit_run_rows(const std::string& fn, const FitRun& a, const float* pts
         r.pts = pts + row * D;
         for (int e = 0; e < E; e++) {
           r.m.target[e] = target[e] + row * DO;
-          r.m.scale[e] = scale && scale[e] ? scale[e] + row * DO : nullptr;
+          r.m.scale[e] = scale && scale[e] ? scale[e] + row * SW : nullptr;
         }
+        r.m.scale_width = SW;
         return pending >= 0 ? wos::launch_fit_run_commit_members(E, state, pending, a.stop_loss, a.losses, n_iters, a.status, a.st)
                             : hipSuccess;
       },

@@ -29,10 +29,13 @@ constexpr int kSirenMaxMembers = 4;
 struct SirenNets {
   SirenNet v[kSirenMaxMembers];
 };
-// the rows of one fit step per member: target (and scale, null: 1) [n][d_out]
+// the rows of one fit step per member: target [n][d_out] and scale (null: 1), [n][scale_width] with
+// scale_width = d_out (a factor per component; 0 stands for it) or d_out * d_out (a row-major matrix
+// per point); one width for every member that has a scale
 struct SirenMemberRows {
   const float* target[kSirenMaxMembers];
   const float* scale[kSirenMaxMembers];
+  int scale_width;
 };
 
 // floats of the fragment-ordered copy of the L hidden weight matrices (0 for L = 0)
@@ -148,11 +151,12 @@ SirenFitPlan siren_fit_plan(const SirenNet& net, int64_t n, size_t stash_cap_byt
 size_t siren_fit_tile_lds_bytes(int d_in, int H);  // dynamic LDS of one tile workgroup
 
 // loss[0] = 1 / (n d_out) sum (scale u - target)^2 (scale null: 1) and, with grads non-null, its
-// gradient (written, not accumulated).  grads null: the loss alone -- packedT, zeros may be null,
+// gradient (written, not accumulated).  scale_width: SirenMemberRows'; with d_out * d_out the
+// residual is S u - target and the seed S^T (2 r) / (n d_out).  grads null: the loss alone -- packedT, zeros may be null,
 // work holds plan.total(false) floats.  n >= 1.  The same n and plan give the same bits.
 hipError_t launch_siren_fit(const SirenNet& net, const float* packed, const float* packedT, const float* zeros,
-                            const float* pts, int64_t n, const float* target, const float* scale, float* loss,
-                            const SirenGrads* grads, const SirenFitPlan& plan, float* work, hipStream_t s);
+                            const float* pts, int64_t n, const float* target, const float* scale, int scale_width,
+                            float* loss, const SirenGrads* grads, const SirenFitPlan& plan, float* work, hipStream_t s);
 // The same step for members 0 .. E - 1 on the same points, each launch covering all of them: member e
 // does exactly what launch_siren_fit does on nets.v[e] and its rows.  packed, packedT and work are
 // member 0's, member e's lie e * member_stride floats further on; `zeros` is shared.  loss: member e's
@@ -199,23 +203,25 @@ hipError_t launch_adam_update(const AdamSegs& segs, float* exp_avg, float* exp_a
 hipError_t launch_adam_update_members(const AdamMembers& m, int E, const AdamScalars& sc, const float* norm,
                                       const int* stop, hipStream_t s);
 // wos_siren_fit_run's state: state[0] the sticky stop flag, state[1] the bits of the iteration's loss.
-// The gather copies rows idx[0 .. batch) of the pool arrays (pool_scale and scale may be null) into
-// pts / target / scale, clamping and counting (status[1]) an index outside [0, n_pool), and commits
+// The gather copies rows idx[0 .. batch) of the pool arrays (pool_scale and scale may be null; their
+// rows are scale_width floats, 0: d_out) into pts / target / scale, clamping and counting (status[1]) an index outside [0, n_pool), and commits
 // iteration prev >= 0 first: unless stopped, losses[prev] = the loss, status[0] = prev + 1, and the
 // flag is set when stop_loss >= 0 and the loss <= stop_loss.  launch_fit_run_commit: the commit alone.
 hipError_t launch_fit_run_gather(int d_in, int d_out, const float* pool_pts, const float* pool_target,
-                                 const float* pool_scale, int64_t n_pool, const int64_t* idx, int64_t batch, float* pts,
-                                 float* target, float* scale, int* state, int64_t prev, float stop_loss, float* losses,
+                                 const float* pool_scale, int scale_width, int64_t n_pool, const int64_t* idx,
+                                 int64_t batch, float* pts, float* target, float* scale, int* state, int64_t prev, float stop_loss, float* losses,
                                  int64_t* status, hipStream_t s);
 hipError_t launch_fit_run_commit(int* state, int64_t iter, float stop_loss, float* losses, int64_t* status,
                                  hipStream_t s);
 // The same for E members that share the pool's points and the index draw.  Member e gathers its own
-// pool_target[e] / pool_scale[e] (a null entry: no scale) into target / scale + e * rows_stride and
+// pool_target[e] / pool_scale[e] (a null entry: no scale; rows of scale_width floats, 0: d_out) into
+// target / scale + e * rows_stride and
 // commits into state + e * kFitStateWords, losses + e * losses_stride and status + 2 e; member 0
 // writes the shared pts.
 struct FitPools {
   const float* target[kSirenMaxMembers];
   const float* scale[kSirenMaxMembers];
+  int scale_width;
 };
 hipError_t launch_fit_run_gather_members(int d_in, int d_out, int E, const float* pool_pts, const FitPools& pools,
                                          int64_t n_pool, const int64_t* idx, int64_t batch, float* pts, float* target,

@@ -6,7 +6,12 @@
 //   r       = fma(scale, u, -target)                      (scale absent: 1, i.e. u - target rounded once)
 //   ub      = (scale (r + r)) (1 / N)                     the seed d loss / d u, 1 / N rounded once on the host
 //   loss    = (sum of r r) / N
-// the gradients are the backward of wos_siren_vjp seeded with g_u = ub and no tangent columns:
+// With a matrix wrap (MATRIX: scale is S [n][d_out][d_out], row-major) the two lines read
+//   r_i     = -target_i, then r_i = fma(S[i][m], u_m, r_i) for m = 0 .. d_out - 1 in order
+//   ub_m    = acc (1 / N) with g_i = r_i + r_i, acc = S[0][m] g_0 (rounded), then
+//             acc = fma(S[i][m], g_i, acc) for i = 1 .. d_out - 1: the seed S^T (2 r) / N
+// and everything from r and ub on is the same code.
+// The gradients are the backward of wos_siren_vjp seeded with g_u = ub and no tangent columns:
 //   output   dWo[i][h] = sum_p ub_i a[h],  dbo = sum_p ub,  da = Wo^T ub
 //   sine     dz = (w c) da
 //   hidden   dW = sum_p dz a_prev^T,  db = sum_p dz,  da_prev = W^T dz
@@ -34,8 +39,9 @@ namespace wos {
 // layout: dWo [d_out][H] | dbo [d_out] | db_0 .. db_L [H] each | dW0 [H][D]; loss_part: [tile].
 // Grid y is the member: its network and rows come from the argument arrays, and its packed copies,
 // stash and partials lie blockIdx.y * member_stride floats past member 0's.  The points and the
-// zeros are shared.
-template <int D, int RT, bool GRADS>
+// zeros are shared.  MATRIX: a member's scale is [n][d_out][d_out]; a member without one takes the
+// unscaled path, as in the other instantiation.
+template <int D, int RT, bool GRADS, bool MATRIX>
 __global__ __launch_bounds__(256) void siren_fit_tile_kernel(const SirenNets nets, const float4* __restrict__ packed,
                                                             const float4* __restrict__ packedT,
                                                             const float* __restrict__ zeros,
@@ -131,20 +137,45 @@ __global__ __launch_bounds__(256) void siren_fit_tile_kernel(const SirenNets net
   {  // output layer, the forward's chain; the thread that holds u_i of a point forms its r and ub
     const float* Wo = net.w[L + 1];
     const float* bo = net.b[L + 1];
-    if (tid < 3 * cols) {
-      const int i = tid >> 5;
-      float r = 0.0f, ub = 0.0f;
-      if (i < DO) {
-        const float* wr = Wo + i * H;
-        float u = 0.0f;
-        for (int h = 0; h < H; h++) u = fmaf(wr[h], Xl[h * cols + j], u);
-        u = u + bo[i];
-        const int64_t p = base + j;
-        if (p < n) {
-          const float sc = scale ? scale[p * DO + i] : 1.0f;
-          r = fmaf(sc, u, -target[p * DO + i]);
-          ub = (sc * (r + r)) * inv_count;
+    const int i = tid >> 5;  // the output row of this thread, for tid < 3 * cols
+    const int64_t p = base + j;
+    const bool live = tid < 3 * cols && i < DO && p < n;
+    float u = 0.0f;
+    if (tid < 3 * cols && i < DO) {
+      const float* wr = Wo + i * H;
+      for (int h = 0; h < H; h++) u = fmaf(wr[h], Xl[h * cols + j], u);
+      u = u + bo[i];
+    }
+    if (MATRIX && scale) {
+      // a point's d_out values meet in LDS: u in the seeds' rows, then r in its own, then the seeds
+      const float* S = scale + (p * DO + i) * DO;  // row i of the point's matrix (read when live)
+      if (tid < 3 * cols) Sl[tid] = u;
+      __syncthreads();
+      float r = 0.0f;
+      if (live) {
+        r = -target[p * DO + i];
+        for (int m = 0; m < DO; m++) r = fmaf(S[m], Sl[m * cols + j], r);
+      }
+      if (tid < 3 * cols) Rl[tid] = r;
+      __syncthreads();  // every u has been read: the seeds' rows are free again
+      float ub = 0.0f;
+      if (live) {  // this thread's output is column i of S now: ub_i = (sum over k of S[k][i] (r_k + r_k)) / N
+        const float* Sc = scale + p * DO * DO + i;
+        const float g0 = Rl[j] + Rl[j];
+        float acc = Sc[0] * g0;
+        for (int k = 1; k < DO; k++) {
+          const float g = Rl[k * cols + j] + Rl[k * cols + j];
+          acc = fmaf(Sc[k * DO], g, acc);
         }
+        ub = acc * inv_count;
+      }
+      if (tid < 3 * cols) Sl[tid] = ub;
+    } else if (tid < 3 * cols) {
+      float r = 0.0f, ub = 0.0f;
+      if (live) {
+        const float sc = scale ? scale[p * DO + i] : 1.0f;
+        r = fmaf(sc, u, -target[p * DO + i]);
+        ub = (sc * (r + r)) * inv_count;
       }
       Rl[tid] = r;
       Sl[tid] = ub;
@@ -320,24 +351,30 @@ struct FitTileArgs {
   int P;
   float* loss_part;
   size_t member_stride;
+  bool matrix;  // rows.scale holds a d_out x d_out matrix per point
 };
 
-template <int D, int RT, bool GRADS>
+template <int D, int RT, bool GRADS, bool MATRIX>
 static hipError_t siren_fit_tile_launch(const SirenNets& nets, int E, const FitTileArgs& a, hipStream_t s) {
   const size_t lds = siren_fit_tile_lds_bytes(D, nets.v[0].H);
   const int64_t grid = (a.n + kSirenTile - 1) / kSirenTile;
-  hipLaunchKernelGGL((siren_fit_tile_kernel<D, RT, GRADS>), dim3((unsigned)grid, E), dim3(256), lds, s, nets,
+  hipLaunchKernelGGL((siren_fit_tile_kernel<D, RT, GRADS, MATRIX>), dim3((unsigned)grid, E), dim3(256), lds, s, nets,
                      (const float4*)a.packed, (const float4*)a.packedT, a.zeros, a.pts, a.n, a.rows, a.inv_count, a.xs,
                      a.ds, a.layer_stride, a.tile_part, a.P, a.loss_part, a.member_stride);
   return hipGetLastError();
 }
 
+template <int D, bool GRADS, bool MATRIX>
+static hipError_t siren_fit_tile_rows(const SirenNets& nets, int E, const FitTileArgs& a, hipStream_t s) {
+  return nets.v[0].H > 128 ? siren_fit_tile_launch<D, 2, GRADS, MATRIX>(nets, E, a, s)
+                           : siren_fit_tile_launch<D, 1, GRADS, MATRIX>(nets, E, a, s);
+}
+
 template <bool GRADS>
 static hipError_t siren_fit_tile_select(const SirenNets& nets, int E, const FitTileArgs& a, hipStream_t s) {
-  const SirenNet& net = nets.v[0];
-  if (net.d_in == 2)
-    return net.H > 128 ? siren_fit_tile_launch<2, 2, GRADS>(nets, E, a, s) : siren_fit_tile_launch<2, 1, GRADS>(nets, E, a, s);
-  return net.H > 128 ? siren_fit_tile_launch<3, 2, GRADS>(nets, E, a, s) : siren_fit_tile_launch<3, 1, GRADS>(nets, E, a, s);
+  if (nets.v[0].d_in == 2)
+    return a.matrix ? siren_fit_tile_rows<2, GRADS, true>(nets, E, a, s) : siren_fit_tile_rows<2, GRADS, false>(nets, E, a, s);
+  return a.matrix ? siren_fit_tile_rows<3, GRADS, true>(nets, E, a, s) : siren_fit_tile_rows<3, GRADS, false>(nets, E, a, s);
 }
 
 hipError_t launch_siren_fit_members(const SirenNets& nets, int E, const float* packed, const float* packedT,
@@ -347,6 +384,10 @@ hipError_t launch_siren_fit_members(const SirenNets& nets, int E, const float* p
   const SirenNet& net = nets.v[0];  // every member has its shape
   const int D = net.d_in, DO = net.d_out, H = net.H, L = net.L, cols = 32;
   if (n <= 0 || plan.tiles < 1 || E < 1 || E > kSirenMaxMembers) return hipErrorInvalidValue;
+  // floats per row of a scale: d_out, or d_out * d_out for a matrix per point (0: d_out).  With
+  // d_out = 1 the two are one layout and one arithmetic, and the diagonal kernel serves both.
+  const int SW = rows.scale_width ? rows.scale_width : DO;
+  if (SW != DO && SW != DO * DO) return hipErrorInvalidValue;
   hipError_t e;
   const int T = plan.tiles, P = (int)siren_vjp_tile_part_floats(net);
   const size_t layer_stride = (size_t)T * H * cols;
@@ -382,8 +423,10 @@ hipError_t launch_siren_fit_members(const SirenNets& nets, int E, const float* p
     a.n = nc;
     for (int m = 0; m < E; m++) {
       a.rows.target[m] = rows.target[m] + base * DO;
-      a.rows.scale[m] = rows.scale[m] ? rows.scale[m] + base * DO : nullptr;
+      a.rows.scale[m] = rows.scale[m] ? rows.scale[m] + base * SW : nullptr;
     }
+    a.rows.scale_width = SW;
+    a.matrix = SW != DO;
     a.inv_count = inv_count;
     a.loss_part = loss_part;
     a.member_stride = member_stride;
@@ -416,13 +459,14 @@ hipError_t launch_siren_fit_members(const SirenNets& nets, int E, const float* p
 }
 
 hipError_t launch_siren_fit(const SirenNet& net, const float* packed, const float* packedT, const float* zeros,
-                            const float* pts, int64_t n, const float* target, const float* scale, float* loss,
-                            const SirenGrads* grads, const SirenFitPlan& plan, float* work, hipStream_t s) {
+                            const float* pts, int64_t n, const float* target, const float* scale, int scale_width,
+                            float* loss, const SirenGrads* grads, const SirenFitPlan& plan, float* work, hipStream_t s) {
   SirenNets nets{};
   nets.v[0] = net;
   SirenMemberRows rows{};
   rows.target[0] = target;
   rows.scale[0] = scale;
+  rows.scale_width = scale_width;
   return launch_siren_fit_members(nets, 1, packed, packedT, zeros, pts, n, rows, loss, 0, grads, 0, plan, work, 0, s);
 }
 

@@ -144,9 +144,10 @@ __global__ __launch_bounds__(256) void fit_run_gather_kernel(const float* __rest
 #pragma unroll
     for (int k = 0; k < D; k++) pts[j * D + k] = pool_pts[r * D + k];
   }
-  for (int i = 0; i < d_out; i++) {
-    target[j * d_out + i] = pool_target[r * d_out + i];
-    if (pool_scale) scale[j * d_out + i] = pool_scale[r * d_out + i];
+  for (int i = 0; i < d_out; i++) target[j * d_out + i] = pool_target[r * d_out + i];
+  if (pool_scale) {
+    const int sw = pools.scale_width ? pools.scale_width : d_out;  // a factor per component, or a matrix per point
+    for (int i = 0; i < sw; i++) scale[j * sw + i] = pool_scale[r * sw + i];
   }
 }
 
@@ -196,12 +197,13 @@ hipError_t launch_fit_run_gather_members(int d_in, int d_out, int E, const float
 }
 
 hipError_t launch_fit_run_gather(int d_in, int d_out, const float* pool_pts, const float* pool_target,
-                                 const float* pool_scale, int64_t n_pool, const int64_t* idx, int64_t batch, float* pts,
-                                 float* target, float* scale, int* state, int64_t prev, float stop_loss, float* losses,
-                                 int64_t* status, hipStream_t s) {
+                                 const float* pool_scale, int scale_width, int64_t n_pool, const int64_t* idx,
+                                 int64_t batch, float* pts, float* target, float* scale, int* state, int64_t prev,
+                                 float stop_loss, float* losses, int64_t* status, hipStream_t s) {
   FitPools pools{};
   pools.target[0] = pool_target;
   pools.scale[0] = pool_scale;
+  pools.scale_width = scale_width;
   return launch_fit_run_gather_members(d_in, d_out, 1, pool_pts, pools, n_pool, idx, batch, pts, target, scale, 0, state, prev,
                                        stop_loss, losses, 0, status, s);
 }

@@ -14,6 +14,7 @@ WOS_OK = 0
 WOS_E_CAPACITY = -4
 WOS_PTRS_DEVICE = 0x1
 WOS_ASYNC = 0x2
+WOS_FIT_SCALE_MATRIX = 0x4  # wos_siren_fit and the fit loops: scale is [rows][d_out][d_out]
 MAX_CHANNELS = 4  # include/wos.h WOS_MAX_CHANNELS
 # include/wos.h WOS_LHS_*: the stratified sampler's shuffles (wos_selftest_lhs_permute, wos_selftest_lhs_plan)
 LHS_REG1, LHS_REG2, LHS_LDS, LHS_PACK_R1, LHS_PACK_R2, LHS_SERIAL = range(6)

@@ -379,9 +379,10 @@ class PressureProjector:
         seeded alike selects the same samples), target = wrap(x, network_prev(x)) - grad_p[idx] with
         the previous network evaluated by wos_amd.siren.eval, and the loss
         mean((wrap(x, network(x)) - target)^2) attached to network's parameters.  wrap(x, u_net) -> u
-        must be diagonal-affine in u_net (query_velocity's karman and taylorgreen branches;
-        wos_amd.siren.diagonal_wrap refuses any other): its scale goes to the kernel, its offset into
-        the target."""
+        must be affine in u_net, wrap(x, N) = S(x) N + c(x) (wos_amd.siren.affine_wrap refuses any other):
+        diagonal, as query_velocity's karman and taylorgreen branches, or mixing the components, as its
+        jpipe branch and slip_wrap.  Its scale -- a factor per component, or a matrix per point -- goes
+        to the kernel, its offset into the target."""
         n = self.samples.shape[0]
         hi = n - 1 if self.dim == 2 else n
         idx = torch.randint(0, hi, (n_samples,), device=self.device, generator=generator)
@@ -391,7 +392,7 @@ class PressureProjector:
             if wrap is None:
                 scale, target = None, u_prev - grad_p[idx]
             else:
-                scale, offset = _diagonal(wrap, x, u_prev.shape[-1])
+                scale, offset = _affine(wrap, x, u_prev.shape[-1])
                 target = wrap(x, u_prev) - grad_p[idx] - offset
         return _siren.fit_loss(network, x, target, scale)
 
@@ -427,7 +428,7 @@ class PressureProjector:
             if wrap is None:
                 scale, target = None, u_prev - grad_p
             else:
-                scale, offset = _diagonal(wrap, self.samples, u_prev.shape[-1])
+                scale, offset = _affine(wrap, self.samples, u_prev.shape[-1])
                 target = wrap(self.samples, u_prev) - grad_p - offset
         losses = []
         for first in range(0, n_iters, per_call):
@@ -482,7 +483,7 @@ class PressureProjector:
                 if wraps[e] is None:
                     scale, target = None, u_prev - grad_p[e]
                 else:
-                    scale, offset = _diagonal(wraps[e], self.samples, u_prev.shape[-1])
+                    scale, offset = _affine(wraps[e], self.samples, u_prev.shape[-1])
                     target = wraps[e](self.samples, u_prev) - grad_p[e] - offset
                 targets.append(target)
                 scales.append(scale)
@@ -495,21 +496,52 @@ class PressureProjector:
         return _ensemble_blocks(who, networks, states, n_iters, per_call, stop, run_block), states
 
 
-_checked_wraps = weakref.WeakSet()
+_wrap_mixes = weakref.WeakKeyDictionary()  # wrap -> whether it mixes the velocity's components
 
 
-def _diagonal(wrap, x, d_out):
-    """siren.diagonal_wrap for the two fit losses.  The probe reads its verdict on the host, so a
-    wrap is probed at its first batch only: whether it mixes components does not depend on the
-    points.  A callable that cannot be weakly referenced is probed every time."""
-    known = wrap in _checked_wraps
-    out = _siren.diagonal_wrap(wrap, x, d_out, check=not known)
-    if not known:
+def _affine(wrap, x, d_out):
+    """(scale, offset) of a wrap for the two fit losses, as wos_amd.siren.fit takes them: scale
+    [..., d_out] for a wrap that is diagonal in the network's output (siren.diagonal_wrap's bits),
+    [..., d_out, d_out] for one that mixes its components (siren.affine_wrap).  The probe and the
+    classification read their verdicts on the host, so a wrap is probed and classified at its first
+    batch only -- whether it is affine, and whether it mixes components, does not depend on the points --
+    and every later batch builds the cached form without a synchronisation.  A callable that cannot be
+    weakly referenced is probed every time."""
+    try:
+        mixes = _wrap_mixes.get(wrap)
+    except TypeError:
+        mixes = None
+    if mixes is None:
+        scale, offset, mixes = _siren.affine_wrap(wrap, x, d_out)
         try:
-            _checked_wraps.add(wrap)
+            _wrap_mixes[wrap] = mixes
         except TypeError:
             pass
-    return out
+        return scale, offset
+    if not mixes:
+        return _siren.diagonal_wrap(wrap, x, d_out, check=False)
+    with torch.no_grad():
+        return _siren._affine_columns(wrap, x.detach(), d_out)
+
+
+def slip_wrap(normal, weight):
+    """The free-slip wrap of a curved wall, wrap(x, u) = u - (1 - weight(x)) (n(x) . u) n(x): the
+    network's normal component is removed and a share weight(x) of it put back, u_t + weight u_n --
+    the reference's jpipe branch around its bend (src/2d/models/base.py:191-222, with the clamped
+    wall distance over eps as the weight).  normal(x) -> [..., d] unit normals, weight(x) -> [...] in
+    [0, 1], both torch callables of the points; where weight is 1 the wrap is the identity, where it
+    is 0 the velocity is tangential.  Affine in u but not diagonal: u = (I - (1 - w) n n^T) N, which
+    siren.affine_wrap classifies as mixing and the fit losses and loops here take as a matrix per
+    point.  Pure torch and differentiable in x, so source_from_network(wrap=) and
+    siren.divergence_with_wrap take it as they are; compose masks around it in a function of your own,
+    e.g. lambda x, u: inlet(x, slip(x, u)) (INTEGRATION.md)."""
+    def wrap(x, u):
+        n = normal(x)
+        w = weight(x)
+        un = (n * u).sum(-1, keepdim=True)
+        return u - (1 - w).unsqueeze(-1) * un * n
+    wrap.__name__ = "slip_wrap"  # the name a refusal gives
+    return wrap
 
 
 def advection_fit_loss(network, network_prev, samples, dt, size, network_tilde=None, wrap=None):
@@ -542,7 +574,7 @@ def _advection_target(network_prev, x, dt, size, network_tilde, wrap):
             target = 2 * target - query(network_tilde, back)
         scale = None
         if wrap is not None:
-            scale, offset = _diagonal(wrap, x, target.shape[-1])
+            scale, offset = _affine(wrap, x, target.shape[-1])
             target = target - offset
     return target, scale
 
@@ -602,9 +634,9 @@ def fit_advection(network, network_prev, dt, size, n_iters, *, n_samples=None, s
     over its own count.  The counts are read on the host: the one synchronisation per block.  An
     iteration left without a point raises ValueError, naming the iteration, before the block is
     enqueued: network and state are then as the previous block left them.
-    wrap(x, u_net) -> u as in advection_fit_loss: pointwise and diagonal-affine in u_net.  A wrap whose
+    wrap(x, u_net) -> u as in advection_fit_loss: pointwise and affine in u_net.  A wrap whose
     value at a point depends on the rest of the batch (the 3D smoke branch's per-call np.random draw,
-    the jpipe branch's norm over the batch) is not covered by the block form: a block hands it the
+    the jpipe branch's norm over the batch as the reference wrote it) is not covered by the block form: a block hands it the
     points of k iterations at once.  iters_per_call=1 hands such a wrap exactly one iteration's points.
     state: a wos_amd.siren.AdamState to continue (None: a fresh one with `lr`).  early_stop as in
     PressureProjector.fit_projection: None, or the loss at or below which the loop stops after that

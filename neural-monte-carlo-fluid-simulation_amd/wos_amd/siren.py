@@ -10,7 +10,8 @@ function over a module's own parameters: PressureProjector.source_from_network(d
 trains through the projection without an autograd graph over the network.  fit() is one iteration
 of the time-stepper's velocity fits -- the regression loss of the value and its weight gradients in
 one value-only pass (wos_siren_fit, csrc/wos_siren_fit.hip) -- fit_loss() the same as an autograd
-scalar, diagonal_wrap() the (scale, offset) form of query_velocity's masks that fit() takes.
+scalar, diagonal_wrap() the (scale, offset) form of query_velocity's masks that fit() takes and
+affine_wrap() the same for a wrap that mixes the velocity's components (a matrix per point).
 adam_step() is the loop's optimiser -- clip_grad_norm_ and torch.optim.Adam.step() in one call on an
 AdamState (wos_adam_step, csrc/wos_siren_train.hip) -- and fit_run() K iterations of gather, fit()
 and adam_step() on a fixed pool from one call (wos_siren_fit_run); fit_run_batches() K iterations of
@@ -127,6 +128,20 @@ def _operand(who, name, a, shape, on_gpu, device, like="the points"):
     if _is_torch(a):
         a = a.detach().cpu().numpy()
     return np.ascontiguousarray(a, dtype=np.float32)
+
+
+def _scale_operand(who, name, a, lead, d_out, on_gpu, device, like="the points"):
+    """A fit's scale as _operand() takes it, in either of its two forms: (array, matrix) with matrix
+    False for lead + (d_out,), a factor per component, and True for lead + (d_out, d_out), a matrix per
+    point (WOS_FIT_SCALE_MATRIX).  None stays (None, False)."""
+    if a is None:
+        return None, False
+    shape = tuple(np.shape(a))
+    diagonal, full = tuple(lead) + (d_out,), tuple(lead) + (d_out, d_out)
+    if shape not in (diagonal, full):
+        raise ValueError(f"siren.{who}: {name} must have shape {diagonal} (a factor per component) or {full} (a matrix "
+                         f"per point), got {shape}")
+    return _operand(who, name, a, shape, on_gpu, device, like), shape == full
 
 
 def eval(net, x, *, value=True, jacobian=False, divergence=False, stream=None):  # noqa: A001 (the module's verb)
@@ -380,7 +395,9 @@ def fit(net, x, target, scale=None, *, grads=True, stream=None, workspace_bytes=
     """One step of the time-stepper's velocity fits without its optimiser (wos_siren_fit,
     csrc/wos_siren_fit.hip): loss = mean((scale * net(x) - target)^2) over the points x [..., d_in]
     and the outputs, target and scale [..., d_out] (scale=None: 1), and its gradient with respect to
-    every weight and bias.  Returns (loss, grad_weights, grad_biases), the two lists in pack() order,
+    every weight and bias.  scale [..., d_out, d_out], a matrix S per point, makes it
+    mean((S @ net(x) - target)^2): the form of a wrap that mixes the network's components
+    (affine_wrap()); a matrix that is diagonal gives the bits of its diagonal as a [..., d_out] scale.  Returns (loss, grad_weights, grad_biases), the two lists in pack() order,
     or the loss alone with grads=False: no backward sweep, no stash, no gradient buffer, the same
     bits in the loss.  A torch CUDA tensor in: torch tensors out (loss a 0-d device tensor), enqueued
     on `stream` as in eval() without a host synchronisation; numpy (or a CPU tensor) in: numpy out
@@ -396,7 +413,8 @@ def fit(net, x, target, scale=None, *, grads=True, stream=None, workspace_bytes=
     if target is None:
         raise ValueError("siren.fit: target is None")
     t = _operand("fit", "target", target, lead + (p.d_out,), on_gpu, dev)
-    sc = None if scale is None else _operand("fit", "scale", scale, lead + (p.d_out,), on_gpu, dev)
+    sc, matrix = _scale_operand("fit", "scale", scale, lead, p.d_out, on_gpu, dev)
+    form = _lib.WOS_FIT_SCALE_MATRIX if matrix else 0
     n = 1
     for k in lead:
         n *= int(k)
@@ -427,7 +445,7 @@ def fit(net, x, target, scale=None, *, grads=True, stream=None, workspace_bytes=
         st, keep = _net_struct(p)
         check(L.wos_siren_fit(C.byref(st), xs.data_ptr(), n, t.data_ptr(), None if sc is None else sc.data_ptr(),
                               loss.data_ptr(), _ptr_array(gw) if grads else None, _ptr_array(gb) if grads else None, ws,
-                              _lib.WOS_PTRS_DEVICE | _lib.WOS_ASYNC, xs.device.index or 0, s), "wos_siren_fit")
+                              _lib.WOS_PTRS_DEVICE | _lib.WOS_ASYNC | form, xs.device.index or 0, s), "wos_siren_fit")
         del keep
         return (loss, gw, gb) if grads else loss
     if _is_torch(x):
@@ -439,7 +457,7 @@ def fit(net, x, target, scale=None, *, grads=True, stream=None, workspace_bytes=
     gw = [np.empty(a.shape, np.float32) for a in host[:nl]] if grads else []
     gb = [np.empty(a.shape, np.float32) for a in host[nl:]] if grads else []
     check(L.wos_siren_fit(C.byref(st), xs.ctypes.data, n, t.ctypes.data, None if sc is None else sc.ctypes.data,
-                          loss.ctypes.data, _ptr_array(gw) if grads else None, _ptr_array(gb) if grads else None, ws, 0,
+                          loss.ctypes.data, _ptr_array(gw) if grads else None, _ptr_array(gb) if grads else None, ws, form,
                           dev, s), "wos_siren_fit")
     del keep
     return (loss[()], gw, gb) if grads else loss[()]
@@ -486,7 +504,8 @@ def _fit_fn():
 
 
 def fit_loss(module, x, target, scale=None):
-    """mean((scale * module(x) - target)^2) as a differentiable scalar of the module's own
+    """mean((scale * module(x) - target)^2) -- scale [..., d_out], or [..., d_out, d_out] and then
+    mean((scale @ module(x) - target)^2), as in fit() -- as a differentiable scalar of the module's own
     parameters, through one autograd node over fit(): the forward computes the loss and every
     parameter gradient in the fused step and keeps the gradients, the backward multiplies them by
     the incoming scalar (once differentiable: a second-order request raises; retain_graph=True works,
@@ -616,7 +635,7 @@ def fit_run(net, state, pool_x, pool_target, pool_scale, idx, *, stop_loss=None,
     """K iterations of gather -> fit() -> adam_step() in one call (wos_siren_fit_run,
     csrc/wos_siren_train.hip), for a fit whose samples, target and scale are fixed for the whole loop
     (the projection fit): iteration i takes the rows idx[i] of pool_x [n_pool, d_in], pool_target and
-    pool_scale [n_pool, d_out] (pool_scale may be None), and equals, bit for bit in the loss, every
+    pool_scale [n_pool, d_out] or [n_pool, d_out, d_out] (fit()'s two forms; it may be None), and equals, bit for bit in the loss, every
     parameter and both moments, x = pool_x[idx[i]], fit(net, x, ...), adam_step(net, grads, state).
     THE NETWORK'S OWN TENSORS ARE UPDATED IN PLACE, as are the state's moments.  CUDA tensors only;
     idx [K, batch] int64, contiguous.  Returns (losses [K] float32, status [2] int64) as device
@@ -641,7 +660,7 @@ def fit_run(net, state, pool_x, pool_target, pool_scale, idx, *, stop_loss=None,
     n_pool = int(pool_x.shape[0])
     xs = pool_x.detach().to(torch.float32).contiguous()
     t = _operand("fit_run", "pool_target", pool_target, (n_pool, p.d_out), True, dev, "pool_x")
-    sc = None if pool_scale is None else _operand("fit_run", "pool_scale", pool_scale, (n_pool, p.d_out), True, dev, "pool_x")
+    sc, matrix = _scale_operand("fit_run", "pool_scale", pool_scale, (n_pool,), p.d_out, True, dev, "pool_x")
     if not _is_torch(idx) or idx.device != dev or idx.dtype != torch.int64 or idx.dim() != 2 or not idx.is_contiguous() \
             or idx.shape[0] < 1 or idx.shape[1] < 1:
         raise ValueError(f"siren.fit_run: idx must be a contiguous int64 tensor [K, batch] on {dev}")
@@ -651,17 +670,18 @@ def fit_run(net, state, pool_x, pool_target, pool_scale, idx, *, stop_loss=None,
         return L.wos_siren_fit_run(*head, xs.data_ptr(), t.data_ptr(), None if sc is None else sc.data_ptr(), n_pool,
                                    idx.data_ptr(), K, batch, *rest)
     return _run_loop("fit_run", "pool is", p, state, dev, [xs, t, idx] + ([] if sc is None else [sc]), K, call, stop_loss,
-                     check_every, stream, workspace_bytes, clamps=True)
+                     check_every, stream, workspace_bytes, clamps=True, matrix=matrix)
 
 
 def _run_loop(who, what, p, state, dev, inputs, K, call, stop_loss, check_every, stream, workspace_bytes, clamps=False,
-              ensemble=False):
+              ensemble=False, matrix=False):
     """What fit_run(), fit_run_batches() and their ensemble forms share once their inputs are device
     tensors on `dev`: the checks of the network, the state and the loop's settings, the outputs, the
     stream discipline, the call -- call(library, head, *the arguments from exp_avg on), head being the
     entry point's leading arguments, (net,) or (n_members, nets) -- and the state's step after it.
     ensemble: p and state are the members' lists, the moments go over as arrays of pointers, losses
-    and status gain a leading member axis, and each state's step advances by its own status[e][0]."""
+    and status gain a leading member axis, and each state's step advances by its own status[e][0].
+    matrix: the scales are matrices per point (WOS_FIT_SCALE_MATRIX)."""
     import torch
     ps, states = (list(p), list(state)) if ensemble else ([p], [state])
     tensors = []
@@ -702,7 +722,7 @@ def _run_loop(who, what, p, state, dev, inputs, K, call, stop_loss, check_every,
         head = (C.byref(structs[0][0]),)
         m, v = moments[0].data_ptr(), moments[1].data_ptr()
     opt = first.params()
-    flags = _lib.WOS_PTRS_DEVICE | (0 if check_every > 0 else _lib.WOS_ASYNC)
+    flags = _lib.WOS_PTRS_DEVICE | (0 if check_every > 0 else _lib.WOS_ASYNC) | (_lib.WOS_FIT_SCALE_MATRIX if matrix else 0)
     rc = call(_lib.load(), head, m, v, first.step, C.byref(opt), -1.0 if stop_loss is None else float(stop_loss), check_every,
               losses.data_ptr(), status.data_ptr(), ws, flags, dev.index or 0, s)
     del structs
@@ -739,7 +759,7 @@ def fit_run_batches(net, state, x, target, scale, counts, *, stop_loss=None, che
     """K iterations of fit() -> adam_step() in one call (wos_siren_fit_run_batches) for a fit whose
     points are new every iteration and of another count every iteration (the advection fit, with the
     samples inside an obstacle dropped): x [total, d_in], target and scale [total, d_out] (scale may be
-    None) hold the rows of all iterations one after the other, counts the K positive row counts, which
+    None, or [total, d_out, d_out]: fit()'s two forms) hold the rows of all iterations one after the other, counts the K positive row counts, which
     sum to total.  Iteration i reads its counts[i] rows in place, as the slice x[o:o + counts[i]] with
     o = sum(counts[:i]), and equals, bit for bit in the loss, every parameter and both moments,
     fit(net, x[o:o + n], target[o:o + n], scale[o:o + n]) and adam_step(net, grads, state): the loss is
@@ -759,14 +779,14 @@ def fit_run_batches(net, state, x, target, scale, counts, *, stop_loss=None, che
     dev = x.device
     xs = x.detach().to(torch.float32).contiguous()
     t = _operand("fit_run_batches", "target", target, (total, p.d_out), True, dev, "x")
-    sc = None if scale is None else _operand("fit_run_batches", "scale", scale, (total, p.d_out), True, dev, "x")
+    sc, matrix = _scale_operand("fit_run_batches", "scale", scale, (total,), p.d_out, True, dev, "x")
     K = len(offsets) - 1
 
     def call(L, head, *rest):
         return L.wos_siren_fit_run_batches(*head, xs.data_ptr(), t.data_ptr(), None if sc is None else sc.data_ptr(),
                                            (C.c_int64 * (K + 1))(*offsets), K, *rest)
     return _run_loop("fit_run_batches", "points are", p, state, dev, [xs, t] + ([] if sc is None else [sc]), K, call,
-                     stop_loss, check_every, stream, workspace_bytes)
+                     stop_loss, check_every, stream, workspace_bytes, matrix=matrix)
 
 
 def _batch_offsets(who, counts, total):
@@ -809,12 +829,30 @@ def _member_operands(who, name, arrays, E, shape, dev, like, optional=False):
             for e, a in enumerate(arrays)]
 
 
+def _member_scales(who, name, arrays, E, lead, d_out, dev, like):
+    """One scale per member (the list, or an entry, may be None), each in either of fit()'s two forms:
+    (scales, matrix).  One call has one form: when any member's is a matrix per point, a member's
+    factors per component become diagonal matrices, which give the same values."""
+    if arrays is None:
+        return [None] * E, False
+    arrays = list(arrays)
+    if len(arrays) != E:
+        raise ValueError(f"siren.{who}: {name} must hold one array per member ({E}), got {len(arrays)}")
+    pairs = [_scale_operand(who, f"{name}[{e}]", a, lead, d_out, True, dev, like) for e, a in enumerate(arrays)]
+    matrix = any(m for _, m in pairs)
+    if not matrix:
+        return [sc for sc, _ in pairs], False
+    import torch
+    return [sc if sc is None or m else torch.diag_embed(sc).contiguous() for sc, m in pairs], True
+
+
 def fit_run_ensemble(nets, states, pool_x, pool_targets, pool_scales, idx, *, stop_loss=None, check_every=0, stream=None,
                      workspace_bytes=None):
     """fit_run() for the E <= 4 members of an ensemble in one device loop (wos_siren_fit_run_ensemble):
     nets and states are lists of E networks of one shape and their AdamStates (the same lr, betas, eps,
     max_grad_norm and step), pool_targets a list of E tensors [n_pool, d_out], pool_scales None or a
-    list whose entries may be None.  The members share pool_x and the index draw idx -- common random
+    list whose entries may be None, [n_pool, d_out] or [n_pool, d_out, d_out] (with both forms in one
+    list, the factors per component go over as diagonal matrices).  The members share pool_x and the index draw idx -- common random
     numbers, as the walks of a multi-channel solve -- and every launch of an iteration covers all of
     them.  Member e's losses, parameters and moments are, bit for bit, fit_run()'s on member e alone.
     EVERY NETWORK IS UPDATED IN PLACE.  Returns (losses [E, K], status [E, 2]) on the device.  The stop
@@ -832,7 +870,7 @@ def fit_run_ensemble(nets, states, pool_x, pool_targets, pool_scales, idx, *, st
     n_pool = int(pool_x.shape[0])
     xs = pool_x.detach().to(torch.float32).contiguous()
     ts = _member_operands("fit_run_ensemble", "pool_targets", pool_targets, E, (n_pool, p.d_out), dev, "pool_x")
-    scs = _member_operands("fit_run_ensemble", "pool_scales", pool_scales, E, (n_pool, p.d_out), dev, "pool_x", optional=True)
+    scs, matrix = _member_scales("fit_run_ensemble", "pool_scales", pool_scales, E, (n_pool,), p.d_out, dev, "pool_x")
     if not _is_torch(idx) or idx.device != dev or idx.dtype != torch.int64 or idx.dim() != 2 or not idx.is_contiguous() \
             or idx.shape[0] < 1 or idx.shape[1] < 1:
         raise ValueError(f"siren.fit_run_ensemble: idx must be a contiguous int64 tensor [K, batch] on {dev}")
@@ -842,7 +880,7 @@ def fit_run_ensemble(nets, states, pool_x, pool_targets, pool_scales, idx, *, st
     def call(L, head, *rest):
         return L.wos_siren_fit_run_ensemble(*head, xs.data_ptr(), t_ptrs, s_ptrs, n_pool, idx.data_ptr(), K, batch, *rest)
     return _run_loop("fit_run_ensemble", "pool is", ps, states, dev, [xs, idx] + ts + [sc for sc in scs if sc is not None], K,
-                     call, stop_loss, check_every, stream, workspace_bytes, clamps=True, ensemble=True)
+                     call, stop_loss, check_every, stream, workspace_bytes, clamps=True, ensemble=True, matrix=matrix)
 
 
 def fit_run_batches_ensemble(nets, states, x, targets, scales, counts, *, stop_loss=None, check_every=0, stream=None,
@@ -850,7 +888,7 @@ def fit_run_batches_ensemble(nets, states, x, targets, scales, counts, *, stop_l
     """fit_run_batches() for the E <= 4 members of an ensemble in one device loop
     (wos_siren_fit_run_batches_ensemble): the members share the points x [total, d_in] and the row
     counts; targets is a list of E tensors [total, d_out], scales None or a list whose entries may be
-    None.  Member e's losses, parameters and moments are, bit for bit, fit_run_batches()'s on member e
+    None, [total, d_out] or [total, d_out, d_out] as in fit_run_ensemble().  Member e's losses, parameters and moments are, bit for bit, fit_run_batches()'s on member e
     alone.  nets, states, the returned (losses [E, K], status [E, 2]) and the per-member stop as in
     fit_run_ensemble()."""
     import torch
@@ -865,7 +903,7 @@ def fit_run_batches_ensemble(nets, states, x, targets, scales, counts, *, stop_l
     dev = x.device
     xs = x.detach().to(torch.float32).contiguous()
     ts = _member_operands("fit_run_batches_ensemble", "targets", targets, E, (total, p.d_out), dev, "x")
-    scs = _member_operands("fit_run_batches_ensemble", "scales", scales, E, (total, p.d_out), dev, "x", optional=True)
+    scs, matrix = _member_scales("fit_run_batches_ensemble", "scales", scales, E, (total,), p.d_out, dev, "x")
     K = len(offsets) - 1
     t_ptrs, s_ptrs = _ptr_array(ts), _opt_ptr_array(scs)
 
@@ -873,7 +911,7 @@ def fit_run_batches_ensemble(nets, states, x, targets, scales, counts, *, stop_l
         return L.wos_siren_fit_run_batches_ensemble(*head, xs.data_ptr(), t_ptrs, s_ptrs, (C.c_int64 * (K + 1))(*offsets), K,
                                                     *rest)
     return _run_loop("fit_run_batches_ensemble", "points are", ps, states, dev, [xs] + ts + [sc for sc in scs if sc is not None],
-                     K, call, stop_loss, check_every, stream, workspace_bytes, ensemble=True)
+                     K, call, stop_loss, check_every, stream, workspace_bytes, ensemble=True, matrix=matrix)
 
 
 def _opt_ptr_array(arrays):
@@ -892,8 +930,8 @@ def diagonal_wrap(wrap, x, d_out, check=True):
     clamp, wall and obstacle weights) and taylorgreen (src/2d/models/base.py:169-189):
     offset = wrap(x, 0), scale = wrap(x, 1) - offset.  check=True probes one random N and raises
     ValueError unless wrap(x, N) equals scale * N + offset to float rounding: a wrap that mixes the
-    output's components (the jpipe branch) is not covered by fit()'s `scale` and keeps the
-    siren.apply + autograd route.  Pure torch, detached, of x's dtype on x's device."""
+    output's components (the jpipe branch) has no diagonal form -- affine_wrap() returns its matrix,
+    which fit() takes as well.  Pure torch, detached, of x's dtype on x's device."""
     import torch
     with torch.no_grad():
         xd = x.detach()
@@ -920,5 +958,68 @@ def diagonal_wrap(wrap, x, d_out, check=True):
                 name = getattr(wrap, "__name__", type(wrap).__name__)
                 raise ValueError(f"siren.diagonal_wrap: wrap '{name}' is not diagonal-affine in the network's output "
                                  f"(it mixes components or is nonlinear: {int(bad.sum())} of {bad.numel()} entries "
-                                 f"differ from scale * N + offset); keep the siren.apply route for it")
+                                 f"differ from scale * N + offset); siren.affine_wrap covers a wrap that mixes components")
     return scale, offset
+
+
+def _affine_columns(wrap, xd, d_out):
+    """(S [..., d_out, d_out], offset [..., d_out]) of a wrap that is affine in the network's output:
+    offset = wrap(x, 0), column m of S = wrap(x, e_m) - offset.  d_out + 1 calls of wrap, nothing read
+    on the host."""
+    import torch
+    shape = tuple(xd.shape[:-1]) + (int(d_out),)
+    zero = torch.zeros(shape, dtype=xd.dtype, device=xd.device)
+    offset = wrap(xd, zero.clone())
+    if tuple(offset.shape) != shape:
+        raise ValueError(f"siren.affine_wrap: wrap returned shape {tuple(offset.shape)} for an output of {shape}")
+    cols = []
+    for m in range(int(d_out)):
+        e = zero.clone()
+        e[..., m] = 1
+        cols.append(wrap(xd, e) - offset)
+    return torch.stack(cols, dim=-1), offset
+
+
+def affine_wrap(wrap, x, d_out, check=True):
+    """(scale, offset, mixes) of a pointwise wrap that is affine in the network's output,
+    wrap(x, N) = S(x) N + offset(x): offset = wrap(x, 0) [..., d_out] and column m of S is
+    wrap(x, e_m) - offset.  mixes is False when every off-diagonal entry of S is exactly zero; scale is
+    then the [..., d_out] diagonal, bit for bit what diagonal_wrap() returns (query_velocity's karman
+    and taylorgreen branches).  Otherwise mixes is True and scale is S [..., d_out, d_out] -- the jpipe
+    branch's free-slip form u = (I - (1 - w) n n^T) N (src/2d/models/base.py:191-222;
+    wos_amd.projection.slip_wrap) -- which fit() and the fit loops take as it is.  check=True probes one
+    random N, diagonal_wrap()'s, and raises ValueError unless wrap(x, N) equals S N + offset to float
+    rounding (diagonal_wrap()'s tolerance, taken per point, not per component: the entries of a
+    projector cancel): a wrap that is nonlinear in N is refused by name.  mixes is read on the host: one
+    synchronisation.  Pure torch, detached, of x's dtype on x's device."""
+    import torch
+    with torch.no_grad():
+        xd = x.detach()
+        S, offset = _affine_columns(wrap, xd, d_out)
+        shape = tuple(offset.shape)
+        if check:
+            key = (shape, xd.dtype, xd.device)
+            probe = _probes.get(key)
+            if probe is None:  # diagonal_wrap's probe, made the same way
+                gen = torch.Generator(device="cpu").manual_seed(20240229)
+                probe = (torch.rand(shape, generator=gen, dtype=torch.float64) * 2.0 + 0.5).to(xd.dtype).to(xd.device)
+                _probes.clear()
+                _probes[key] = probe
+            got = wrap(xd, probe.clone())
+            want = (S * probe.unsqueeze(-2)).sum(-1) + offset
+            eps = torch.finfo(xd.dtype).eps
+            # diagonal_wrap's rule, 8 eps (|S| |N| + |offset| + |wrap(x, N)|), with the three terms summed
+            # over the point's components: an entry such as 1 - n_i^2 of a projector is formed with an
+            # absolute error of eps of the matrix's size, which its own size does not show
+            tol = 8 * eps * (S.abs().sum((-2, -1)) * probe.abs().sum(-1) + offset.abs().sum(-1) + got.abs().sum(-1))
+            bad = (got - want).abs() > tol.unsqueeze(-1)
+            if bool(bad.any()):
+                name = getattr(wrap, "__name__", type(wrap).__name__)
+                raise ValueError(f"siren.affine_wrap: wrap '{name}' is not affine in the network's output (it is "
+                                 f"nonlinear: {int(bad.sum())} of {bad.numel()} entries differ from S N + offset); keep "
+                                 f"the siren.apply route for it")
+        off_diagonal = S * (1 - torch.eye(int(d_out), dtype=S.dtype, device=S.device))
+        mixes = bool((off_diagonal != 0).any())
+        if not mixes:
+            return diagonal_wrap(wrap, xd, d_out, check=False)[0], offset, False
+    return S, offset, True
