@@ -177,6 +177,32 @@ void wos_set_length_hints(int32_t hint_min, int32_t express_min, int32_t express
 int wos_length_hint_stats(int32_t device, int64_t *out);
 int32_t wos_selftest_hint_key(int32_t field);
 
+/* Express layout (additive, ABI 10): which wave starts which walk of the express list.  Scheduling
+ * only, like the hints themselves.  solo_min: the express walks of >= solo_min steps get a wave
+ * each (0: none do; at most 1023).  The walks below go express_per_wave to a wave: stripe 0 in
+ * contiguous blocks of the list, which is sorted longest first, so a wave's walks are of nearly one
+ * length; stripe 1 one walk of each length band, so the wave thins out as its short walks end.
+ * placement 0: a workgroup's express wave is wave (workgroup index mod 4); 1: the first of its
+ * waves on the lowest-numbered SIMD the workgroup occupies.  The express list holds at most as
+ * many walks as one claim per workgroup of the walk kernel's grid covers: the solo tier is cut to
+ * that first, then the list.  A negative argument selects that value's default; values are
+ * clamped, never refused.  wos_get_express_layout: out[0..2] the three values in force.
+ * wos_express_layout_stats: of the last solve on `device`, after waiting for it: out[0] the entries
+ * of its solo tier, out[1] the claims its other express entries went to (both 0 if that solve ran
+ * without hints); with wos_length_hint_stats' out[3] entries, out[1] = ceil((out[3] - out[0]) /
+ * express_per_wave).
+ * wos_selftest_express_slot: host only.  The layout's table for a list of nx entries, for every
+ * solo tier n_solo in 0..nx: a row (n_solo, claim, j, entry) in out (4 words each, at most `rows`
+ * of them written) for every claim in 0..nx+1 and j in 0..express_per_wave+1 that holds an entry;
+ * returns the number of rows there are.
+ * wos_selftest_simd_ids: of one 256-thread workgroup, out[w] the SIMD wave w ran on as the walk
+ * kernel reads it, out[4 + w] the wave's whole hardware id register. */
+void wos_set_express_layout(int32_t solo_min, int32_t stripe, int32_t placement);
+void wos_get_express_layout(int32_t *out);
+int wos_express_layout_stats(int32_t device, int64_t *out);
+int64_t wos_selftest_express_slot(uint32_t nx, uint32_t express_per_wave, int32_t stripe, uint32_t *out, int64_t rows);
+int wos_selftest_simd_ids(int32_t device, uint32_t *out);
+
 typedef struct wos_scene_info {
     int32_t dim, n_prims, n_silhouettes, n_dprims, device;
     float bbox_min[3], bbox_max[3];

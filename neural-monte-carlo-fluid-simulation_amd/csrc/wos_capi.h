@@ -140,9 +140,10 @@ struct HintKey {
   float epsilon_shell = 0, min_star_radius = 0, silhouette_precision = 0, rr_threshold = 0, absorption = 0;
   bool operator==(const HintKey& o) const;
 };
-// the tunables of the length hints (wos_set_length_hints)
+// the tunables of the length hints (wos_set_length_hints) and of the express layout (wos_set_express_layout)
 struct HintTuning {
   int32_t hint_min, express_min, express_per_wave, capacity, priority;
+  int32_t solo_min, stripe, placement;
 };
 extern std::mutex g_hint_mu;
 extern HintTuning g_hint_tuning;

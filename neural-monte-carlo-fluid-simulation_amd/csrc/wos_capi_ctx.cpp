@@ -22,7 +22,9 @@ std::atomic<int64_t> g_max_batch_tasks{kDefaultBatchTasks};
 
 // Length hints (Length hints): walks of >= hint_min steps are listed, those of >=
 // express_min steps start first in the next solve, express_per_wave to a wave at issue priority `priority`.
-constexpr HintTuning kDefaultHintTuning = {24, 40, 4, (int32_t)wos::kHintListMax, 0};
+// Express layout: walks of >= solo_min steps a wave each (0: none), the others striped or in blocks, the
+// express wave rotating (0) or pinned to the workgroup's lowest SIMD (1).
+constexpr HintTuning kDefaultHintTuning = {24, 32, 16, (int32_t)wos::kHintListMax, 0, 64, 0, 0};
 std::mutex g_hint_mu;
 HintTuning g_hint_tuning = kDefaultHintTuning;
 
@@ -403,6 +405,38 @@ void wos_set_length_hints(int32_t hint_min, int32_t express_min, int32_t express
   t.priority = priority < 0 ? d.priority : std::min(priority, 3);
 }
 
+void wos_set_express_layout(int32_t solo_min, int32_t stripe, int32_t placement) {
+  std::lock_guard<std::mutex> lk(g_hint_mu);
+  const HintTuning& d = kDefaultHintTuning;
+  HintTuning& t = g_hint_tuning;
+  t.solo_min = solo_min < 0 ? d.solo_min : std::min(solo_min, wos::kHintBins - 1);
+  t.stripe = stripe < 0 ? d.stripe : std::min(stripe, 1);
+  t.placement = placement < 0 ? d.placement : std::min(placement, 1);
+}
+
+void wos_get_express_layout(int32_t* out) {
+  if (!out) return;
+  std::lock_guard<std::mutex> lk(g_hint_mu);
+  out[0] = g_hint_tuning.solo_min;
+  out[1] = g_hint_tuning.stripe;
+  out[2] = g_hint_tuning.placement;
+}
+
+int64_t wos_selftest_express_slot(uint32_t nx, uint32_t express_per_wave, int32_t stripe, uint32_t* out, int64_t rows) {
+  int64_t r = 0;
+  for (uint32_t n_solo = 0; n_solo <= nx; n_solo++)
+    for (uint32_t c = 0; c < nx + 2u; c++)
+      for (uint32_t j = 0; j < express_per_wave + 2u; j++) {
+        const uint32_t e = wos::express_slot(c, j, nx, n_solo, express_per_wave, stripe != 0 ? 1u : 0u);
+        if (e == wos::kExpressNone) continue;
+        if (out && r < rows) {
+          out[4 * r] = n_solo; out[4 * r + 1] = c; out[4 * r + 2] = j; out[4 * r + 3] = e;
+        }
+        r++;
+      }
+  return r;
+}
+
 int32_t wos_selftest_hint_key(int32_t field) {
   HintKey a, b;
   int k = 0;
@@ -435,6 +469,22 @@ int wos_length_hint_stats(int32_t device, int64_t* out) {
   out[1] = h[wos::H_NLIST] > h[wos::H_CAP] ? h[wos::H_NLIST] - h[wos::H_CAP] : 0;
   out[2] = std::min(h[wos::H_NLIST], h[wos::H_CAP]);
   out[3] = h[wos::H_NEXPRESS];
+  return WOS_OK;
+}
+
+int wos_express_layout_stats(int32_t device, int64_t* out) {
+  if (!out) return fail(WOS_E_INVALID, "wos_express_layout_stats: null output");
+  for (int k = 0; k < 2; k++) out[k] = 0;
+  if (device < 0 || device >= kMaxDevices) return fail(WOS_E_INVALID, "wos_express_layout_stats: no such device");
+  DevCtx& c = g_ctx[device];
+  std::lock_guard<std::mutex> lk(c.mu);
+  if (!c.ready || !c.hint_last || !c.d_hint_list) return WOS_OK;
+  HIP_TRY(hipSetDevice(device));
+  if (c.inflight) HIP_TRY(hipEventSynchronize(c.done));
+  uint32_t h[wos::H_WORDS];
+  HIP_TRY(hipMemcpy(h, c.d_counters + wos::kNumCounterSlots, sizeof(h), hipMemcpyDeviceToHost));
+  out[0] = h[wos::H_NSOLO];
+  out[1] = h[wos::H_XG];
   return WOS_OK;
 }
 

@@ -26,6 +26,20 @@ int wos_selftest_math(int32_t which, const double* x, double* out, int64_t n, in
   return WOS_OK;
 }
 
+int wos_selftest_simd_ids(int32_t device, uint32_t* out) {
+  if (!out) return fail(WOS_E_INVALID, "wos_selftest_simd_ids: null output");
+  constexpr int kWords = 2 * 4;  // (wos_selftest.hip: two words per wave of a 256-thread block)
+  HIP_TRY(hipSetDevice(device));
+  uint32_t* d = nullptr;
+  HIP_TRY(hipMalloc((void**)&d, kWords * sizeof(uint32_t)));
+  hipError_t e = wos::launch_simd_id_selftest(d, nullptr);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = hipMemcpy(out, d, kWords * sizeof(uint32_t), hipMemcpyDeviceToHost);
+  hipFree(d);
+  if (e != hipSuccess) return fail(WOS_E_DEVICE, std::string("wos_selftest_simd_ids: ") + hipGetErrorString(e));
+  return WOS_OK;
+}
+
 int wos_selftest_lhs(uint64_t key, const int64_t* gidx, int64_t n, int32_t n_pairs, int32_t dim, int32_t jump_lds,
                      float* out, int32_t device) {
   if (!gidx || !out || n < 0 || n > (1 << 20) || n_pairs < 1 || n_pairs > (1 << 14) || (dim != 2 && dim != 3))

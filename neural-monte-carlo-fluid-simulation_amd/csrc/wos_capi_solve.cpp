@@ -311,6 +311,7 @@ int solve_locked(wos_scene* s, const wos_solver_params* prm, const float* pts, i
     // the list belongs to nobody until this solve's walk kernel, which refills it, is enqueued
     c.hint_key_valid = false;
     hint_word = wos::kHintCollect | (hint_use ? wos::kHintUse : 0u) | ((uint32_t)ht.priority << wos::kHintPrioShift) |
+                (ht.stripe ? wos::kHintStripe : 0u) | (ht.placement ? wos::kHintPinned : 0u) |
                 ((uint32_t)ht.hint_min << wos::kHintMinShift);
   }
   if (n > 0) c.hint_last = hinted;
@@ -332,11 +333,11 @@ int solve_locked(wos_scene* s, const wos_solver_params* prm, const float* pts, i
     tk.hint = hint_word;
     WOS_TRY(batch_head(c, dim, plan, k, d_pts + b0 * dim, nb, tk, ev[0], st,
                        hinted ? (unsigned long long*)(hc + wos::H_CK_CUR) : nullptr));
-    // at most one express wave's worth per workgroup of the walk grid: where more walks than that are
-    // "long", they are the bulk, and sparse waves would only cost throughput
+    // at most one claim per workgroup of the walk grid: where more walks than that are "long", they are
+    // the bulk, and sparse waves would only cost throughput
     if (hinted)
       HIP_TRY(wos::launch_hint_build(hc, hint_use ? 1 : 0, (uint32_t)ht.express_min, (uint32_t)ht.express_per_wave,
-                                     (uint32_t)ht.capacity, (uint32_t)walk_grid * (uint32_t)ht.express_per_wave, tk,
+                                     (uint32_t)ht.capacity, (uint32_t)walk_grid, (uint32_t)ht.solo_min, tk,
                                      st));
     HIP_TRY(wos::launch_first_balls(plan.kv, plan.dfb, dp, d_pts + b0 * dim, nb, bbase, index_stride, tk,
                                     c.d_counters, q_points, plan.grid_fb, plan.shmem_fb_run, plan.lhs_floats, st));

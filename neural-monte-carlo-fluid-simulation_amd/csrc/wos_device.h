@@ -56,10 +56,18 @@ enum { D_ITERS = 0, D_LANES, D_STAR, D_RAY, D_SAMPLE, D_STEP, D_LOOP, D_RAYOVF, 
        D_FB_UPD, D_FB_SMP, D_FB_MA, D_FB_MB, D_FB_ST, D_FB_ITSUM, D_FB_ITMAX,
 #if WOS_DIAG
        D_E_ITERS, D_E_LANES, D_E_LOOP,  // iterations of waves that hold express walks (length hints)
+       // ... split six ways, slot 2 * live + dry: live walks 1 (0), 2-4 (1), more (2); dry: a wave of the workgroup
+       // has found the bulk queue empty (D_QDRY, a flag in the workgroup's s_diag)
+       D_EB_ITERS, D_EB_ITERS_LAST = D_EB_ITERS + 5, D_EB_LOOP, D_EB_LOOP_LAST = D_EB_LOOP + 5, D_QDRY,
 #endif
        D_NUM };  // X: iterations after the wave's task queue ran dry
 // slots holding maxima (folded with atomicMax)
-__host__ __device__ constexpr bool diag_is_max(int k) { return k == D_FB_MAX || k == D_WMAXLEN || k == D_WAVEMAX; }
+__host__ __device__ constexpr bool diag_is_max(int k) {
+#if WOS_DIAG
+  if (k == D_QDRY) return true;
+#endif
+  return k == D_FB_MAX || k == D_WMAXLEN || k == D_WAVEMAX;
+}
 static __device__ unsigned long long g_diag[D_NUM];
 #if WOS_DIAG
 static __shared__ unsigned long long s_diag[D_NUM];
@@ -3862,6 +3870,13 @@ __device__ __forceinline__ void wave_priority(int level) {
 __device__ __forceinline__ void wave_priority_set(int level) {
   if (level <= 0) __builtin_amdgcn_s_setprio(0);
   else wave_priority(level);
+}
+
+// the SIMD of the compute unit the calling wave runs on: HW_REG_HW_ID (register 4), field SIMD_ID, bits 4-5
+// (wos_selftest_simd_ids reports it beside the whole register, to confirm the field on the device)
+constexpr int kHwRegHwId = 4, kHwIdSimdShift = 4, kHwIdSimdBits = 2;
+__device__ __forceinline__ uint32_t hw_simd_id() {
+  return __builtin_amdgcn_s_getreg(kHwRegHwId | (kHwIdSimdShift << 6) | ((kHwIdSimdBits - 1) << 11));
 }
 
 // ---- kernel 2: walks ---------------------------------------------------------

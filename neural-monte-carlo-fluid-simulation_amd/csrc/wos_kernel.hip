@@ -171,11 +171,20 @@ hipError_t launch_point_setup(int dim, const DevScene& sc, const DevParams& prm,
 // task bitmap and its point flagged in pstate (after point setup rewrote it).  The bits of the
 // previous express list are cleared first, so the bitmap is never swept.  Then the list, the claim
 // counters and the checksum are reset for the walk kernel that follows.
-constexpr int kHintBins = 1024;
+// The layout (express_slot, wos_scene.h): the entries of >= solo_min steps (0: none) are the solo tier,
+// a prefix of the histogram; at most max_claims claims in all, so that one round of the walk grid's
+// express waves hands out the whole list: the solo tier is cut to max_claims entries, then the list to
+// what the claims left over hold.
+// The kernel sits between point setup and the first balls, and its time is global-memory round trips:
+// a thread reads its entries kHintBatch at a time (the loads of a batch are independent, then those of
+// their points' states), and keeps which of them go express as a bit each, so the second pass reads
+// the list alone.
+constexpr int kHintBatch = 8;
+static_assert((uint64_t)kHintListMax <= 64ull * kHintBins, "a thread's entries: a bit each of a 64-bit mask");
 __global__ __launch_bounds__(kHintBins) void wos_hint_build_kernel(uint32_t* __restrict__ hc, int use,
                                                                    uint32_t express_min, uint32_t epw, uint32_t cap,
-                                                                   uint32_t max_express, const DevTasks tk) {
-  __shared__ uint32_t s_bin[kHintBins], s_wave[kHintBins / kWave];
+                                                                   uint32_t max_claims, uint32_t solo_min, const DevTasks tk) {
+  __shared__ uint32_t s_bin[kHintBins], s_wave[kHintBins / kWave], s_nsolo;
   const int tid = threadIdx.x;
   uint32_t* const express = *reinterpret_cast<uint32_t* const*>(hc + H_EXPRESS);
   uint32_t* const bits = *reinterpret_cast<uint32_t* const*>(hc + H_BITS);
@@ -187,21 +196,38 @@ __global__ __launch_bounds__(kHintBins) void wos_hint_build_kernel(uint32_t* __r
   // (a list that overflowed is a sample of walks that are the bulk, not the tail: no express list)
   const bool ok = use != 0 && ck_cur == ck_list && hc[H_NLIST] <= hc[H_CAP];
   const uint32_t T = (uint32_t)tk.T, wpp = (uint32_t)tk.wpp;
-  for (uint32_t i = tid; i < n_old; i += kHintBins) {
-    const uint32_t t = express[i];
-    atomicAnd(&bits[t >> 5], ~(1u << (t & 31u)));
+  for (uint32_t i0 = tid; i0 < n_old; i0 += kHintBatch * kHintBins) {
+    uint32_t t[kHintBatch];
+    for (int k = 0; k < kHintBatch; k++) t[k] = i0 + k * kHintBins < n_old ? express[i0 + k * kHintBins] : kExpressNone;
+    for (int k = 0; k < kHintBatch; k++)
+      if (t[k] != kExpressNone) atomicAnd(&bits[t[k] >> 5], ~(1u << (t[k] & 31u)));
   }
   s_bin[tid] = 0u;
+  if (tid == 0) s_nsolo = 0u;
   __syncthreads();
-  // an entry goes express: long enough, a task of this batch, its point estimated; bin 0: the longest
-  const auto bin_of = [&](const uint2 e) -> int {
-    if (e.y < express_min || e.x >= T || !(tk.pstate[e.x / wpp] & kPtEstimate)) return -1;
-    return kHintBins - 1 - (int)(e.y < (uint32_t)kHintBins - 1u ? e.y : (uint32_t)kHintBins - 1u);
+  // bin 0: the longest
+  const auto bin_of = [](const uint32_t steps) -> uint32_t {
+    return (uint32_t)kHintBins - 1u - (steps < (uint32_t)kHintBins - 1u ? steps : (uint32_t)kHintBins - 1u);
   };
+  // an entry goes express: long enough, a task of this batch, its point estimated.  Bit k of `go`:
+  // the thread's entry tid + k kHintBins does.
+  uint64_t go = 0ull;
   if (ok)
-    for (uint32_t i = tid; i < n; i += kHintBins) {
-      const int b = bin_of(list[i]);
-      if (b >= 0) atomicAdd(&s_bin[b], 1u);
+    for (uint32_t k0 = 0; (uint32_t)tid + k0 * kHintBins < n; k0 += kHintBatch) {
+      uint2 e[kHintBatch];
+      bool cand[kHintBatch];
+      int32_t ps[kHintBatch];
+      for (int k = 0; k < kHintBatch; k++) {
+        const uint32_t i = (uint32_t)tid + (k0 + k) * kHintBins;
+        e[k] = i < n ? list[i] : make_uint2(0u, 0u);
+        cand[k] = i < n && e[k].y >= express_min && e[k].x < T;
+      }
+      for (int k = 0; k < kHintBatch; k++) ps[k] = cand[k] ? tk.pstate[e[k].x / wpp] : 0;
+      for (int k = 0; k < kHintBatch; k++)
+        if (ps[k] & kPtEstimate) {
+          go |= 1ull << (k0 + k);
+          atomicAdd(&s_bin[bin_of(e[k].y)], 1u);
+        }
     }
   __syncthreads();
   // exclusive scan of the bins: inside each wave by shuffles, then the waves' totals
@@ -220,23 +246,34 @@ __global__ __launch_bounds__(kHintBins) void wos_hint_build_kernel(uint32_t* __r
     total += s_wave[w];
   }
   s_bin[tid] = before + inc - mine;  // the bin's fill cursor
+  // the solo tier: the bins of >= solo_min steps (solo_min < kHintBins: wos_set_express_layout)
+  if (solo_min > 0u && (uint32_t)tid == bin_of(solo_min)) s_nsolo = before + inc;
   __syncthreads();
-  if (ok)
-    for (uint32_t i = tid; i < n; i += kHintBins) {
-      const uint2 e = list[i];
-      const int b = bin_of(e);
-      if (b < 0) continue;
-      // (the longest max_express of them: express waves are for the few walks that outlast the bulk)
-      const uint32_t pos = atomicAdd(&s_bin[b], 1u);
-      if (pos >= max_express) continue;
-      express[pos] = e.x;
-      atomicOr(&bits[e.x >> 5], 1u << (e.x & 31u));
-      atomicOr(&tk.pstate[e.x / wpp], kPtExpress);
+  // (the longest of them: express waves are for the few walks that outlast the bulk)
+  const uint32_t n_solo = s_nsolo < max_claims ? s_nsolo : max_claims;
+  const uint64_t room = (uint64_t)n_solo + (uint64_t)(max_claims - n_solo) * epw;
+  const uint32_t nx = ok ? ((uint64_t)total < room ? total : (uint32_t)room) : 0u;
+  for (uint32_t k0 = 0; k0 < 64u && (go >> k0) != 0ull; k0 += kHintBatch) {
+    uint2 e[kHintBatch];
+    for (int k = 0; k < kHintBatch; k++)
+      e[k] = ((go >> (k0 + k)) & 1ull) ? list[(uint32_t)tid + (k0 + k) * kHintBins] : make_uint2(0u, 0u);
+    for (int k = 0; k < kHintBatch; k++) {
+      if (!((go >> (k0 + k)) & 1ull)) continue;
+      const uint32_t pos = atomicAdd(&s_bin[bin_of(e[k].y)], 1u);
+      if (pos >= nx) continue;
+      express[pos] = e[k].x;
+      atomicOr(&bits[e[k].x >> 5], 1u << (e[k].x & 31u));
+      atomicOr(&tk.pstate[e[k].x / wpp], kPtExpress);
     }
-  __syncthreads();
+  }
+  // (no barrier before these stores: every thread took what it reads of hc -- H_NLIST, H_CAP, H_NEXPRESS, the
+  // checksums and the list pointers -- into registers before the first __syncthreads, and nothing above re-reads hc)
   if (tid == 0) {
-    hc[H_NEXPRESS] = ok ? (total < max_express ? total : max_express) : 0u;
+    const uint32_t ns = n_solo < nx ? n_solo : nx;
+    hc[H_NEXPRESS] = nx;
     hc[H_EPW] = epw;
+    hc[H_NSOLO] = ns;
+    hc[H_XG] = express_claims_below(nx, ns, epw);
     hc[H_CAP] = cap;
     hc[H_CLAIMED] = 0u;
     hc[H_NLIST] = 0u;
@@ -247,9 +284,9 @@ __global__ __launch_bounds__(kHintBins) void wos_hint_build_kernel(uint32_t* __r
 }
 
 hipError_t launch_hint_build(uint32_t* hc, int use, uint32_t express_min, uint32_t express_per_wave, uint32_t cap,
-                             uint32_t max_express, const DevTasks& tk, hipStream_t s) {
+                             uint32_t max_claims, uint32_t solo_min, const DevTasks& tk, hipStream_t s) {
   hipLaunchKernelGGL(wos_hint_build_kernel, dim3(1), dim3(kHintBins), 0, s, hc, use, express_min, express_per_wave, cap,
-                     max_express, tk);
+                     max_claims, solo_min, tk);
   return hipGetLastError();
 }
 
@@ -385,6 +422,10 @@ void diag_print(const char* tag, const void* sym) {
           (double)d[D_XLANES] / (d[D_XITERS] ? d[D_XITERS] : 1), 100.0 * d[D_XLOOP] / (d[D_LOOP] ? d[D_LOOP] : 1));
   fprintf(stderr, "[diag %s] express waves: %llu iterations, lanes/iter %.2f, cycles/iter (loop) %.0f\n", tag, d[D_E_ITERS],
           (double)d[D_E_LANES] / (d[D_E_ITERS] ? d[D_E_ITERS] : 1), (double)d[D_E_LOOP] / (d[D_E_ITERS] ? d[D_E_ITERS] : 1));
+  static const char* const kLive[3] = {"1 live walk", "2-4 live walks", ">4 live walks"};
+  for (int b = 0; b < 6; b++)
+    fprintf(stderr, "[diag %s] express waves, %s, bulk queue %s: %llu iterations, cycles/iter (loop) %.0f\n", tag, kLive[b / 2],
+            (b & 1) ? "dry" : "dealing", d[D_EB_ITERS + b], (double)d[D_EB_LOOP + b] / (d[D_EB_ITERS + b] ? d[D_EB_ITERS + b] : 1));
   const double li = (double)(d[D_L_ITERS] ? d[D_L_ITERS] : 1);
   fprintf(stderr, "[diag %s] <=2 live lanes: %llu iterations, cycles/iter: loop %.0f step %.0f star %.0f (cell %.0f prefix %.0f "
                   "window %.0f final %.0f) mid %.0f ray %.0f end %.0f sample %.0f tail %.0f\n",

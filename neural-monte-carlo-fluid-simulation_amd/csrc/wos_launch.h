@@ -29,11 +29,15 @@ hipError_t launch_first_balls(const KernelVariant& v, const DevScene& sc, const 
 hipError_t launch_point_setup(int dim, const DevScene& sc, const DevParams& prm, const float* pts, int64_t n,
                               const DevTasks& tk, hipStream_t s, unsigned long long* cksum = nullptr);
 // length hints: the express list of the walk kernel about to run from the list its predecessor left
-// (use 0, or another point checksum: none; at most max_express entries, the longest), then the list
-// and the claim counters reset.  hc: the control block; after launch_point_setup(..., cksum = hc +
-// H_CK_CUR), before launch_walks.
+// (use 0, or another point checksum: none; the longest, as many as max_claims claims of the express
+// layout hold: walks of >= solo_min steps a claim each, express_per_wave to a claim below), then the
+// list and the claim counters reset.  hc: the control block; after launch_point_setup(..., cksum =
+// hc + H_CK_CUR), before launch_walks.
 hipError_t launch_hint_build(uint32_t* hc, int use, uint32_t express_min, uint32_t express_per_wave, uint32_t cap,
-                             uint32_t max_express, const DevTasks& tk, hipStream_t s);
+                             uint32_t max_claims, uint32_t solo_min, const DevTasks& tk, hipStream_t s);
+// the SIMD of each wave of one kBlock-thread block: out[w] hw_simd_id(), out[kBlock / kWave + w] the whole
+// hardware id register (wos_selftest.hip)
+hipError_t launch_simd_id_selftest(uint32_t* out, hipStream_t s);
 // geometry queries (wos_query.hip; include/wos.h wos_scene_query): per point the distance, signed
 // distance and closest point [n][dim] of boundary `which` (0 Neumann, 1 Dirichlet) and the state
 // word for `mask` (pstate's bits 0-2, bit 3 inside); every output may be null

@@ -208,8 +208,9 @@ struct DevTasks {
 // next solve of the same walks starts those of >= express_min steps first, longest first, in
 // waves that hold nothing else ("express").  A scheduling hint only: results do not depend on it.
 // DevTasks::hint: bit 0 collect, bit 1 use the express list, bits 2-3 the express waves' issue
-// priority, bits 8-23 hint_min.
-constexpr uint32_t kHintCollect = 1u, kHintUse = 2u;
+// priority, bit 4 striped claims, bit 5 pinned placement (express layout, below), bits 8-23 hint_min.
+constexpr uint32_t kHintCollect = 1u, kHintUse = 2u, kHintStripe = 16u, kHintPinned = 32u;
+constexpr int kHintBins = 1024;  // the build kernel's histogram by steps (its block size): solo_min < kHintBins
 constexpr int kHintPrioShift = 2, kHintMinShift = 8;
 constexpr uint32_t kHintMinMask = 0xFFFFu;
 constexpr int32_t kPtExpress = 1 << 16;    // pstate: some walk of the point is express-owned
@@ -220,11 +221,13 @@ constexpr int kHintBlockWord = kMaxTaskQueues * (int)kTaskQueueStride;
 // `counters`).  The two atomics of the walk kernel sit on lines of their own.
 enum {
   H_NLIST = 0,      // walks offered to the list by the running walk kernel (may exceed H_CAP)
-  H_XCLAIM = 16,    // express entries handed out
+  H_XCLAIM = 16,    // claims handed out (express_slot, below)
   H_NEXPRESS = 32,  // entries of the express list
-  H_EPW,            // express walks a wave claims at once
+  H_EPW,            // express walks a claim below the solo tier holds
   H_CAP,            // capacity of the list in use (<= kHintListMax)
   H_CLAIMED,        // express walks started by the last hinted walk kernel
+  H_NSOLO,          // entries of the solo tier: the first H_NSOLO of the list, a claim each
+  H_XG,             // claims below the solo tier: ceil((H_NEXPRESS - H_NSOLO) / H_EPW)
   H_CK_CUR = 48,    // u64: checksum of the points of the running solve (point setup)
   H_CK_LIST = 50,   // u64: ... of the solve that filled the list
   H_LIST = 52,      // u64: uint2* (task, steps)
@@ -232,6 +235,36 @@ enum {
   H_BITS = 56,      // u64: uint32_t* one bit per task: express-owned
   H_WORDS = 64
 };
+
+// ---- express layout: which entries of the express list (longest first) a claim holds ----
+// The first n_solo entries, the longest walks, are a claim each: a wave of their own.  The m = nx -
+// n_solo entries below go to G = ceil(m / epw) claims of up to epw: striped, claim n_solo + i holds
+// the entries n_solo + i + j G (one of each length band, so the wave thins out as the short ones
+// end); unstriped, the contiguous block n_solo + i epw + j.  Entry j of claim c, or kExpressNone;
+// a claim's entries are j = 0, 1, ... without a gap, and every entry of [0, nx) belongs to exactly
+// one (claim, j) (tests/test_express_layout_cpu.py walks the whole table).
+constexpr uint32_t kExpressNone = 0xFFFFFFFFu;
+#ifdef __HIP__
+#define WOS_HOST_DEVICE __host__ __device__
+#else  // (a host compiler reads this header too: wos_variant.h)
+#define WOS_HOST_DEVICE
+#endif
+WOS_HOST_DEVICE inline uint32_t express_claims_below(uint32_t nx, uint32_t n_solo, uint32_t epw) {
+  return epw > 0u && nx > n_solo ? (nx - n_solo + epw - 1u) / epw : 0u;
+}
+// (G: express_claims_below(nx, n_solo, epw), which the build kernel leaves in H_XG)
+WOS_HOST_DEVICE inline uint32_t express_slot_g(uint32_t c, uint32_t j, uint32_t nx, uint32_t n_solo, uint32_t epw,
+                                                   uint32_t stripe, uint32_t G) {
+  if (c < n_solo) return j == 0u && c < nx ? c : kExpressNone;
+  const uint32_t i = c - n_solo;
+  if (i >= G || j >= epw) return kExpressNone;
+  const uint32_t e = n_solo + (stripe ? i + j * G : i * epw + j);  // (nx <= kHintListMax, epw <= 64: no overflow)
+  return e < nx ? e : kExpressNone;
+}
+WOS_HOST_DEVICE inline uint32_t express_slot(uint32_t c, uint32_t j, uint32_t nx, uint32_t n_solo, uint32_t epw,
+                                                 uint32_t stripe) {
+  return express_slot_g(c, j, nx, n_solo, epw, stripe, express_claims_below(nx, n_solo, epw));
+}
 
 // What a recording pass (wos_tape.hip) keeps of a batch's walks instead of their source-dependent
 // values, so that wos_tape_replay_kernel can redo totalSource and the walk total for any source

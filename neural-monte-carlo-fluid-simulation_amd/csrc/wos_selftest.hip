@@ -127,6 +127,22 @@ hipError_t launch_lhs_selftest(int dim, const DevParams& prm, const long long* g
   return hipGetLastError();
 }
 
+// ---- the SIMD a wave runs on (hw_simd_id, the walk kernel's pinned express placement) ----
+// One kBlock-thread block: out[w] the field as the walk kernel reads it, out[kBlock / kWave + w] the whole
+// hardware id register, so the field's position can be confirmed on the device.
+__global__ __launch_bounds__(kBlock) void wos_simd_id_selftest_kernel(uint32_t* __restrict__ out) {
+  const int w = threadIdx.x / kWave;
+  if ((threadIdx.x & (kWave - 1)) == 0) {
+    out[w] = hw_simd_id();
+    out[kBlock / kWave + w] = __builtin_amdgcn_s_getreg(kHwRegHwId | (31 << 11));
+  }
+}
+
+hipError_t launch_simd_id_selftest(uint32_t* out, hipStream_t s) {
+  hipLaunchKernelGGL(wos_simd_id_selftest_kernel, dim3(1), dim3(kBlock), 0, s, out);
+  return hipGetLastError();
+}
+
 int lhs_permute_selftest_slots(int impl) { return impl == WOS_LHS_PACK_R1 ? 2 : 1; }
 
 int lhs_permute_selftest_max_strata(int impl) {

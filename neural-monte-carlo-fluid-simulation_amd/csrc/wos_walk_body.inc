@@ -31,6 +31,17 @@
 #if WOS_DIAG
   if (threadIdx.x < D_NUM) s_diag[threadIdx.x] = 0u;
 #endif
+  // HINT, pinned placement: every wave tells every wave its SIMD, in the first words of each one's
+  // scratch (free until the first step, and read by its owner alone)
+  uint32_t simd_id = 0u;
+  if constexpr (HINT) {
+    if (tk.hint & kHintPinned) {
+      simd_id = hw_simd_id();
+      if (lane < kBlock / kWave)
+        reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(smem + geom_floats) + lane * walk_scratch_bytes<DIM>())[wave_u] =
+            simd_id;
+    }
+  }
   __syncthreads();
 
   const uint32_t T = (uint32_t)tk.T;
@@ -84,24 +95,34 @@
   // HINT: the control block follows the counter slots (tqueue starts at slot kTaskQueueSlot0)
   unsigned int* const hc = tqueue + kHintBlockWord;
   bool xhold = false;  // this wave holds express walks: nothing from the bulk queue until they have ended
-  // up to H_EPW tasks off the express list into the (empty) ring; false once the list is handed out
-  auto claim_express = [&]() -> bool {
+  // one claim's tasks (express_slot, wos_scene.h: one walk of the solo tier, or up to H_EPW below it) off
+  // the express list into the (empty) ring; false once the list is handed out
+  // (tk: the caller's view of the kernel arguments, as for refill -- inside the walk loop the per-iteration one,
+  // so that the lambda keeps no kernel argument live across the loop)
+  auto claim_express = [&](const DevTasks& tk) -> bool {
     if constexpr (HINT) {
-      uint32_t i0 = 0, n = 0;
+      // (the layout's words are read by lane 0 alone, under its branch, and broadcast: read as wave-uniform
+      // loads they cost every hinted kernel 210-220 B/lane of scratch, make resource-usage)
+      uint32_t nx = 0, epw = 0, n_solo = 0, xg = 0, c = kExpressNone;
       if (lane == 0) {
-        const uint32_t nx = hc[H_NEXPRESS], epw = hc[H_EPW];
-        if (__hip_atomic_load(&hc[H_XCLAIM], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < nx) {
-          i0 = atomicAdd(&hc[H_XCLAIM], epw);
-          n = i0 < nx ? (nx - i0 < epw ? nx - i0 : epw) : 0u;
-          if (n) atomicAdd(&hc[H_CLAIMED], n);
-        }
+        nx = hc[H_NEXPRESS]; epw = hc[H_EPW]; n_solo = hc[H_NSOLO]; xg = hc[H_XG];
+        if (__hip_atomic_load(&hc[H_XCLAIM], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < n_solo + xg)
+          c = atomicAdd(&hc[H_XCLAIM], 1u);
       }
-      i0 = (uint32_t)__builtin_amdgcn_readlane((int)i0, 0);
-      n = (uint32_t)__builtin_amdgcn_readlane((int)n, 0);
-      if (n == 0u) return false;
+      c = (uint32_t)__builtin_amdgcn_readlane((int)c, 0);
+      n_solo = (uint32_t)__builtin_amdgcn_readlane((int)n_solo, 0);
+      xg = (uint32_t)__builtin_amdgcn_readlane((int)xg, 0);
+      if (c >= n_solo + xg) return false;
+      nx = (uint32_t)__builtin_amdgcn_readlane((int)nx, 0);
+      epw = (uint32_t)__builtin_amdgcn_readlane((int)epw, 0);
+      // ring position j holds the claim's entry j: they are j = 0 .. n - 1
       const uint32_t pos = (uint32_t)((lane - head) & (kWave - 1));
-      if (pos < n) {
-        s_t = (*reinterpret_cast<const uint32_t* const*>(hc + H_EXPRESS))[i0 + pos];
+      const uint32_t e = express_slot_g(c, pos, nx, n_solo, epw, tk.hint & kHintStripe, xg);
+      const uint32_t n = (uint32_t)__popcll(__ballot(e != kExpressNone));
+      if (n == 0u) return false;
+      if (lane == 0) atomicAdd(&hc[H_CLAIMED], n);
+      if (e != kExpressNone) {
+        s_t = (*reinterpret_cast<const uint32_t* const*>(hc + H_EXPRESS))[e];
         s_ok = kPtEstimate;
       }
       S = (int)n;
@@ -161,10 +182,23 @@
     }
   };
   if constexpr (HINT) {
-    // express waves: one wave per workgroup (rotating over the SIMDs), which claims until the list is
-    // dry -- the host caps the list at gridDim.x claims, so the first round spreads it over the grid
-    if ((tk.hint & kHintUse) && (uint32_t)wave_u == (blockIdx.x & (kBlock / kWave - 1u)) && hc[H_NEXPRESS] > 0u) {
-      xhold = claim_express();
+    // express waves: one wave per workgroup, which claims until the list is dry -- the build kernel caps
+    // the list at gridDim.x claims, so the first round spreads it over the grid.  Which wave: rotating
+    // over the workgroup's waves with blockIdx (each beside three loaded waves, if wave w sits on SIMD
+    // w), or pinned: the first wave of the workgroup's lowest SIMD (the express waves of a compute
+    // unit's workgroups beside each other)
+    bool xwave = (uint32_t)wave_u == (blockIdx.x & (kBlock / kWave - 1u));
+    if (tk.hint & kHintPinned) {
+      const uint32_t* ids = reinterpret_cast<const uint32_t*>(wscratch);
+      xwave = true;
+      for (int w = 0; w < kBlock / kWave; w++) {
+        const uint32_t o = (uint32_t)__builtin_amdgcn_readfirstlane((int)ids[w]);
+        if (o < simd_id || (o == simd_id && w < wave_u)) xwave = false;
+      }
+      wave_sync();  // (the words are read before the wave's first query overwrites them)
+    }
+    if ((tk.hint & kHintUse) && xwave && hc[H_NEXPRESS] > 0u) {
+      xhold = claim_express(tk);
       if (xhold) wave_priority((int)((tk.hint >> kHintPrioShift) & 3u));
     }
   }
@@ -254,7 +288,7 @@
     }
     if (__ballot(t >= 0) == 0) {
       if (HINT && xhold && S == 0) {  // its express walks have ended: more of them, or the bulk
-        xhold = claim_express();
+        xhold = claim_express(tk);
         if (xhold) continue;
         wave_priority_set(prm.wave_prio);
       }
@@ -289,7 +323,8 @@
     DIAG_COUNT(D_ITERS, 1);
     DIAG_COUNT(D_LANES, __popcll(__ballot(t >= 0)));
 #if WOS_DIAG
-    const bool lone_it = __popcll(__ballot(t >= 0)) <= 2;
+    const int diag_live = __popcll(__ballot(t >= 0));
+    const bool lone_it = diag_live <= 2;
     if (lone_it) DIAG_COUNT(D_L_ITERS, 1);
 #endif
     const int code = walk_iteration<DIM, GG, BSTART, RB, NEU>(sc, prm, G, t >= 0, st, g, ws, ddist, wsteps, firstR, starL,
@@ -364,8 +399,13 @@
       DIAG_COUNT(D_E_ITERS, 1);
       DIAG_COUNT(D_E_LANES, __popcll(__ballot(t >= 0)));
       DIAG_ADD(D_E_LOOP, t_loop);
+      // by the live walks the iteration stepped (before any of them ended) and the state of the bulk queue
+      const int eb = 2 * (diag_live <= 1 ? 0 : diag_live <= 4 ? 1 : 2) + (s_diag[D_QDRY] != 0ull ? 1 : 0);
+      DIAG_COUNT(D_EB_ITERS + eb, 1);
+      DIAG_ADD(D_EB_LOOP + eb, t_loop);
     }
     if (exhausted) {
+      if (lane == 0) DIAG_MAX(D_QDRY, 1);
       DIAG_COUNT(D_XITERS, 1);
       DIAG_COUNT(D_XLANES, __popcll(__ballot(t >= 0)));
       DIAG_ADD(D_XLOOP, t_loop);

@@ -140,6 +140,7 @@ EXPORTS = (
     "wos_adam_step", "wos_siren_fit_run", "wos_siren_fit_run_batches",
     "wos_siren_fit_run_ensemble", "wos_siren_fit_run_batches_ensemble",
     "wos_set_length_hints", "wos_length_hint_stats", "wos_selftest_hint_key",
+    "wos_set_express_layout", "wos_get_express_layout", "wos_express_layout_stats", "wos_selftest_express_slot", "wos_selftest_simd_ids",
 )
 
 # include/wos.h WOS_GFN_*: wos_selftest_gfn's modes and its item and result widths
@@ -210,6 +211,18 @@ def load():
         L.wos_length_hint_stats.argtypes = [C.c_int32, C.POINTER(C.c_int64)]
         L.wos_selftest_hint_key.restype = C.c_int32
         L.wos_selftest_hint_key.argtypes = [C.c_int32]
+    # ... and one built before the express layout
+    if hasattr(L, "wos_set_express_layout"):
+        L.wos_set_express_layout.restype = None
+        L.wos_set_express_layout.argtypes = [C.c_int32] * 3
+        L.wos_get_express_layout.restype = None
+        L.wos_get_express_layout.argtypes = [C.POINTER(C.c_int32)]
+        L.wos_express_layout_stats.restype = C.c_int
+        L.wos_express_layout_stats.argtypes = [C.c_int32, C.POINTER(C.c_int64)]
+        L.wos_selftest_express_slot.restype = C.c_int64
+        L.wos_selftest_express_slot.argtypes = [C.c_uint32, C.c_uint32, C.c_int32, C.c_void_p, C.c_int64]
+        L.wos_selftest_simd_ids.restype = C.c_int
+        L.wos_selftest_simd_ids.argtypes = [C.c_int32, C.POINTER(C.c_uint32)]
     L.wos_default_params.restype = None
     L.wos_default_params.argtypes = [C.POINTER(SolverParams)]
     L.wos_solve.restype = C.c_int

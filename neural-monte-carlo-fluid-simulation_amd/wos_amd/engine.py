@@ -788,6 +788,47 @@ def length_hint_stats(device=0):
     return {"claimed": int(out[0]), "overflow": int(out[1]), "listed": int(out[2]), "express": int(out[3])}
 
 
+def set_express_layout(solo_min=-1, stripe=-1, placement=-1):
+    """Which wave starts which express walk (wos_set_express_layout; a negative value: that one's default): walks
+    of >= solo_min steps a wave each (0: none), the others striped over the waves (1) or in blocks of the sorted
+    list (0), the express wave of a workgroup rotating (0) or pinned to its lowest SIMD (1).  Scheduling only."""
+    _lib.load().wos_set_express_layout(int(solo_min), int(stripe), int(placement))
+
+
+def express_layout():
+    """The express layout in force (wos_get_express_layout)."""
+    out = (C.c_int32 * 3)()
+    _lib.load().wos_get_express_layout(out)
+    return {"solo_min": int(out[0]), "stripe": int(out[1]), "placement": int(out[2])}
+
+
+def express_layout_stats(device=0):
+    """Of the last solve on `device` (waits for it): the entries of its solo tier and the claims its other express
+    entries went to (wos_express_layout_stats)."""
+    out = (C.c_int64 * 2)()
+    check(_lib.load().wos_express_layout_stats(int(device), out), "wos_express_layout_stats")
+    return {"solo": int(out[0]), "claims_below": int(out[1])}
+
+
+def selftest_express_slot(nx, express_per_wave, stripe):
+    """The layout's table for a list of nx entries (host only; wos_selftest_express_slot): rows (n_solo, claim, j,
+    entry) over every solo tier 0..nx, every claim 0..nx+1 and j 0..express_per_wave+1 that holds an entry."""
+    L = _lib.load()
+    rows = int(L.wos_selftest_express_slot(int(nx), int(express_per_wave), int(stripe), None, 0))
+    out = np.empty((rows, 4), np.uint32)
+    got = int(L.wos_selftest_express_slot(int(nx), int(express_per_wave), int(stripe), out.ctypes.data, rows))
+    assert got == rows
+    return out
+
+
+def selftest_simd_ids(device=0):
+    """Of one 256-thread workgroup: the SIMD of each wave as the walk kernel reads it, and each wave's whole
+    hardware id register (wos_selftest_simd_ids)."""
+    out = (C.c_uint32 * 8)()
+    check(_lib.load().wos_selftest_simd_ids(int(device), out), "wos_selftest_simd_ids")
+    return [int(v) for v in out[:4]], [int(v) for v in out[4:]]
+
+
 def selftest_hint_key():
     """Per field of the hint key (host only): does a difference in it alone make two keys unequal?"""
     res = []
