@@ -687,6 +687,56 @@ int wos_selftest_geometry(wos_scene *s, uint32_t schedule, float min_star_radius
                           int32_t kind, const float *items, int64_t n, const uint64_t *masks, int32_t n_masks,
                           float *out, int32_t *tags, uint32_t *sound, uint32_t *counts, int32_t *plan);
 
+/* Device self-test of the source sample of a walk step and of a first ball -- sample_volume_wave,
+ * the wave-cooperative rejection sampler, beside the sequential loop sample_volume it promises to
+ * reproduce -- for the GPU tests (added within ABI 10: a new entry point only; csrc/wos_selftest.hip).
+ * Workgroups of four waves stage the context's PCG32 jump table and the bound table as every kernel
+ * that samples stages them and give each wave its own LDS scratch; wave w takes the 64-bit lane mask
+ * masks[w], its set lanes take the next items in order, and every lane calls sample_volume_wave with
+ * `active` false on clear lanes, as the walk step and the first balls call it.  Clear lanes hold a
+ * ball and a stream that would sample if `active` were not honoured.
+ *   dim      2 or 3
+ *   variant  WOS_SV_FB: the first-ball kernel's instantiation (its block sizes and own generation)
+ *            WOS_SV_RB: the robust kernels' Gfn with `robust` set (scaled balls above mu R = 80)
+ *   need_pdf 0 or 1, as the caller passes it (the walk step 0, the first balls 1)
+ *   items[n][WOS_SV_ITEM]  [0] R  [1] lambda  [2] yukawa (0 or 1)  [3..5] c  [6..8] dir (unit)
+ *   seeds[n]  the 32-bit stream seed; the stream is seeded as the walk seeds its own (Pcg32::seed)
+ * The ball is built as a solve builds it (init, update_ball).  Per item, two results: form 0 the
+ * cooperative form as shipped, form 1 the sequential sample_volume from a copy of the same ball and
+ * stream.  out[n][2][WOS_SV_OUT]: [0] g.r after the clamps  [1] pdf  [2..4] out.  state[n][2]: the
+ * stream state after the call.  iters[n][2]: the iterations the call added.
+ * tags[n]: the regime the cooperative form took for the item (WOS_SV_*), restated from the same
+ * wave-uniform values, with WOS_SV_PUBLISHED or-ed in when the lane wrote its stream to the wave's
+ * scratch -- which the function does on entering a cooperative generation and nowhere else, so the
+ * bit is set on sparse lanes and on dense lanes that continued, and clear on the others.
+ * canary[n_masks][64], one word per lane: on a clear lane the bits WOS_SV_CANARY_* of what the call
+ * changed of that lane's ball, stream, pdf, out or iteration count; on a set lane WOS_SV_CANARY_PDF
+ * when need_pdf is 0 and pdf was written all the same.
+ * plan[8] (may be NULL): the wave size, the minimum and maximum iterations per lane and generation,
+ * the iterations of the own generation (0: none), the sampling lanes it needs, the iterations whose
+ * jump constants are staged in LDS, the iteration limit and the workgroup size, for `dim` and variant.
+ * n = 0 succeeds without a launch.  A null pointer, n < 0, dim outside 2..3, an unknown variant bit
+ * or more set mask bits than items are WOS_E_INVALID. */
+#define WOS_SV_FB 0x1u
+#define WOS_SV_RB 0x2u
+#define WOS_SV_ITEM 9
+#define WOS_SV_OUT 5
+enum { WOS_SV_FALLBACK = 0,  /* off the fast path: the sequential loop (harmonic, 2D mu R >= 80, 3D scaled) */
+       WOS_SV_SOLO,          /* the wave's one sampling lane */
+       WOS_SV_SPARSE,        /* cooperative generations from iteration 0 */
+       WOS_SV_DENSE_OWN,     /* dense wave, accepted inside the own generation */
+       WOS_SV_DENSE_COOP,    /* dense wave, continued cooperatively after it */
+       WOS_SV_PUBLISHED = 0x100 }; /* or-ed in: the lane published its stream for a cooperative generation */
+#define WOS_SV_CANARY_BALL 0x1u
+#define WOS_SV_CANARY_STREAM 0x2u
+#define WOS_SV_CANARY_PDF 0x4u
+#define WOS_SV_CANARY_OUT 0x8u
+#define WOS_SV_CANARY_ITERS 0x10u
+int wos_selftest_sample_volume(int32_t dim, uint32_t variant, int32_t need_pdf, const float *items,
+                               const uint32_t *seeds, int64_t n, const uint64_t *masks, int32_t n_masks,
+                               float *out, uint64_t *state, uint32_t *iters, int32_t *tags, uint32_t *canary,
+                               int32_t *plan, int32_t device);
+
 /* Device self-test of the indexed adjoint's sum kernels (csrc/wos_tape_index.hip) on a
  * caller-supplied index, without a scene: row [n_rows + 1] (row[0] = 0, non-decreasing), id and
  * w [row[n_rows]] (id & 0x7FFFFFFF < n_tasks; bit 31: take c), a and c [n_channels][n_tasks],

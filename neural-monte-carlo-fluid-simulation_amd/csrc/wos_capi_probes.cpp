@@ -263,6 +263,77 @@ int wos_selftest_geometry(wos_scene* s, uint32_t schedule, float min_star_radius
   return WOS_OK;
 }
 
+int wos_selftest_sample_volume(int32_t dim, uint32_t variant, int32_t need_pdf, const float* items,
+                               const uint32_t* seeds, int64_t n, const uint64_t* masks, int32_t n_masks, float* out,
+                               uint64_t* state, uint32_t* iters, int32_t* tags, uint32_t* canary, int32_t* plan,
+                               int32_t device) {
+  if (!items || !seeds || !masks || !out || !state || !iters || !tags || !canary)
+    return fail(WOS_E_INVALID, "wos_selftest_sample_volume: null argument");
+  if (dim != 2 && dim != 3) return fail(WOS_E_INVALID, "wos_selftest_sample_volume: dim must be 2 or 3");
+  if (variant & ~(WOS_SV_FB | WOS_SV_RB))
+    return fail(WOS_E_INVALID, "wos_selftest_sample_volume: variant holds bits beyond WOS_SV_FB | WOS_SV_RB");
+  if (n < 0 || n > (1 << 20) || n_masks < 0 || n_masks > (1 << 20))
+    return fail(WOS_E_INVALID, "wos_selftest_sample_volume: bad item or mask count");
+  // the first item of every wave; the masks name no item beyond the n given
+  std::vector<int32_t> first((size_t)n_masks);
+  int64_t bits = 0;
+  for (int32_t w = 0; w < n_masks; w++) {
+    first[w] = (int32_t)std::min<int64_t>(bits, n);
+    bits += __builtin_popcountll(masks[w]);
+  }
+  if (bits > n)
+    return fail(WOS_E_INVALID, "wos_selftest_sample_volume: the masks' set bits sum to " + std::to_string(bits) +
+                                   ", more than n = " + std::to_string(n));
+  const bool fb = (variant & WOS_SV_FB) != 0, rb = (variant & WOS_SV_RB) != 0;
+  if (plan) wos::sample_volume_plan(dim, fb, plan);
+  if (n == 0 || n_masks == 0) return WOS_OK;
+  if (device < 0 || device >= kMaxDevices) return fail(WOS_E_INVALID, "wos_selftest_sample_volume: no such device");
+  HIP_TRY(hipSetDevice(device));
+  DevCtx& c = g_ctx[device];
+  std::lock_guard<std::mutex> lk(c.mu);
+  WOS_TRY(ctx_ready(c, device));
+  // the jump table and the bound table of a solve's DevParams
+  WOS_TRY(ensure_jump(c, 4096));
+  wos::DevParams dp{};
+  dp.jump = c.d_jump;
+  dp.n_jump = c.n_jump;
+  dp.rej_tab = c.d_rejtab;
+  dp.robust = rb ? 1 : 0;
+  const size_t N = (size_t)n, W = (size_t)n_masks;
+  DevBufs tmp;
+  float *d_items = nullptr, *d_out = nullptr;
+  uint32_t *d_seeds = nullptr, *d_iters = nullptr, *d_canary = nullptr;
+  unsigned long long *d_masks = nullptr, *d_state = nullptr;
+  int32_t *d_first = nullptr, *d_tags = nullptr;
+  HIP_TRY(tmp.get(&d_items, N * WOS_SV_ITEM));
+  HIP_TRY(tmp.get(&d_seeds, N));
+  HIP_TRY(tmp.get(&d_masks, W));
+  HIP_TRY(tmp.get(&d_first, W));
+  HIP_TRY(tmp.get(&d_out, N * 2 * WOS_SV_OUT));
+  HIP_TRY(tmp.get(&d_state, N * 2));
+  HIP_TRY(tmp.get(&d_iters, N * 2));
+  HIP_TRY(tmp.get(&d_tags, N));
+  HIP_TRY(tmp.get(&d_canary, W * 64));
+  HIP_TRY(hipMemcpy(d_items, items, N * WOS_SV_ITEM * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_seeds, seeds, N * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_masks, masks, W * 8, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_first, first.data(), W * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemset(d_out, 0, N * 2 * WOS_SV_OUT * 4));
+  HIP_TRY(hipMemset(d_state, 0, N * 2 * 8));
+  HIP_TRY(hipMemset(d_iters, 0, N * 2 * 4));
+  HIP_TRY(hipMemset(d_tags, 0, N * 4));
+  HIP_TRY(hipMemset(d_canary, 0, W * 64 * 4));
+  HIP_TRY(wos::launch_sample_volume_selftest(dim, rb, fb, dp, need_pdf != 0, d_items, d_seeds, d_masks, d_first,
+                                             n_masks, d_out, d_state, d_iters, d_tags, d_canary, nullptr));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(out, d_out, N * 2 * WOS_SV_OUT * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(state, d_state, N * 2 * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(iters, d_iters, N * 2 * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(tags, d_tags, N * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(canary, d_canary, W * 64 * 4, hipMemcpyDeviceToHost));
+  return WOS_OK;
+}
+
 int wos_selftest_tape_rowsum(const uint32_t* row, int64_t n_rows, const uint32_t* id, const float* w, const float* a,
                              const float* c, int64_t n_tasks, int32_t n_channels, float* out, int32_t* tile_terms,
                              int32_t device) {

@@ -98,6 +98,16 @@ constexpr int kGfnItem = 20, kGfnOut = 32;  // WOS_GFN_ITEM, WOS_GFN_OUT
 hipError_t launch_gfn_selftest(int dim, int mode, const float* items, int64_t n, float* out, hipStream_t s);
 hipError_t launch_freespace_selftest(const float* items, int64_t n, int yukawa, float* out, hipStream_t s);
 
+// probe of the source sample (wos_selftest.hip; include/wos.h wos_selftest_sample_volume): the
+// instantiation sample_volume_wave<dim, rb, fb>; prm: jump, n_jump (>= 2 kRejMax + 2) and rej_tab as a
+// solve sets them; wave w takes lane mask masks[w], its set lanes the items first[w], first[w] + 1,
+// ...; out [n][2][WOS_SV_OUT], state and iters [n][2], tags [n], canary [n_masks][64]
+hipError_t launch_sample_volume_selftest(int dim, bool rb, bool fb, const DevParams& prm, int need_pdf,
+                                         const float* items, const uint32_t* seeds, const unsigned long long* masks,
+                                         const int32_t* first, int n_masks, float* out, unsigned long long* state,
+                                         uint32_t* iters, int32_t* tags, uint32_t* canary, hipStream_t s);
+void sample_volume_plan(int dim, bool fb, int32_t* out);  // wos_selftest_sample_volume's plan[0..7]
+
 // boundary value caching (wos_bvc.hip), 2D
 hipError_t launch_bvc_point_info(const DevScene& sc, const float* pts, int64_t n, float* dd, float* nd,
                                  int32_t* inside, float* src, hipStream_t s);

@@ -5,7 +5,9 @@
 // sampler against the oracle's sequential loop without a full solve.  And a probe of the rejection
 // sampler's decision functions (wos_selftest_rejection): the edge of each one over every draw a
 // stream can produce; and a probe of the
-// Green's-function members of the ball (wos_selftest_gfn).  A translation unit of its own: what a unit instantiates changes its
+// Green's-function members of the ball (wos_selftest_gfn); and a probe of the source sample
+// (wos_selftest_sample_volume): sample_volume_wave under chosen lane masks beside the sequential
+// sample_volume.  A translation unit of its own: what a unit instantiates changes its
 // kernels' inlining and scratch (DESIGN.md "Kernel variants"), and these instantiations must not
 // touch the five kernel units.
 #include "wos_device.h"
@@ -721,6 +723,156 @@ hipError_t launch_geometry_selftest(int dim, int kind, const DevScene& sc, const
   else
     launch_geometry_kind<3, false>(kind, sc, prm, items, masks, first, n_masks, shmem, geom_floats, out, tags, sound, counts, s);
   return hipGetLastError();
+}
+
+// ---- the source sample (wos_selftest_sample_volume) ----------------------------------------------
+// Workgroups of kBlock threads stage the jump constants and the bound table as every kernel that
+// samples does (stage_rej_jump) and give each wave a RejLDS; wave w of the grid takes lane mask w, its
+// set lanes the next items in order.  Every lane builds a ball as a solve builds it (init,
+// update_ball) -- clear lanes a ball that would sample if `active` were not honoured -- and calls
+// sample_volume_wave convergently, clear lanes with active false, as walk_iteration and first_balls
+// call it.  Beside it each set lane runs the sequential sample_volume from a copy of the same ball
+// and stream.  The regime tag restates sample_volume_wave's own choice from the same wave-uniform
+// values; the canary words compare what a call had no business touching, bit for bit.
+namespace {
+
+template <int DIM, bool RB>
+__device__ __forceinline__ bool sv_same_ball(const Gfn<DIM, RB>& a, const Gfn<DIM, RB>& b) {
+  bool same = a.yukawa == b.yukawa;
+  const auto eq = [](float x, float y) { return __float_as_uint(x) == __float_as_uint(y); };
+  for (int k = 0; k < DIM; k++) same = same && eq(a.c[k], b.c[k]) && eq(a.yVol[k], b.yVol[k]) && eq(a.ySurf[k], b.ySurf[k]);
+  return same && eq(a.R, b.R) && eq(a.r, b.r) && eq(a.lambda, b.lambda) && eq(a.sqrtLambda, b.sqrtLambda) &&
+         eq(a.muR, b.muR) && eq(a.A0, b.A0) && eq(a.A1, b.A1) && eq(a.B0, b.B0) && eq(a.B1, b.B1);
+}
+
+template <int DIM, bool RB, bool FB>
+__global__ __launch_bounds__(kBlock) void wos_sample_volume_selftest_kernel(
+    const DevParams prm, int need_pdf, const float* __restrict__ items, const uint32_t* __restrict__ seeds,
+    const unsigned long long* __restrict__ masks, const int32_t* __restrict__ first, int n_masks,
+    float* __restrict__ out, unsigned long long* __restrict__ state, uint32_t* __restrict__ iters,
+    int32_t* __restrict__ tags, uint32_t* __restrict__ canary) {
+  __shared__ RejLDS rej[kBlock / kWave];
+  const int lane = threadIdx.x & (kWave - 1);
+  stage_rej_jump(prm);
+  __syncthreads();
+  const int wave_u = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / kWave));
+  const int w = (int)blockIdx.x * (kBlock / kWave) + wave_u;
+  if (w >= n_masks) return;  // wave-uniform; no block barrier follows
+  const unsigned long long mask = masks[w];
+  const bool on = ((mask >> lane) & 1ull) != 0;
+  const int64_t i = (int64_t)first[w] + __popcll(mask & ((1ull << lane) - 1ull));
+  // clear lanes: a Yukawa ball on the fast path of either dimension, and a live stream
+  float R = 0.5f, lam = 50.0f, c[DIM], dir[DIM];
+  bool yuk = true;
+  uint32_t seed = 0x9E3779B9u + (uint32_t)lane;
+  for (int k = 0; k < DIM; k++) { c[k] = 0.25f * (float)(k + 1); dir[k] = k == 0 ? 1.0f : 0.0f; }
+  if (on) {
+    const float* it = items + i * WOS_SV_ITEM;
+    R = it[0]; lam = it[1]; yuk = it[2] != 0.0f; seed = seeds[i];
+    for (int k = 0; k < DIM; k++) { c[k] = it[3 + k]; dir[k] = it[6 + k]; }
+  }
+  Gfn<DIM, RB> g;
+  g.muR = g.A0 = g.A1 = g.B0 = g.B1 = 0.0f;
+  g.init(yuk, lam);
+  g.update_ball(c, R, RB);
+  Pcg32 s;
+  s.seed((uint64_t)seed);
+  const float pdf0 = -1234.5f;  // the canary value of pdf and out
+  const Gfn<DIM, RB> g0 = g;
+  const Pcg32 s0 = s;
+
+  // the sequential form first, on copies (it shares nothing with the wave form but the staged tables)
+  Gfn<DIM, RB> gq = g0;
+  Pcg32 sq = s0;
+  float pdfq = pdf0, outq[DIM];
+  uint32_t itq = 0;
+  for (int k = 0; k < DIM; k++) outq[k] = pdf0;
+  if (on) sample_volume<DIM>(prm, gq, dir, sq, &pdfq, outq, &itq, need_pdf != 0);
+
+  float pdfw = pdf0, outw[DIM];
+  uint32_t itw = 0;
+  for (int k = 0; k < DIM; k++) outw[k] = pdf0;
+  // a lane publishes its stream in the wave's scratch only when it enters a cooperative generation:
+  // the one trace of the regime the function itself leaves (no stream starts at the mark: 2^-64)
+  constexpr unsigned long long kUnpublished = 0xFFFFFFFFFFFFFFFFull;
+  rej[wave_u].s0[lane] = kUnpublished;
+  wave_sync();
+  sample_volume_wave<DIM, RB, FB>(prm, on, g, dir, s, &pdfw, outw, &itw, need_pdf != 0, &rej[wave_u], lane);
+  wave_sync();
+  const bool published = rej[wave_u].s0[lane] != kUnpublished;
+
+  // sample_volume_wave's regime
+  const bool coop = on && g0.yukawa && (DIM == 3 ? !g0.scaled() : g0.muR < 80.0f);
+  const int nc = __popcll(__ballot(coop));
+  const bool dense = WOS_REJ_OWN != 0 && kRejOwnD<DIM, FB> > 0 && nc >= kRejOwnMin;
+  const int tag = !coop ? WOS_SV_FALLBACK
+                  : nc == 1 ? WOS_SV_SOLO
+                  : !dense ? WOS_SV_SPARSE
+                  : ((int)itw <= kRejOwnD<DIM, FB> ? WOS_SV_DENSE_OWN : WOS_SV_DENSE_COOP);
+
+  uint32_t cw = 0;
+  const bool pdf_same = __float_as_uint(pdfw) == __float_as_uint(pdf0);
+  if (!on) {
+    if (!sv_same_ball<DIM, RB>(g, g0)) cw |= WOS_SV_CANARY_BALL;
+    if (s.state != s0.state) cw |= WOS_SV_CANARY_STREAM;
+    if (!pdf_same) cw |= WOS_SV_CANARY_PDF;
+    for (int k = 0; k < DIM; k++)
+      if (__float_as_uint(outw[k]) != __float_as_uint(pdf0)) cw |= WOS_SV_CANARY_OUT;
+    if (itw != 0u) cw |= WOS_SV_CANARY_ITERS;
+  } else if (!need_pdf && !pdf_same) {
+    cw |= WOS_SV_CANARY_PDF;
+  }
+  canary[(int64_t)w * kWave + lane] = cw;
+  if (!on) return;
+  float* o = out + i * 2 * WOS_SV_OUT;
+  for (int k = 0; k < 2 * WOS_SV_OUT; k++) o[k] = 0.0f;
+  o[0] = g.r; o[1] = pdfw;
+  o[WOS_SV_OUT + 0] = gq.r; o[WOS_SV_OUT + 1] = pdfq;
+  for (int k = 0; k < DIM; k++) { o[2 + k] = outw[k]; o[WOS_SV_OUT + 2 + k] = outq[k]; }
+  state[i * 2 + 0] = s.state; state[i * 2 + 1] = sq.state;
+  iters[i * 2 + 0] = itw; iters[i * 2 + 1] = itq;
+  tags[i] = tag | (published ? WOS_SV_PUBLISHED : 0);
+}
+
+template <int DIM, bool RB, bool FB>
+void launch_sample_volume_variant(const DevParams& prm, int need_pdf, const float* items, const uint32_t* seeds,
+                                  const unsigned long long* masks, const int32_t* first, int n_masks, float* out,
+                                  unsigned long long* state, uint32_t* iters, int32_t* tags, uint32_t* canary,
+                                  hipStream_t s) {
+  const dim3 grid((n_masks + kBlock / kWave - 1) / (kBlock / kWave)), blk(kBlock);
+  hipLaunchKernelGGL((wos_sample_volume_selftest_kernel<DIM, RB, FB>), grid, blk, 0, s, prm, need_pdf, items, seeds,
+                     masks, first, n_masks, out, state, iters, tags, canary);
+}
+
+}  // namespace
+
+hipError_t launch_sample_volume_selftest(int dim, bool rb, bool fb, const DevParams& prm, int need_pdf,
+                                         const float* items, const uint32_t* seeds, const unsigned long long* masks,
+                                         const int32_t* first, int n_masks, float* out, unsigned long long* state,
+                                         uint32_t* iters, int32_t* tags, uint32_t* canary, hipStream_t s) {
+#define WOS_SV_LAUNCH(D, R, F) \
+  launch_sample_volume_variant<D, R, F>(prm, need_pdf, items, seeds, masks, first, n_masks, out, state, iters, tags, canary, s)
+  if (dim == 2) {
+    if (rb) { if (fb) WOS_SV_LAUNCH(2, true, true); else WOS_SV_LAUNCH(2, true, false); }
+    else { if (fb) WOS_SV_LAUNCH(2, false, true); else WOS_SV_LAUNCH(2, false, false); }
+  } else {
+    if (rb) { if (fb) WOS_SV_LAUNCH(3, true, true); else WOS_SV_LAUNCH(3, true, false); }
+    else { if (fb) WOS_SV_LAUNCH(3, false, true); else WOS_SV_LAUNCH(3, false, false); }
+  }
+#undef WOS_SV_LAUNCH
+  return hipGetLastError();
+}
+
+// the sampler's schedule constants for dim and the first-ball (fb) or walk instantiation
+void sample_volume_plan(int dim, bool fb, int32_t* out) {
+  out[0] = kWave;
+  out[1] = dim == 2 ? kRejBmin<2, false> : (fb ? kRejBmin<3, true> : kRejBmin<3, false>);
+  out[2] = kRejBcap;
+  out[3] = WOS_REJ_OWN != 0 ? (dim == 2 ? kRejOwnD<2, false> : (fb ? kRejOwnD<3, true> : kRejOwnD<3, false>)) : 0;
+  out[4] = kRejOwnMin;
+  out[5] = WOS_REJ_JUMP_LDS > 0 ? kRejJumpLds : 0;
+  out[6] = kRejMax;
+  out[7] = kBlock;
 }
 
 }  // namespace wos

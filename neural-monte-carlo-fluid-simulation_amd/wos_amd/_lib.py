@@ -133,6 +133,7 @@ EXPORTS = (
     "wos_tape_vjp", "wos_tape_read",
     "wos_tape_index_build", "wos_tape_index_get_info", "wos_tape_index_read", "wos_tape_vjp_indexed",
     "wos_selftest_tape_rowsum", "wos_selftest_rejection", "wos_selftest_geometry", "wos_selftest_gfn",
+    "wos_selftest_sample_volume",
     "wos_scene_query",
     "wos_siren_eval", "wos_selftest_siren_layer",
     "wos_siren_vjp", "wos_selftest_siren_vjp_layer",
@@ -146,6 +147,15 @@ EXPORTS = (
 # include/wos.h WOS_GFN_*: wos_selftest_gfn's modes and its item and result widths
 GFN_HARMONIC, GFN_YUKAWA, GFN_ROBUST = 0, 1, 2
 GFN_ITEM, GFN_OUT = 20, 32
+
+# include/wos.h WOS_SV_*: wos_selftest_sample_volume's variant bits, widths, regime tags and canary bits
+SV_FB, SV_RB = 1, 2
+SV_ITEM, SV_OUT = 9, 5
+SV_FALLBACK, SV_SOLO, SV_SPARSE, SV_DENSE_OWN, SV_DENSE_COOP = range(5)
+SV_PUBLISHED = 0x100
+SV_CANARY = {"ball": 0x1, "stream": 0x2, "pdf": 0x4, "out": 0x8, "iters": 0x10}
+# plan[k] of wos_selftest_sample_volume
+SV_PLAN = ("wave", "bmin", "bcap", "own", "own_min", "jump_lds", "limit", "block")
 
 # include/wos.h WOS_GEO_*: wos_selftest_geometry's kinds, regime tags, soundness bits and count slots
 GEO_RAY, GEO_STAR, GEO_DIRICHLET = 0, 1, 2
@@ -337,6 +347,10 @@ def load():
         L.wos_selftest_geometry.argtypes = [C.c_void_p, C.c_uint32, C.c_float, C.c_float, C.c_int32, C.c_void_p,
                                             C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_void_p]
+    L.wos_selftest_sample_volume.restype = C.c_int
+    L.wos_selftest_sample_volume.argtypes = [C.c_int32, C.c_uint32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,
+                                             C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_int32]
     L.wos_last_error.restype = C.c_char_p
     L.wos_last_error.argtypes = []
     L.wos_selftest_gfn.restype = C.c_int

@@ -877,6 +877,34 @@ def selftest_gfn(dim, mode, items, device=0):
     return out
 
 
+def selftest_sample_volume(dim, items, seeds, masks, *, fb=False, rb=False, need_pdf=False, device=0):
+    """The source sample on items float32 [n, SV_ITEM] with stream seeds uint32 [n], wave w of the probe
+    under lane mask masks[w] (uint64), run by the kernels' own device code (wos_selftest_sample_volume;
+    layouts in include/wos.h): sample_volume_wave<dim, rb, fb> as shipped (form 0) beside the sequential
+    sample_volume (form 1).  Returns a dict: r, pdf float32 [n, 2], out float32 [n, 2, 3], state uint64
+    [n, 2], iters uint32 [n, 2], tags int32 [n], canary uint32 [len(masks), 64] and plan (SV_PLAN)."""
+    items = np.ascontiguousarray(items, dtype=np.float32).reshape(-1, _lib.SV_ITEM)
+    seeds = np.ascontiguousarray(seeds, dtype=np.uint32).reshape(-1)
+    masks = np.ascontiguousarray(masks, dtype=np.uint64).reshape(-1)
+    n = items.shape[0]
+    if seeds.size != n:
+        raise WosError("items and seeds must have one length")
+    out = np.zeros((n, 2, _lib.SV_OUT), np.float32)
+    state = np.zeros((n, 2), np.uint64)
+    iters = np.zeros((n, 2), np.uint32)
+    tags = np.zeros(n, np.int32)
+    canary = np.zeros((masks.size, 64), np.uint32)
+    plan = np.zeros(8, np.int32)
+    variant = (_lib.SV_FB if fb else 0) | (_lib.SV_RB if rb else 0)
+    check(_lib.load().wos_selftest_sample_volume(int(dim), variant, int(bool(need_pdf)), items.ctypes.data,
+                                                 seeds.ctypes.data, n, masks.ctypes.data, masks.size,
+                                                 out.ctypes.data, state.ctypes.data, iters.ctypes.data,
+                                                 tags.ctypes.data, canary.ctypes.data, plan.ctypes.data, device),
+          "wos_selftest_sample_volume")
+    return {"r": out[:, :, 0], "pdf": out[:, :, 1], "out": out[:, :, 2:5], "state": state, "iters": iters,
+            "tags": tags, "canary": canary, "plan": dict(zip(_lib.SV_PLAN, (int(v) for v in plan)))}
+
+
 def selftest_lhs(key, gidx, n_pairs, dim, jump_lds=True, device=0):
     """The first-ball kernel's stratified samples of the point indices gidx, built by the
     kernel's own device code (wos_selftest_lhs): float32 [n, 2 n_pairs, dim - 1]."""

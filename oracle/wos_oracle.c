@@ -2554,3 +2554,35 @@ int oracle_gfn(int dim, int mode, const float *items, int64_t n, float *out)
     g_robust = 0;
     return 0;
 }
+
+/* ========================================================================= */
+/* The source sample on caller-supplied items (tests/test_sample_volume_cpu.py,
+ * tests/test_gpu_sample_volume.py): gfn_sample_volume above -- the reference's plain loop, no
+ * screen, no fast path -- on a ball and a stream set up as the solves set them up (gfn_init,
+ * gfn_update_ball, pcg_seed), in det-math mode.  Layouts: wos_oracle.h. */
+/* ========================================================================= */
+int oracle_sample_volume(int dim, int robust, const float *items, const uint32_t *seeds, int64_t n, float *out,
+                         uint64_t *state, uint32_t *iters)
+{
+    if (!items || !seeds || !out || !state || !iters || n < 0) return -1;
+    if (dim != 2 && dim != 3) return -2;
+    g_libm = 0;
+    g_robust = robust != 0;
+    for (int64_t i = 0; i < n; i++) {
+        const float *it = items + ORACLE_SV_ITEM * i;
+        float *o = out + ORACLE_SV_OUT * i;
+        float c[3] = {0, 0, 0}, dir[3] = {0, 0, 0}, sp[3] = {0, 0, 0}, pdf = 0.0f;
+        for (int k = 0; k < dim; k++) { c[k] = it[3 + k]; dir[k] = it[6 + k]; }
+        gfn_t g;
+        gfn_init(&g, dim, it[2] != 0.0f, it[1]);
+        gfn_update_ball(&g, c, it[0]);
+        pcg_t s; pcg_seed(&s, seeds[i], 1u);
+        uint64_t cnt = 0;
+        gfn_sample_volume(&g, dir, &s, &pdf, sp, &cnt);
+        o[0] = g.r; o[1] = pdf; o[2] = sp[0]; o[3] = sp[1]; o[4] = dim == 3 ? sp[2] : 0.0f;
+        state[i] = s.state;
+        iters[i] = (uint32_t)cnt;
+    }
+    g_robust = 0;
+    return 0;
+}

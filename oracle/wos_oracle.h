@@ -159,6 +159,19 @@ int oracle_dirichlet_dists(const oracle_scene_desc *scene, const float *x, int64
 #define ORACLE_GFN_OUT 32
 int oracle_gfn(int dim, int mode, const float *items, int64_t n, float *out);
 
+/* The source sample (sampleVolume + rejectionSampleGreensFn) on n caller-supplied items: the ball
+ * and the stream set up as the solves set them up, det-math mode, `robust` as oracle_params'
+ * robust_float.  An item is ORACLE_SV_ITEM floats:
+ *   [0] R  [1] lambda  [2] yukawa (0 or 1)  [3..5] c  [6..8] dir (unit)
+ * seeds[n]: the 32-bit seed of the item's PCG32 stream.  A result is ORACLE_SV_OUT floats:
+ *   [0] r after the clamps  [1] pdf (of the last sampled radius, before the clamps)  [2..4] the point
+ * state[n]: the stream state after the call; iters[n]: the loop's iterations (0 for the 3D harmonic
+ * closed form).  Returns 0, -1 (null or n < 0) or -2 (dim). */
+#define ORACLE_SV_ITEM 9
+#define ORACLE_SV_OUT 5
+int oracle_sample_volume(int dim, int robust, const float *items, const uint32_t *seeds, int64_t n, float *out,
+                         uint64_t *state, uint32_t *iters);
+
 double oracle_bessel(int which, double x, int math_mode); /* 0:i0 1:i1 2:k0 3:k1 */
 double oracle_math(int which, double x, int math_mode);   /* 0 exp 1 log 2 sin 3 cos 4 atan, f32: 10 expf 11 logf 12 sinf 13 cosf 14 cbrtf */
 uint32_t oracle_seed32(uint64_t key, uint64_t idx, uint64_t pair, uint32_t tag);

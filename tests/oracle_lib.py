@@ -114,6 +114,9 @@ def lib():
         L.oracle_dirichlet_dists.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
         L.oracle_gfn.restype = C.c_int
         L.oracle_gfn.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]
+        L.oracle_sample_volume.restype = C.c_int
+        L.oracle_sample_volume.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                           C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -368,3 +371,24 @@ def gfn(dim, mode, items):
     if rc != 0:
         raise RuntimeError(f"oracle_gfn failed: {rc}")
     return out
+
+
+SV_ITEM, SV_OUT = 9, 5  # oracle/wos_oracle.h ORACLE_SV_ITEM, ORACLE_SV_OUT
+
+
+def sample_volume(dim, items, seeds, robust=False):
+    """oracle_sample_volume: the reference's plain rejection loop on items float32 [n, SV_ITEM]
+    with stream seeds uint32 [n] (layouts in oracle/wos_oracle.h).  Returns a dict: r, pdf float32
+    [n], out float32 [n, 3], state uint64 [n], iters uint32 [n]."""
+    items = np.ascontiguousarray(items, dtype=np.float32).reshape(-1, SV_ITEM)
+    seeds = np.ascontiguousarray(seeds, dtype=np.uint32).reshape(-1)
+    n = items.shape[0]
+    assert seeds.size == n
+    out = np.zeros((n, SV_OUT), np.float32)
+    state = np.zeros(n, np.uint64)
+    iters = np.zeros(n, np.uint32)
+    rc = lib().oracle_sample_volume(int(dim), int(bool(robust)), items.ctypes.data, seeds.ctypes.data, n,
+                                    out.ctypes.data, state.ctypes.data, iters.ctypes.data)
+    if rc != 0:
+        raise RuntimeError(f"oracle_sample_volume failed: {rc}")
+    return {"r": out[:, 0], "pdf": out[:, 1], "out": out[:, 2:5], "state": state, "iters": iters}
